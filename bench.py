@@ -15,7 +15,15 @@ obstacles), --cfg 6 (the detect_collision.py floor point cloud as an
 fcl::OcTree), --cfg 7 (cfg3 with the Panda links as BVH triangle meshes,
 convex=False), --cfg 5 (RRTConnect plan() end to end: a step is one plan()).
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--cpu-sample S] [--cfg C]
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds what takes runs of its own: the CPU oracle baseline and its
+cross-check of the GPU results (--cpu-sample, --cpu-plans), the per-stage
+profile passes of --host / --capi-multi and their single-world check, and the
+one-state round trip of --cfg 5.  --dump-outputs DIR writes what the last timed
+step returned (flags and pair masks; cfg5: the path) as DIR/<name>.npy.
+
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--cfg C] [--dump-outputs DIR]
+        python bench.py --full [--cpu-sample S] ...
         torchrun --nproc-per-node N bench.py --gpus N ...
         python bench.py --host ...          (the batch in host memory: numpy in / numpy out, PCIe timed)
         python bench.py --capi-multi N ...  (one process, N GPUs through mpg_collide_batch_multi_device)
@@ -60,11 +68,12 @@ def parse():
     p.add_argument("--goal", default="far", help="cfg5 goal (scenes.PLAN_GOALS)")
     p.add_argument("--spec-nodes", type=int, default=None, help="cfg5: outcome-tree nodes explored before each batch")
     p.add_argument("--cpu-plans", type=int, default=-1,
-                   help="cfg5: plans timed with the CPU oracle checker (-1: the same seeds as the GPU run, 0: none)")
+                   help="cfg5 with --full: plans timed with the CPU oracle checker (-1: the same seeds as the GPU "
+                        "run, 0: none)")
     p.add_argument("--per-gpu", type=int, default=0, help="configs per GPU per step (default: BASELINE size)")
     p.add_argument("--cpu-sample", type=int, default=1 << 20,
-                   help="configs timed on the CPU oracle for cpu_baseline on all the box's cores (rank 0, N=1 only; "
-                        "0 = skip); a quarter of them on one core")
+                   help="with --full: configs timed on the CPU oracle for cpu_baseline on all the box's cores "
+                        "(rank 0, N=1 only; 0 = skip); a quarter of them on one core")
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="threads of the all-core CPU baseline (0: the box's share, OMP_NUM_THREADS or nproc)")
     p.add_argument("--gather", action="store_true", help="also time an all-gather of the results to every rank")
@@ -75,7 +84,40 @@ def parse():
     p.add_argument("--host", action="store_true",
                    help="the batch in host memory: numpy in, numpy out through PlanningWorld.collide_batch "
                         "(mpg_collide_batch with MPG_MEM_HOST, PCIe both ways inside the timed step)")
+    p.add_argument("--full", action="store_true",
+                   help="also what the headline figure does not need: the CPU oracle baseline and its cross-check "
+                        "of the GPU results, the profile passes and single-world check of --host / --capi-multi, "
+                        "the one-state round trip of --cfg 5")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step returned as DIR/<name>.npy (float32 flags, "
+                        "float64 pair-mask words; at most 64 MB: above that a fixed seeded sample of rows)")
     return p.parse_args()
+
+
+DUMP_LIMIT = 63 * 10**6  # bytes of array data --dump-outputs writes at most: under 64 MB with the .npy headers
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT):
+    """--dump-outputs: `arrays` (name -> torch tensor or numpy array, what the
+    timed path returned in its last step) as DIR/<name>.npy.  8-bit flags as
+    float32, 32-bit mask words (read as unsigned) and doubles as float64: every
+    value is held exactly.  Above `limit` bytes in all, every array keeps the
+    same fraction of its rows, drawn by default_rng(0) and kept in order, so
+    arrays with equal row counts keep the same rows and two builds the same
+    sample."""
+    os.makedirs(dirname, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        if a.dtype == np.int32:
+            a = a.view(np.uint32)
+        out[name] = (a, np.float32 if a.dtype.itemsize == 1 else np.float64)
+    total = sum(a.size * np.dtype(t).itemsize for a, t in out.values())
+    for name, (a, t) in out.items():
+        if total > limit and len(a):
+            keep = max(1, len(a) * limit // total)
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(t))
 
 
 def launch_ranks(n: int) -> int:
@@ -257,7 +299,10 @@ def main():
         result["gather_distance_ms"] = gather_dist_ms
         result["gather_distance_bytes_per_rank"] = n * 24
 
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.dump_outputs:  # the last timed step's results (each rank its shard)
+        sfx = f"_rank{rank}" if world > 1 else ""
+        dump_outputs(args.dump_outputs, {"flags" + sfx: flags, "masks" + sfx: masks}, DUMP_LIMIT // world)
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         k = args.cpu_sample if cfg != 7 else min(args.cpu_sample, 1 << 13)  # the mesh oracle is ~100x slower
         threads = args.cpu_threads or box_threads()
         result["cpu_baseline"] = cpu_baseline(cfg, q_host[:k], flags, masks, threads)
@@ -316,27 +361,35 @@ def capi_multi_main(args):
         step()
     sync_all()
     elapsed = time.perf_counter() - t0
-    worlds[0].profile_enable(True)
-    worlds[0].profile_read()
-    prof_steps = max(1, min(args.steps, 5))
-    for _ in range(prof_steps):
-        step()
-    sync_all()
-    prof = worlds[0].profile_read()
-    worlds[0].profile_enable(False)
-    st = {k: {"ms_per_launch": v[0] / max(v[1], 1), "launches_per_step": v[1] / prof_steps,
-              "units_per_launch": v[2] / max(v[1], 1)} for k, v in prof.items()}
-    roofline, valu = rooflines(st, cfg, dim, W)
-    ok = True
-    if N > 1 or args.gather:  # shard 0 against a plain single-world call on the same data
-        f0 = torch.empty_like(fl[0])
-        m0 = torch.empty_like(mk[0])
-        worlds[0].collide_batch_device(qs[0].data_ptr(), n, f0.data_ptr(), m0.data_ptr(),
-                                       torch.cuda.current_stream(0).cuda_stream)
-        sync_all()
-        ok = bool(torch.equal(f0, fl[0]) and torch.equal(m0, mk[0]))
+    if args.dump_outputs:
+        out = {f"{nm}_gpu{k}": a[k] for k in range(N) for nm, a in (("flags", fl), ("masks", mk))}
         if args.gather:
-            ok &= bool(torch.equal(gf[:n], fl[0]) and torch.equal(gm[:n], mk[0]))
+            out.update(flags_gathered=gf, masks_gathered=gm)
+        dump_outputs(args.dump_outputs, out)
+    extra = {}
+    if args.full:  # a profile pass and the single-world check: runs of their own
+        worlds[0].profile_enable(True)
+        worlds[0].profile_read()
+        prof_steps = max(1, min(args.steps, 5))
+        for _ in range(prof_steps):
+            step()
+        sync_all()
+        prof = worlds[0].profile_read()
+        worlds[0].profile_enable(False)
+        st = {k: {"ms_per_launch": v[0] / max(v[1], 1), "launches_per_step": v[1] / prof_steps,
+                  "units_per_launch": v[2] / max(v[1], 1)} for k, v in prof.items()}
+        roofline, valu = rooflines(st, cfg, dim, W)
+        ok = True
+        if N > 1 or args.gather:  # shard 0 against a plain single-world call on the same data
+            f0 = torch.empty_like(fl[0])
+            m0 = torch.empty_like(mk[0])
+            worlds[0].collide_batch_device(qs[0].data_ptr(), n, f0.data_ptr(), m0.data_ptr(),
+                                           torch.cuda.current_stream(0).cuda_stream)
+            sync_all()
+            ok = bool(torch.equal(f0, fl[0]) and torch.equal(m0, mk[0]))
+            if args.gather:
+                ok &= bool(torch.equal(gf[:n], fl[0]) and torch.equal(gm[:n], mk[0]))
+        extra = {"shard0_matches_single_world_call": ok, "roofline": roofline, "valu_roofline": valu}
     result = {
         "metric": "configs/sec full collide() Panda-7DoF+10 boxes" if cfg == 3 else f"configs/sec collide() cfg{cfg}",
         "value": n * N * args.steps / elapsed, "unit": "configs/s", "n_gpus": N, "steps": args.steps,
@@ -348,8 +401,7 @@ def capi_multi_main(args):
                    "configs_per_gpu": n, "pairs": n_pairs, "mask_words": W,
                    "parallelism": f"capi-multi x{N}: one process, one host thread per GPU "
                                   f"(mpg_collide_batch_multi_device){', gather into GPU 0' if args.gather else ''}"},
-        "shard0_matches_single_world_call": ok,
-        "roofline": roofline, "valu_roofline": valu, "lib_hash": lib_hash(),
+        **extra, "lib_hash": lib_hash(),
     }
     print(json.dumps(result), flush=True)
 
@@ -378,18 +430,27 @@ def host_main(args, world, rank, local, backend, cfg, n, w, q_host, dim, W, n_pa
     if dist.is_initialized():
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    # the per-stage kernel times (HIP events on the launch streams) from a
-    # few more calls, outside the timed region: the events cost host time in
-    # the launching thread, which the pipeline would show
-    w.profile_enable(True)
-    w.profile_read()
-    for _ in range(max(1, min(args.steps, 5))):
-        w.collide_batch(q_host)
-    prof = w.profile_read()
-    w.profile_enable(False)
-    prof_steps = max(1, min(args.steps, 5))
-    st = {k: {"ms_per_launch": v[0] / max(v[1], 1), "launches_per_step": v[1] / prof_steps,
-              "units_per_launch": v[2] / max(v[1], 1)} for k, v in prof.items()}
+    if args.dump_outputs:
+        sfx = f"_rank{rank}" if world > 1 else ""
+        dump_outputs(args.dump_outputs, {"flags" + sfx: flags, "masks" + sfx: masks}, DUMP_LIMIT // world)
+    extra = {}
+    if args.full:
+        # the per-stage kernel times (HIP events on the launch streams) from a
+        # few more calls, outside the timed region: the events cost host time in
+        # the launching thread, which the pipeline would show
+        w.profile_enable(True)
+        w.profile_read()
+        for _ in range(max(1, min(args.steps, 5))):
+            w.collide_batch(q_host)
+        prof = w.profile_read()
+        w.profile_enable(False)
+        prof_steps = max(1, min(args.steps, 5))
+        st = {k: {"ms_per_launch": v[0] / max(v[1], 1), "launches_per_step": v[1] / prof_steps,
+                  "units_per_launch": v[2] / max(v[1], 1)} for k, v in prof.items()}
+        roofline, valu = rooflines(st, cfg, dim, W)
+        extra = {"roofline": roofline, "valu_roofline": valu,
+                 "stages": {k: {"ms_per_step": st[k]["ms_per_launch"] * st[k]["launches_per_step"],
+                                "units_per_launch": st[k]["units_per_launch"]} for k in STAGES}}
     if dist.is_initialized():
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local}" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -399,7 +460,6 @@ def host_main(args, world, rank, local, backend, cfg, n, w, q_host, dim, W, n_pa
     # mask rows of the colliding configurations out
     pcie_bytes = n * (8 * dim) + n + n * rate * 4 * W
     step_s = elapsed / args.steps
-    roofline, valu = rooflines(st, cfg, dim, W)
     result = {
         "metric": ("configs/sec full collide() Panda-7DoF+10 boxes" if cfg == 3 else f"configs/sec collide() cfg{cfg}")
         + ", host buffers (numpy in/out, PCIe included)",
@@ -418,13 +478,10 @@ def host_main(args, world, rank, local, backend, cfg, n, w, q_host, dim, W, n_pa
                  "note": "q rows in (8*dof B) + flags (1 B) + packed mask rows of colliding configurations "
                          "(4W B each) out; peak = PCIe Gen5 x16 spec (MI355X_MICROARCH.md), one link shared by "
                          "both directions on this box (profiles/r06a/host_probe.json)"},
-        "roofline": roofline,
-        "valu_roofline": valu,
+        **extra,
         "lib_hash": lib_hash(),
-        "stages": {k: {"ms_per_step": st[k]["ms_per_launch"] * st[k]["launches_per_step"],
-                       "units_per_launch": st[k]["units_per_launch"]} for k in STAGES},
     }
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         k = args.cpu_sample if cfg != 7 else min(args.cpu_sample, 1 << 13)
         threads = args.cpu_threads or box_threads()
         result["cpu_baseline"] = cpu_baseline(cfg, q_host[:k], flags, masks, threads)
@@ -584,18 +641,24 @@ def plan_main(args, world, rank, local, backend):
                      "note": "one validity batch per planner iteration: round-trip latency, not bandwidth, "
                              "bounds a plan"},
     }
-    # the validity round trip the planner pays per batch: one state, host buffers
-    one = np.array([scenes.PLAN_START])
-    for _ in range(20):
-        w.collide_batch(one)
-    rt = []
-    for _ in range(300):
-        t1 = time.perf_counter()
-        w.collide_batch(one)
-        rt.append(time.perf_counter() - t1)
-    result_rt = {"one_state_round_trip_us_median": float(np.median(rt) * 1e6),
-                 "one_state_round_trip_us_p90": float(np.percentile(rt, 90) * 1e6)}
-    if rank == 0 and world == 1 and args.cpu_plans != 0:
+    if args.dump_outputs and args.steps:  # the last timed plan()'s path, (waypoints, dof)
+        sfx = f"_rank{rank}" if world > 1 else ""
+        dump_outputs(args.dump_outputs, {"path" + sfx: np.asarray(paths[args.steps - 1], dtype=np.float64)},
+                     DUMP_LIMIT // world)
+    result_rt = {}
+    if args.full:
+        # the validity round trip the planner pays per batch: one state, host buffers
+        one = np.array([scenes.PLAN_START])
+        for _ in range(20):
+            w.collide_batch(one)
+        rt = []
+        for _ in range(300):
+            t1 = time.perf_counter()
+            w.collide_batch(one)
+            rt.append(time.perf_counter() - t1)
+        result_rt = {"one_state_round_trip_us_median": float(np.median(rt) * 1e6),
+                     "one_state_round_trip_us_p90": float(np.percentile(rt, 90) * 1e6)}
+    if args.full and rank == 0 and world == 1 and args.cpu_plans != 0:
         import ctypes
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle  # test infrastructure: the CPU baseline's checker

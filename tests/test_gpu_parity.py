@@ -796,6 +796,33 @@ def test_bench_one_rank_nccl_gather():
     assert r["gather_distance_ms"] > 0 and r["gather_distance_bytes_per_rank"] == 65536 * 24
 
 
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` run times K steps and
+    stops there (no CPU baseline: that is --full); --dump-outputs writes the
+    last step's flags (float32) and pair-mask words (float64), which are the
+    oracle's on the same seeded batch."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    n = 20000
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup",
+                          "1", "--per-gpu", str(n), "--dump-outputs", str(tmp_path)],
+                         env=env, capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert r["steps"] == 3 and r["value"] > 0 and r["unit"] == "configs/s" and r["dtype"] == "f64"
+    assert r["higher_is_better"] is True and "cpu_baseline" not in r
+    assert abs(r["ms_per_step"] * r["value"] - 1e3 * n) <= 1e-6 * 1e3 * n  # one step = n configurations
+    f, m = np.load(tmp_path / "flags.npy"), np.load(tmp_path / "masks.npy")
+    assert f.dtype == np.float32 and m.dtype == np.float64
+    q = scenes.sample_states(scenes.panda(), n, scenes.CFG_SEED[3])
+    fo, mo = ow(3).collide_batch(q, nthreads=NTHREADS)
+    np.testing.assert_array_equal(f, fo)
+    np.testing.assert_array_equal(m, mo)
+
+
 # --------------------------------------------------------------- point clouds
 @pytest.mark.parametrize("kind", ["floor", "blue"])
 def test_point_cloud_world_matches_oracle(kind):

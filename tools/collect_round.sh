@@ -8,8 +8,9 @@ set -e
 TAG=$1
 D=profiles/$TAG
 mkdir -p $D
-[ -f gpurun_out/bench_${TAG}_final.json ] && cp gpurun_out/bench_${TAG}_final.json $D/bench.json
-for c in 2 4 5; do [ -f gpurun_out/bench_${TAG}_cfg$c.json ] && cp gpurun_out/bench_${TAG}_cfg$c.json $D/bench_cfg$c.json; done
+BOUT=${BOUT:-bench_out}  # tools/gpu_round.sh's bench lines (bench.py --full)
+[ -f $BOUT/bench_${TAG}_final.json ] && cp $BOUT/bench_${TAG}_final.json $D/bench.json
+for c in 2 4 5; do [ -f $BOUT/bench_${TAG}_cfg$c.json ] && cp $BOUT/bench_${TAG}_cfg$c.json $D/bench_cfg$c.json; done
 if [ -d gpurun_out/prof_$TAG ]; then
   cp gpurun_out/prof_$TAG/trace/trace_kernel_stats.csv $D/kernel_stats.csv
   for p in gpurun_out/prof_$TAG/pmc_*/; do cp $p/pmc_counter_collection.csv $D/$(basename $p).csv; done

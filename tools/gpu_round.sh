@@ -10,6 +10,8 @@
 set -o pipefail
 TAG=${1:-r04}; shift
 mkdir -p gpurun_out
+BOUT=${BOUT:-bench_out}  # where the bench lines go
+mkdir -p $BOUT
 for step in "$@"; do
   case $step in
   tests)
@@ -26,17 +28,18 @@ for step in "$@"; do
     NCFG=1048576 bash tools/profile.sh ${TAG}_cfg4 --cfg 4 || exit 1
     cp gpurun_out/prof_${TAG}_cfg4/pmc_summary.json profiles/pmc_cfg4.json ;;
   bench)
-    timeout -k 10 300 python bench.py > gpurun_out/bench_${TAG}_final.json 2> gpurun_out/bench_${TAG}_final.err || { tail gpurun_out/bench_${TAG}_final.err; exit 1; }
-    head -c 400 gpurun_out/bench_${TAG}_final.json; echo
+    # --full: the lines of record carry the CPU baseline, its cross-check and the profile passes
+    timeout -k 10 300 python bench.py --full > $BOUT/bench_${TAG}_final.json 2> $BOUT/bench_${TAG}_final.err || { tail $BOUT/bench_${TAG}_final.err; exit 1; }
+    head -c 400 $BOUT/bench_${TAG}_final.json; echo
     for c in 2 4 5; do
-      timeout -k 10 300 python bench.py --cfg $c > gpurun_out/bench_${TAG}_cfg$c.json 2> gpurun_out/bench_${TAG}_cfg$c.err || { tail gpurun_out/bench_${TAG}_cfg$c.err; exit 1; }
-      head -c 300 gpurun_out/bench_${TAG}_cfg$c.json; echo
+      timeout -k 10 300 python bench.py --full --cfg $c > $BOUT/bench_${TAG}_cfg$c.json 2> $BOUT/bench_${TAG}_cfg$c.err || { tail $BOUT/bench_${TAG}_cfg$c.err; exit 1; }
+      head -c 300 $BOUT/bench_${TAG}_cfg$c.json; echo
     done ;;
   extra)  # round 6: host-buffer line, the in-process multi-GPU C route (one GPU here)
-    timeout -k 10 300 python bench.py --host > gpurun_out/bench_${TAG}_host.json 2> gpurun_out/bench_${TAG}_host.err || { tail gpurun_out/bench_${TAG}_host.err; exit 1; }
-    head -c 400 gpurun_out/bench_${TAG}_host.json; echo
-    timeout -k 10 300 python bench.py --capi-multi 1 --gather > gpurun_out/bench_${TAG}_capi1.json 2> gpurun_out/bench_${TAG}_capi1.err || { tail gpurun_out/bench_${TAG}_capi1.err; exit 1; }
-    head -c 400 gpurun_out/bench_${TAG}_capi1.json; echo ;;
+    timeout -k 10 300 python bench.py --full --host > $BOUT/bench_${TAG}_host.json 2> $BOUT/bench_${TAG}_host.err || { tail $BOUT/bench_${TAG}_host.err; exit 1; }
+    head -c 400 $BOUT/bench_${TAG}_host.json; echo
+    timeout -k 10 300 python bench.py --full --capi-multi 1 --gather > $BOUT/bench_${TAG}_capi1.json 2> $BOUT/bench_${TAG}_capi1.err || { tail $BOUT/bench_${TAG}_capi1.err; exit 1; }
+    head -c 400 $BOUT/bench_${TAG}_capi1.json; echo ;;
   *) echo "unknown step $step"; exit 2 ;;
   esac
 done
