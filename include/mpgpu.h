@@ -39,7 +39,9 @@
  * the input of one chunk crosses PCIe while earlier chunks compute and are
  * unpacked (internal threads and streams; the call is still synchronous).
  *
- * Threading: a world is immutable after creation; concurrent calls on one
+ * Threading: a world is immutable after creation, but for the current poses
+ * of its free frames (mpg_world_set_free_poses, which is not concurrent with
+ * any other call on the world); concurrent calls on one
  * world from several host threads are allowed when each uses its own stream
  * and MPG_MEM_DEVICE.  MPG_MEM_HOST calls on one world are serialised.
  * mpg_distance_batch* and mpg_check_motion_batch use scratch owned by the
@@ -57,7 +59,7 @@ extern "C" {
 #endif
 
 #define MPG_VERSION_MAJOR 0
-#define MPG_VERSION_MINOR 1
+#define MPG_VERSION_MINOR 2
 
 /* status codes */
 #define MPG_OK 0
@@ -133,8 +135,25 @@ typedef struct mpg_world_desc {
 
   /* --- user links (PinocchioModel::setLinkOrder) ---------------------------- */
   int32_t n_links;
-  const int32_t *link_parent;     /* frame.parent joint (0 = universe)      */
-  const double *link_placement;   /* [n_links*12] frame.placement           */
+  const int32_t *link_parent;     /* frame.parent joint (0 = universe), or
+                                     MPG_LINK_FREE: a free frame            */
+  const double *link_placement;   /* [n_links*12] frame.placement (of a free
+                                     frame: its initial world pose)         */
+  /* Free frames.  A user link with link_parent == MPG_LINK_FREE has no joint
+   * above it: its pose is an input (mpg_world_set_free_poses,
+   * mpg_collide_batch_free, the rows of mpg_collide_link_poses).  Free frames
+   * are the trailing entries of the link arrays (n_free, their count, is
+   * derived).  Each carries exactly one moving object with the identity
+   * moving_offset -- a movable object, whose world transform is the frame's
+   * isometry itself (the rotation matrix of the pose's quaternion, Eigen's
+   * toRotationMatrix, and the position: the same 12 doubles a static object
+   * created at that pose has in static_transform).  A pair with a movable
+   * object has a link-borne moving object (robot or attached body) as its
+   * other member: movable x static and movable x movable pairs, a second
+   * object on a free frame or another offset are MPG_E_INVALID.  Every
+   * geometry kind is allowed on a free frame, with the pair refusals above.
+   * The initial current pose is link_placement as (p, wxyz), the quaternion by
+   * the conversion mpg_fk_batch applies to every link.                     */
 
   /* --- geometry ------------------------------------------------------------- */
   int32_t n_geoms;
@@ -213,6 +232,7 @@ typedef struct mpg_world_desc {
 
 #define MPG_GJK_LIBCCD 0
 #define MPG_GJK_INDEP 1
+#define MPG_LINK_FREE (-1) /* link_parent of a free frame */
 
 typedef struct mpg_world mpg_world;
 
@@ -226,7 +246,8 @@ typedef struct mpg_world_info {
   int64_t snapshot_bytes;
 } mpg_world_info;
 
-/* Build an immutable device snapshot of the world on `device`. */
+/* Build a device snapshot of the world on `device`: immutable, except the
+ * current poses of its free frames. */
 int mpg_world_create(const mpg_world_desc *desc, int device, mpg_world **out);
 int mpg_world_destroy(mpg_world *world);
 int mpg_world_get_info(const mpg_world *world, mpg_world_info *info);
@@ -307,6 +328,60 @@ int mpg_release_stream(mpg_world *world, void *stream);
  */
 int mpg_collide_link_poses(mpg_world *world, const double *link_pose, int64_t n, uint8_t *flags,
                            uint32_t *pair_mask, int mem, void *stream);
+
+/*
+ * Movable scene objects (worlds with free frames, see mpg_world_desc).
+ *
+ * mpg_world_set_free_poses replaces the world's current free poses: pose7
+ * [n_free*7] = (px, py, pz, qw, qx, qy, qz) per free frame, host memory.
+ * Every entry point evaluates the movable objects there afterwards
+ * (mpg_collide_batch, mpg_collide_contacts, mpg_distance_batch*,
+ * mpg_check_motion_batch, mpg_collide_count, mpg_fk_batch, which echoes them
+ * in the free frames' columns, and the planner on top).  Nothing is rebuilt.
+ * NOT concurrent with other calls on the world: it waits for the work already
+ * queued on the world's device (a device synchronisation), then overwrites
+ * the poses in place; the caller keeps other threads out meanwhile.
+ *
+ * mpg_collide_batch_free is mpg_collide_batch with the free poses given per
+ * call: free_pose [free_rows * n_free * 7], free_rows == n (one pose set per
+ * configuration) or 1 (one set shared by the batch); free_pose == NULL: the
+ * current poses (then identical to mpg_collide_batch).  `mem` applies to q,
+ * free_pose and the outputs alike.  With MPG_MEM_DEVICE the call reads the
+ * caller's array from the kernels, keeps no state in the world and does not
+ * synchronise: two streams may run it on one world with different pose
+ * arrays.  The current poses are not modified.
+ *
+ * mpg_collide_link_poses and mpg_fk_batch rows are [n_links*7] with the free
+ * frames included (the trailing n_free poses): the first reads them, the
+ * second writes the current ones.  mpg_collide_link_poses on mpg_fk_batch's
+ * kinematic columns plus free poses equals mpg_collide_batch_free.
+ *
+ * Pose validity.  Host-memory poses (mpg_world_set_free_poses, MPG_MEM_HOST
+ * free_pose, the free columns of MPG_MEM_HOST link-pose rows) are checked: a non-finite value, or a quaternion with
+ * | |q| - 1 | > 1e-6, is MPG_E_INVALID.  The bound comes from the cull
+ * margin: a quaternion of norm 1 + e scales the object's rotation matrix by
+ * (1 + e)^2, moving its surface by 2 e r; the margin of a world with free
+ * frames is widened by 4e-6 times the largest geometry radius for it.
+ * Device-memory poses are the caller's contract; no kernel indexes memory by
+ * anything derived from a pose, so a bad pose can only give a wrong bit.
+ *
+ * Any finite pose gives the exact result: the cull drops a movable object
+ * whose bounding sphere lies outside the ball that holds every link-borne
+ * object (an exact fp64 test per row and object; mpg_world_get_free_info's
+ * far_radius, margins included), so an object parked far away costs nothing
+ * in the narrow phase and never widens the fp32 coordinate bound.
+ *
+ * Per-row poses for contacts, distance and motion validation, several
+ * objects on one free frame, mpg_collide_batch_multi* with per-call poses
+ * (set the poses on each world) and a movable base of an articulation are
+ * not provided.
+ */
+int mpg_world_set_free_poses(mpg_world *world, const double *pose7);
+int mpg_collide_batch_free(mpg_world *world, const double *q, const double *free_pose, int64_t free_rows,
+                           int64_t n, uint8_t *flags, uint32_t *pair_mask, int mem, void *stream);
+/* n_free, the far test's radius (0 without free frames) and the current poses
+ * [n_free*7] (host); any output pointer may be NULL. */
+int mpg_world_get_free_info(const mpg_world *world, int32_t *n_free, double *far_radius, double *pose7);
 
 /*
  * Batched motion validation: for each edge e, OMPL's
@@ -448,7 +523,8 @@ int mpg_distance_batch_ex(mpg_world *world, const double *q, int64_t n, int32_t 
 int mpg_collide_contacts(mpg_world *world, const double *input, int64_t n, int input_kind, uint8_t *flags,
                          uint32_t *pair_mask, double *depth, double *normal, double *pos, int mem, void *stream);
 
-/* link_pose: [n*n_links*7] = getLinkPose(l) -> (px, py, pz, qw, qx, qy, qz). */
+/* link_pose: [n*n_links*7] = getLinkPose(l) -> (px, py, pz, qw, qx, qy, qz);
+ * free frames: their current poses. */
 int mpg_fk_batch(mpg_world *world, const double *q, int64_t n, double *link_pose, int mem,
                  void *stream);
 

@@ -21,6 +21,7 @@ STAGES = ("cull", "bucket", "narrow")  # MPG_STAGE_* order
  JOINT_PRISMATIC_UNALIGNED, JOINT_RUBX, JOINT_RUBY, JOINT_RUBZ, JOINT_RUB_UNALIGNED) = range(12)
 GEOM_CONVEX, GEOM_BOX, GEOM_SPHERE, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_OCTREE, GEOM_MESH, GEOM_ELLIPSOID, GEOM_CONE = range(9)
 GJK_LIBCCD, GJK_INDEP = 0, 1
+LINK_FREE = -1  # MPG_LINK_FREE: link_parent of a free frame
 
 _I32P = ctypes.POINTER(ctypes.c_int32)
 _F64P = ctypes.POINTER(ctypes.c_double)
@@ -90,6 +91,12 @@ SIGNATURES = {
                                                       ctypes.c_void_p]),
     "mpg_collide_link_poses": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "mpg_world_set_free_poses": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "mpg_collide_batch_free": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                              ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                              ctypes.c_void_p]),
+    "mpg_world_get_free_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
+                                               ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]),
     "mpg_check_motion_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                               ctypes.c_uint32, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),

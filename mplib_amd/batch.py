@@ -6,7 +6,9 @@ a plain-array world description and evaluates ``collide()`` /
 Inputs may be host numpy arrays (copied through staging buffers) or device
 tensors (any object exposing ``data_ptr()``, e.g. a torch tensor on the
 world's device; the launch is enqueued on the given stream and not
-synchronised).
+synchronised).  A descriptor may hold free frames (``link_parent`` =
+``_capi.LINK_FREE``): the poses of the movable objects on them are inputs --
+``set_free_poses`` and ``collide_batch(..., free_pose=...)``.
 
 Reference semantics: ``flags[i] == PlanningWorld.collide()`` after
 ``set_qpos_all(q[i])`` (src/planning_world.h:248-250, cpp:250-262), and bit p
@@ -106,6 +108,10 @@ class DeviceWorld:
         self.n_links = info.n_links
         self.device = info.device
         self.block_size = info.block_size
+        nf, far = ctypes.c_int32(0), ctypes.c_double(0.0)
+        C.check(L.mpg_world_get_free_info(h, ctypes.byref(nf), ctypes.byref(far), None), "mpg_world_get_free_info")
+        self.n_free = nf.value          # free frames: the trailing user links (movable objects)
+        self.far_radius = far.value     # the cull's far-test radius (0 without free frames)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -131,27 +137,73 @@ class DeviceWorld:
         C.check(C.lib().mpg_release_stream(self._h, ctypes.c_void_p(int(stream))), "mpg_release_stream")
 
     # ------------------------------------------------------------------
-    def collide_batch(self, q, flags=None, pair_mask=None, stream: Optional[int] = None):
+    def collide_batch(self, q, flags=None, pair_mask=None, stream: Optional[int] = None, free_pose=None):
         """Host path (numpy): returns (flags[n] u8, pair_mask[n, W] u32).
         Device path (tensors with data_ptr()): fills the given device buffers
-        on ``stream`` and returns them without synchronising."""
+        on ``stream`` and returns them without synchronising.
+        ``free_pose``: the free frames' poses for this call, ``[n, n_free, 7]``
+        (one set per configuration) or ``[n_free, 7]`` (shared), in the same
+        memory as ``q`` (mpg_collide_batch_free); None: the current poses."""
         if hasattr(q, "data_ptr"):
             n = q.shape[0] if q.dim() > 1 else q.numel() // self.dof
             if flags is None:
                 raise ValueError("device path needs preallocated flags (and optionally pair_mask)")
+            mk = ctypes.c_void_p(pair_mask.data_ptr() if pair_mask is not None else 0)
+            if free_pose is not None:
+                rows = self._free_rows(free_pose.numel(), n)
+                C.check(C.lib().mpg_collide_batch_free(self._h, ctypes.c_void_p(q.data_ptr()),
+                                                       ctypes.c_void_p(free_pose.data_ptr()), rows, n,
+                                                       ctypes.c_void_p(flags.data_ptr()), mk, C.MPG_MEM_DEVICE,
+                                                       ctypes.c_void_p(stream or 0)), "mpg_collide_batch_free")
+                return flags, pair_mask
             C.check(C.lib().mpg_collide_batch(self._h, ctypes.c_void_p(q.data_ptr()), n,
-                                              ctypes.c_void_p(flags.data_ptr()),
-                                              ctypes.c_void_p(pair_mask.data_ptr() if pair_mask is not None else 0),
+                                              ctypes.c_void_p(flags.data_ptr()), mk,
                                               C.MPG_MEM_DEVICE, ctypes.c_void_p(stream or 0)), "mpg_collide_batch")
             return flags, pair_mask
         qa = np.ascontiguousarray(np.asarray(q, dtype=np.float64)).reshape(-1, self.dof)
         n = qa.shape[0]
         fl = np.zeros(n, np.uint8)
         pm = np.zeros((n, self.mask_words), np.uint32)
+        if free_pose is not None:
+            fp = np.ascontiguousarray(np.asarray(free_pose, dtype=np.float64))
+            rows = self._free_rows(fp.size, n)
+            C.check(C.lib().mpg_collide_batch_free(self._h, qa.ctypes.data_as(ctypes.c_void_p),
+                                                   fp.ctypes.data_as(ctypes.c_void_p), rows, n,
+                                                   fl.ctypes.data_as(ctypes.c_void_p), pm.ctypes.data_as(ctypes.c_void_p),
+                                                   C.MPG_MEM_HOST, ctypes.c_void_p(stream or 0)),
+                    "mpg_collide_batch_free")
+            return fl, pm
         C.check(C.lib().mpg_collide_batch(self._h, qa.ctypes.data_as(ctypes.c_void_p), n,
                                           fl.ctypes.data_as(ctypes.c_void_p), pm.ctypes.data_as(ctypes.c_void_p),
                                           C.MPG_MEM_HOST, ctypes.c_void_p(stream or 0)), "mpg_collide_batch")
         return fl, pm
+
+    def _free_rows(self, size: int, n: int) -> int:
+        per = self.n_free * 7
+        if per == 0:
+            raise ValueError("the world has no free frames")
+        if size == per:
+            return 1
+        if size == per * n:
+            return n
+        raise ValueError(f"free_pose must hold [{self.n_free}, 7] or [{n}, {self.n_free}, 7] values")
+
+    def set_free_poses(self, pose7):
+        """Replace the world's current free poses, ``[n_free, 7]`` (p, wxyz):
+        every entry point uses them afterwards; nothing is rebuilt.  Not
+        concurrent with other calls on this world (mpg_world_set_free_poses)."""
+        p = np.ascontiguousarray(np.asarray(pose7, dtype=np.float64))
+        if p.size != self.n_free * 7 or self.n_free == 0:
+            raise ValueError(f"pose7 must hold [{self.n_free}, 7] values (the world's free frames)")
+        C.check(C.lib().mpg_world_set_free_poses(self._h, p.ctypes.data_as(ctypes.c_void_p)),
+                "mpg_world_set_free_poses")
+
+    def free_poses(self) -> np.ndarray:
+        """The current free poses, ``[n_free, 7]``."""
+        out = np.zeros((self.n_free, 7))
+        C.check(C.lib().mpg_world_get_free_info(self._h, None, None, out.ctypes.data_as(ctypes.c_void_p)),
+                "mpg_world_get_free_info")
+        return out
 
     def debug_collide_pairs(self, geom_a: int, geom_b: int, Ta, Tb) -> np.ndarray:
         """Narrow phase only: fcl::collide(geometry geom_a at Ta[i], geom_b at

@@ -14,6 +14,7 @@
 #include <map>
 #include <memory>
 #include <optional>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <tuple>
@@ -184,8 +185,16 @@ struct CollisionObject {
   }
   void set_transform(const SE3& t) {
     tf = t;
+    has_pose7 = false;
     ++version;
   }
+  // the (p, wxyz) vector the transform was made from, kept so that a movable
+  // object's pose reaches the device as given (its matrix there is then the
+  // same 12 doubles as tf)
+  Vec7 pose7{};
+  bool has_pose7 = false;
+  void set_pose7(const Vec7& p);
+  Vec7 get_pose7() const;  // pose7, or tf's (p, wxyz) when it was set as a matrix
 };
 using ObjPtr = std::shared_ptr<CollisionObject>;
 
@@ -672,7 +681,10 @@ struct AttachedBody {
   // attached_body.h:56.  Writes the transform without bumping the object's
   // version: an attached object's own transform is not part of the device
   // snapshot (its pose comes from the link), so no rebuild follows.
-  void update_pose() const { object->tf = global_pose(); }
+  void update_pose() const {
+    object->tf = global_pose();
+    object->has_pose7 = false;  // the transform is a matrix product now, no pose vector stands for it
+  }
   void set_pose(const SE3& p) {
     pose = p;
     ++version;
@@ -718,6 +730,21 @@ class PlanningWorld {
   // PlanningWorldTpl::addPointCloud (src/planning_world.cpp:102-110)
   void add_point_cloud(const std::string& n, const std::vector<Vec3>& vertices, double resolution = 0.001);
   bool remove_normal_object(const std::string& n);
+  // Movable scene objects: their poses are inputs of the device snapshot
+  // (free frames, include/mpgpu.h), so set_pose on one needs no rebuild and
+  // collide_batch can take poses per call.  Marking is a structure change; it
+  // leaves the pair table as it is.  An attached object is an attached body
+  // whether marked or not.
+  void set_normal_object_movable(const std::string& n, bool movable = true);
+  bool is_normal_object_movable(const std::string& n) const { return movable_.count(n) > 0; }
+  // the marked objects whose pose is an input of the current snapshot, in
+  // scene order = the pose column order.  A marked object that is attached, or
+  // whose transform was last set as a matrix (attach / detach leave the
+  // link's global pose in it), is held as the unmarked world holds it -- an
+  // attached body, or static at that matrix, bit for bit -- until set_pose
+  // gives it a pose vector again.
+  std::vector<std::string> get_movable_object_names() const;
+  bool pose_is_input(const std::string& n) const;
   bool is_normal_object_attached(const std::string& n) const { return attached_.count(n) > 0; }
   AttachedPtr get_attached_object(const std::string& n) const;
   void attach_object(const std::string& n, const std::string& art, int link, const Vec7& pose,
@@ -760,6 +787,13 @@ class PlanningWorld {
   const std::vector<PairInfo>& pair_table();
   void collide_batch(const double* q, int64_t n, uint8_t* flags, uint32_t* masks);
   void collide_batch_device(const void* q, int64_t n, void* flags, void* masks, void* stream);
+  // with the movable objects' poses per call: poses [pose_rows, M, 7] in
+  // get_movable_object_names() order, pose_rows = n or 1; NULL: current poses
+  void collide_batch_free(const double* q, const double* poses, int64_t pose_rows, int64_t n, uint8_t* flags,
+                          uint32_t* masks);
+  void collide_batch_free_device(const void* q, const void* poses, int64_t pose_rows, int64_t n, void* flags,
+                                 void* masks, void* stream);
+  std::vector<double> movable_poses() const;  // current (p, wxyz) per movable object
   // distance_batch_ex on device buffers (MPG_MEM_DEVICE, enqueued on stream)
   void distance_batch_device(const void* q, int64_t n, const DistanceRequest& r, void* d_self, void* p_self,
                              void* pts_self, void* d_others, void* p_others, void* pts_others, void* stream);
@@ -796,10 +830,13 @@ class PlanningWorld {
   std::vector<double> current_state() const;
   std::vector<std::string> attached_order() const;
   std::vector<std::string> scene_order() const;
+  void push_free_poses();  // the movable objects' poses to the device world, when they changed
 
   std::map<std::string, ArtPtr> arts_, planned_;
   std::map<std::string, ObjPtr> objs_;
   std::vector<std::string> obj_insertion_;
+  std::set<std::string> movable_;
+  std::vector<double> pushed_poses_;  // what world_ holds as its current free poses
   std::map<std::string, AttachedPtr> attached_;
   std::vector<std::string> attached_insertion_;
   AcmPtr acm_;

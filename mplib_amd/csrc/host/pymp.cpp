@@ -320,7 +320,12 @@ PYBIND11_MODULE(pymp, m_all) {
 
   py::class_<CollisionObject, std::shared_ptr<CollisionObject>>(m, "CollisionObject")
       .def(py::init([](const GeomPtr& g, const std::vector<double>& p, const std::vector<double>& q) {
-             return std::make_shared<CollisionObject>(g, se3_from_pq(vec3_arg(p), quat_arg(q)));
+             auto o = std::make_shared<CollisionObject>(g, se3_from_pq(vec3_arg(p), quat_arg(q)));
+             const auto pv = vec3_arg(p);
+             const auto qv = quat_arg(q);
+             o->set_pose7({pv[0], pv[1], pv[2], qv[0], qv[1], qv[2], qv[3]});
+             o->version = 0;
+             return o;
            }),
            py::arg("collision_geometry"), py::arg("position") = std::vector<double>{0, 0, 0},
            py::arg("quaternion") = std::vector<double>{1, 0, 0, 0})
@@ -328,8 +333,16 @@ PYBIND11_MODULE(pymp, m_all) {
       .def("get_translation", [](const CollisionObject& o) { return vec(o.tf.p, 3); })
       .def("get_rotation", [](const CollisionObject& o) { return mat3(o.tf); })
       .def("set_transformation",
-           [](CollisionObject& o, const std::vector<double>& pose) { o.set_transform(se3_from_pose7(vec7_arg(pose))); },
-           py::arg("pose"));
+           [](CollisionObject& o, const std::vector<double>& pose) { o.set_pose7(vec7_arg(pose)); },
+           py::arg("pose"))
+      .def("set_pose", [](CollisionObject& o, const std::vector<double>& pose) { o.set_pose7(vec7_arg(pose)); },
+           py::arg("pose"),
+           "Set the object's world pose (px, py, pz, qw, qx, qy, qz).  On a movable scene object "
+           "(PlanningWorld.set_normal_object_movable) the next device call sees it without a snapshot rebuild.")
+      .def("get_pose", [](const CollisionObject& o) {
+        const Vec7 p = o.get_pose7();
+        return std::vector<double>(p.begin(), p.end());
+      });
 
   py::enum_<GJKSolverType>(m, "GJKSolverType")
       .value("GST_LIBCCD", GST_LIBCCD)
@@ -924,6 +937,12 @@ PYBIND11_MODULE(pymp, m_all) {
       .def("set_articulation_planned", &PW::set_articulation_planned, py::arg("name"), py::arg("planned"))
       .def("print_attached_body_pose", &PW::print_attached_body_pose)
       .def("get_normal_object_names", &PW::get_normal_object_names)
+      .def("set_normal_object_movable", &PW::set_normal_object_movable, py::arg("name"), py::arg("movable") = true,
+           "Mark a scene object movable: its pose becomes an input of the device snapshot (set_pose needs no "
+           "rebuild, collide_batch takes object_poses).  Leaves get_collision_pair_info() unchanged.")
+      .def("is_normal_object_movable", &PW::is_normal_object_movable, py::arg("name"))
+      .def("get_movable_object_names", &PW::get_movable_object_names,
+           "Movable scene objects in scene order: the pose column order of collide_batch_device's object poses.")
       .def("get_normal_object", &PW::get_normal_object, py::arg("name"))
       .def("has_normal_object", &PW::has_normal_object, py::arg("name"))
       .def("add_normal_object", &PW::add_normal_object, py::arg("name"), py::arg("collision_object"))
@@ -1052,12 +1071,48 @@ PYBIND11_MODULE(pymp, m_all) {
              return out;
            })
       .def("collide_batch",
-           [](PW& w, py::array_t<double, py::array::c_style | py::array::forcecast> states) {
+           [](PW& w, py::array_t<double, py::array::c_style | py::array::forcecast> states,
+              std::optional<py::dict> object_poses) {
              const int dim = w.state_dim();
              if (states.ndim() != 2 || states.shape(1) != dim)
                throw std::invalid_argument("states must be [N, " + std::to_string(dim) + "] float64");
              const int64_t n = states.shape(0);
              const int W = w.mask_words();
+             // object_poses: the movable objects' columns, per row ([N, 7]) or
+             // shared ((7,)); names left out keep their current pose
+             std::vector<double> poses;
+             int64_t pose_rows = 0;
+             if (object_poses) {
+               const std::vector<std::string> names = w.get_movable_object_names();
+               const size_t M = names.size();
+               using Arr = py::array_t<double, py::array::c_style | py::array::forcecast>;
+               std::vector<std::optional<Arr>> given(M);
+               pose_rows = 1;
+               for (auto item : *object_poses) {
+                 const std::string name = py::cast<std::string>(item.first);
+                 const auto it = std::find(names.begin(), names.end(), name);
+                 if (it == names.end())
+                   throw std::invalid_argument("object_poses: '" + name + "' is not a movable scene object");
+                 Arr a = Arr::ensure(item.second);
+                 if (!a) throw std::invalid_argument("object_poses['" + name + "'] must be a float64 array");
+                 const bool shared = a.ndim() == 1 && a.shape(0) == 7;
+                 const bool per_row = a.ndim() == 2 && a.shape(0) == n && a.shape(1) == 7;
+                 if (!shared && !per_row)
+                   throw std::invalid_argument("object_poses['" + name + "'] must be (7,) or (" + std::to_string(n) +
+                                               ", 7)");
+                 if (per_row) pose_rows = n;
+                 given[it - names.begin()] = a;
+               }
+               const std::vector<double> cur = w.movable_poses();
+               if (M == 0) pose_rows = 0;
+               poses.resize((size_t)pose_rows * M * 7);
+               for (int64_t r = 0; r < pose_rows; ++r)
+                 for (size_t k = 0; k < M; ++k) {
+                   const double* src = cur.data() + 7 * k;
+                   if (given[k]) src = given[k]->data() + (given[k]->ndim() == 2 ? 7 * r : 0);
+                   std::copy(src, src + 7, poses.data() + ((size_t)r * M + k) * 7);
+                 }
+             }
              py::array_t<uint8_t> flags(n);
              py::array_t<uint32_t> masks({(ssize_t)n, (ssize_t)W});
              const double* q = states.data();
@@ -1065,21 +1120,32 @@ PYBIND11_MODULE(pymp, m_all) {
              uint32_t* mk = masks.mutable_data();
              {
                py::gil_scoped_release rel;
-               w.collide_batch(q, n, f, mk);
+               if (pose_rows > 0) w.collide_batch_free(q, poses.data(), pose_rows, n, f, mk);
+               else w.collide_batch(q, n, f, mk);
              }
              return py::make_tuple(flags, masks);
            },
-           py::arg("states"),
+           py::arg("states"), py::arg("object_poses") = py::none(),
            "Batched collide(): flags[i] = collide() at states[i]; bit p of masks[i] = pair p reported by "
-           "collide_full() (see get_collision_pair_info()).")
+           "collide_full() (see get_collision_pair_info()).  object_poses: {name: (7,) or (N, 7) float64 (p, wxyz)} "
+           "for movable scene objects -- row i is checked with the objects at their row-i poses; names left out "
+           "keep their current pose; the objects' stored poses are not modified.")
       .def("collide_batch_device",
-           [](PW& w, uintptr_t q, int64_t n, uintptr_t flags, uintptr_t masks, uintptr_t stream) {
-             w.collide_batch_device(reinterpret_cast<const void*>(q), n, reinterpret_cast<void*>(flags),
-                                    reinterpret_cast<void*>(masks), reinterpret_cast<void*>(stream));
+           [](PW& w, uintptr_t q, int64_t n, uintptr_t flags, uintptr_t masks, uintptr_t stream,
+              uintptr_t object_poses, int64_t object_pose_rows) {
+             if (object_poses)
+               w.collide_batch_free_device(reinterpret_cast<const void*>(q), reinterpret_cast<const void*>(object_poses),
+                                           object_pose_rows, n, reinterpret_cast<void*>(flags),
+                                           reinterpret_cast<void*>(masks), reinterpret_cast<void*>(stream));
+             else
+               w.collide_batch_device(reinterpret_cast<const void*>(q), n, reinterpret_cast<void*>(flags),
+                                      reinterpret_cast<void*>(masks), reinterpret_cast<void*>(stream));
            },
            py::arg("states_ptr"), py::arg("n"), py::arg("flags_ptr"), py::arg("masks_ptr") = 0,
-           py::arg("stream") = 0,
-           "Enqueue the batched check on device buffers (float64 [n, dim], uint8 [n], uint32 [n, W]).")
+           py::arg("stream") = 0, py::arg("object_poses_ptr") = 0, py::arg("object_pose_rows") = 0,
+           "Enqueue the batched check on device buffers (float64 [n, dim], uint8 [n], uint32 [n, W]).  "
+           "object_poses_ptr: float64 [object_pose_rows, M, 7] device array of the movable objects' poses in "
+           "get_movable_object_names() order, object_pose_rows = n or 1 (0: their current poses).")
       .def("distance_batch_device",
            [](PW& w, uintptr_t q, int64_t n, uintptr_t d_self, uintptr_t p_self, uintptr_t d_others,
               uintptr_t p_others, uintptr_t pts_self, uintptr_t pts_others, uintptr_t stream,

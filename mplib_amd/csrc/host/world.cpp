@@ -7,7 +7,9 @@
 // table, in the same (o1, o2) argument order, and filterCollisions (:265-274)
 // becomes a per-pair "allowed" bit resolved when the device snapshot is built.
 // The snapshot is rebuilt whenever the world, the ACM, an object pose, or a
-// constant joint value changes.
+// constant joint value changes -- except the pose of a scene object marked
+// movable, which is an input of the snapshot (a free frame, include/mpgpu.h)
+// and is pushed to the device before the next call.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -215,10 +217,59 @@ void PlanningWorld::add_point_cloud(const std::string& n, const std::vector<Vec3
   SE3 I;
   for (int i = 0; i < 9; ++i) I.R[i] = (i % 4 == 0) ? 1.0 : 0.0;
   I.p[0] = I.p[1] = I.p[2] = 0.0;
-  add_normal_object(n, std::make_shared<CollisionObject>(std::make_shared<OcTree>(vertices, resolution), I));
+  auto cloud = std::make_shared<CollisionObject>(std::make_shared<OcTree>(vertices, resolution), I);
+  cloud->set_pose7({0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0});  // the identity, as a pose vector too
+  cloud->version = 0;
+  add_normal_object(n, cloud);
 }
+void CollisionObject::set_pose7(const Vec7& p) {
+  set_transform(se3_from_pose7(p));
+  pose7 = p;
+  has_pose7 = true;
+}
+Vec7 CollisionObject::get_pose7() const {
+  if (has_pose7) return pose7;
+  Vec7 p{tf.p[0], tf.p[1], tf.p[2], 1.0, 0.0, 0.0, 0.0};
+  mpg::mat_to_quat(tf.R, &p[3], &p[4]);
+  return p;
+}
+
+void PlanningWorld::set_normal_object_movable(const std::string& n, bool movable) {
+  if (!objs_.count(n)) throw std::invalid_argument("no normal object named " + n);
+  if (movable) movable_.insert(n);
+  else movable_.erase(n);
+  ++structure_version_;
+}
+bool PlanningWorld::pose_is_input(const std::string& n) const {
+  return movable_.count(n) && !attached_.count(n) && objs_.at(n)->has_pose7;
+}
+std::vector<std::string> PlanningWorld::get_movable_object_names() const {
+  std::vector<std::string> out;
+  for (auto& n : scene_order())
+    if (pose_is_input(n)) out.push_back(n);
+  return out;
+}
+std::vector<double> PlanningWorld::movable_poses() const {
+  std::vector<double> out;
+  for (auto& n : get_movable_object_names()) {
+    const Vec7 p = objs_.at(n)->get_pose7();
+    out.insert(out.end(), p.begin(), p.end());
+  }
+  return out;
+}
+// set_pose on a movable object does not change the snapshot key: before a
+// device call the poses that changed since the last push go to the world
+void PlanningWorld::push_free_poses() {
+  if (!world_) return;
+  const std::vector<double> cur = movable_poses();
+  if (cur.empty() || cur == pushed_poses_) return;
+  check_status(mpg_world_set_free_poses(world_->get(), cur.data()), "mpg_world_set_free_poses");
+  pushed_poses_ = cur;
+}
+
 bool PlanningWorld::remove_normal_object(const std::string& n) {
   if (!objs_.erase(n)) return false;
+  movable_.erase(n);
   obj_insertion_.erase(std::remove(obj_insertion_.begin(), obj_insertion_.end(), n), obj_insertion_.end());
   if (attached_.erase(n))
     attached_insertion_.erase(std::remove(attached_insertion_.begin(), attached_insertion_.end(), n),
@@ -340,6 +391,7 @@ bool PlanningWorld::detach_object(const std::string& n, bool also_remove) {
   if (also_remove) {
     if (objs_.erase(n))
       obj_insertion_.erase(std::remove(obj_insertion_.begin(), obj_insertion_.end(), n), obj_insertion_.end());
+    movable_.erase(n);
     acm_->remove_entry(n);
     acm_->remove_default_entry(n);
   }
@@ -409,7 +461,10 @@ uint64_t PlanningWorld::snapshot_key(const CollisionRequest& r) const {
     for (size_t i = 0; i < q.size(); ++i)
       if (std::find(slots.begin(), slots.end(), (int)i) == slots.end()) mixd(q[i]);
   }
-  for (auto& n : obj_insertion_) mix(objs_.at(n)->version);
+  // a movable scene object's pose is an input of the snapshot, not part of it
+  for (auto& n : obj_insertion_) {
+    mix(pose_is_input(n) ? ~0ull : objs_.at(n)->version);
+  }
   for (auto& n : attached_insertion_) {
     mix((uint64_t)(uintptr_t)attached_.at(n).get());
     mix(attached_.at(n)->version);
@@ -422,10 +477,13 @@ void PlanningWorld::ensure_snapshot(const CollisionRequest& r, bool need_device)
   const uint64_t key = snapshot_key(r);
   if (key == desc_key_) {
     if (need_device && !world_) {
+      // the descriptor's free frames hold the poses of its build
       world_ = std::make_unique<DeviceWorld>(*desc_, default_device());
       world_key_ = key;
+      pushed_poses_.clear();
       apply_device_options();
     }
+    if (need_device) push_free_poses();
     return;
   }
   world_.reset();
@@ -512,11 +570,26 @@ void PlanningWorld::ensure_snapshot(const CollisionRequest& r, bool need_device)
     d.moving_geom.push_back(d.add_geometry(b->object->geom.get()));
     push_se3(d.moving_offset, b->pose);
   }
-  const int n_moving = (int)d.moving_link.size();
-  // scene objects (static)
+  // movable scene objects: one free frame each (the trailing links), the
+  // object on it with the identity offset; the pair loops below address them
+  // by scene name, so marking an object movable moves no pair
   std::vector<std::string> scene = scene_order();
   std::map<std::string, int> scene_id;
   for (auto& n : scene) {
+    if (!pose_is_input(n)) continue;
+    scene_id[n] = (int)d.moving_link.size();
+    d.moving_link.push_back((int)d.link_parent.size());
+    d.link_parent.push_back(MPG_LINK_FREE);
+    push_se3(d.link_placement, objs_.at(n)->tf);
+    d.moving_geom.push_back(d.add_geometry(objs_.at(n)->geom.get()));
+    SE3 I;
+    mpg::se3_identity(I);
+    push_se3(d.moving_offset, I);
+  }
+  const int n_moving = (int)d.moving_link.size();
+  // scene objects (static)
+  for (auto& n : scene) {
+    if (pose_is_input(n)) continue;
     scene_id[n] = n_moving + (int)d.static_geom.size();
     d.static_geom.push_back(d.add_geometry(objs_.at(n)->geom.get()));
     push_se3(d.static_transform, objs_.at(n)->tf);
@@ -589,7 +662,9 @@ void PlanningWorld::ensure_snapshot(const CollisionRequest& r, bool need_device)
   if (need_device) {
     world_ = std::make_unique<DeviceWorld>(d, default_device());
     world_key_ = key;
+    pushed_poses_.clear();
     apply_device_options();
+    push_free_poses();
   }
 }
 
@@ -671,6 +746,20 @@ mpg_world* PlanningWorld::device_world() {
 void PlanningWorld::collide_batch(const double* q, int64_t n, uint8_t* flags, uint32_t* masks) {
   ensure_snapshot(CollisionRequest());
   check_status(mpg_collide_batch(world_->get(), q, n, flags, masks, MPG_MEM_HOST, nullptr), "mpg_collide_batch");
+}
+void PlanningWorld::collide_batch_free(const double* q, const double* poses, int64_t pose_rows, int64_t n,
+                                       uint8_t* flags, uint32_t* masks) {
+  ensure_snapshot(CollisionRequest());
+  check_status(mpg_collide_batch_free(world_->get(), q, poses, pose_rows, n, flags, masks, MPG_MEM_HOST, nullptr),
+               "mpg_collide_batch_free");
+}
+void PlanningWorld::collide_batch_free_device(const void* q, const void* poses, int64_t pose_rows, int64_t n,
+                                              void* flags, void* masks, void* stream) {
+  ensure_snapshot(CollisionRequest());
+  check_status(mpg_collide_batch_free(world_->get(), static_cast<const double*>(q), static_cast<const double*>(poses),
+                                      pose_rows, n, static_cast<uint8_t*>(flags), static_cast<uint32_t*>(masks),
+                                      MPG_MEM_DEVICE, stream),
+               "mpg_collide_batch_free");
 }
 void PlanningWorld::collide_batch_device(const void* q, int64_t n, void* flags, void* masks, void* stream) {
   ensure_snapshot(CollisionRequest());
@@ -860,6 +949,8 @@ std::vector<int64_t> PlanningWorld::sample_pair_counts(int64_t n, uint64_t seed)
     full_world_ = std::make_unique<DeviceWorld>(f, default_device());
     full_key_ = desc_key_;
   }
+  if (const std::vector<double> cur = movable_poses(); !cur.empty())
+    check_status(mpg_world_set_free_poses(full_world_->get(), cur.data()), "mpg_world_set_free_poses");
   std::vector<int64_t> counts(pairs_.size(), 0);
   check_status(mpg_collide_count(full_world_->get(), full_lo_.data(), full_hi_.data(), n, seed, counts.data(), nullptr),
                "mpg_collide_count");

@@ -29,6 +29,15 @@ constexpr float kBpMargin = 1e-4f;  // metres
 // with 3x headroom); world creation keeps the margin above this times the
 // coordinate bound, so far-from-origin worlds keep the soundness argument
 constexpr double kFp32CullRel = 4e-6;
+// where the cull parks the centre of a movable object that its far test
+// dropped: its square (1e30) is finite in fp32 and above every (r + r +
+// margin)^2, so each bounding-sphere test of the object fails
+constexpr float kFarPark = 1e15f;
+// host-memory free poses: the largest | |quaternion| - 1 | accepted.  The
+// rotation matrix of a quaternion of norm 1 + e is scaled by (1 + e)^2, which
+// moves a surface point of a shape of radius r by 2 e r; the cull margin of a
+// world with free frames carries 4 * kFreeQuatTol * (largest radius) for it
+constexpr double kFreeQuatTol = 1e-6;
 // travel bound of a prismatic move-group joint without finite limits (metres)
 constexpr double kDefaultTravel = 10.0;
 

@@ -146,6 +146,16 @@ struct DevWorld {
   // bounding test read (LR_*; lat_rec_ok = every chain fits kLatChain)
   cptr<double> lat_rec;  // [n_pairs][LR_STRIDE]
   int lat_rec_ok;
+  // free frames (include/mpgpu.h): the trailing n_free user links, whose poses
+  // are inputs.  free_obj[k] = the movable object on free frame k; free_cur =
+  // the world's current poses [n_free*7] (p, wxyz), the only part of a world
+  // that mpg_world_set_free_poses rewrites; far_r = radius of the ball around
+  // the origin beyond which a movable object's bounding sphere cannot meet a
+  // link-borne object (margins included)
+  int n_free;
+  cptr<int> free_obj;
+  const double* free_cur;
+  double far_r;
 };
 constexpr int kLatChain = 12;
 // latency pair record: header, then per side (0 = pair_a, 1 = pair_b) the

@@ -1149,9 +1149,35 @@ __global__ __launch_bounds__(BLOCK) void cull_kernel(DevWorld w, const double* _
   bool forced = false;
   if (FROM_POSES) {
     for (int m = 0; m < w.n_moving; ++m) put(m, bp_from_pose7(w.bp, in + (c * w.n_links + w.moving_link[m]) * 7, m));
-    for (int l = 0; l < w.n_links; ++l) {
+    const int nk = w.n_links - w.n_free;
+    for (int l = 0; l < nk; ++l) {
       const double* pl = in + (c * w.n_links + l) * 7;
       forced |= !(std::fabs(pl[0]) <= w.pose_bound && std::fabs(pl[1]) <= w.pose_bound && std::fabs(pl[2]) <= w.pose_bound);
+    }
+    // far test of the movable objects, exact in fp64: one whose bounding
+    // sphere lies outside the ball that holds every link-borne object (far_r:
+    // margin and slack included) meets none of them in this row -- its centre
+    // is parked where every fp32 sphere test fails; the others have their
+    // coordinates inside the bound the cull margin was sized for
+    for (int k = 0; k < w.n_free; ++k) {
+      const double* pl = in + (c * w.n_links + nk + k) * 7;
+      const int m = w.free_obj[k];
+      const cptr<double> gr = w.geom_rec + G_STRIDE * w.moving_geom[m];
+      double R[9];
+      quat_to_mat(pl[3], pl[4], pl[5], pl[6], R);
+      double d2 = 0.0;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const double ci = R[3 * i] * gr[G_OBB_C] + R[3 * i + 1] * gr[G_OBB_C + 1] + R[3 * i + 2] * gr[G_OBB_C + 2] + pl[i];
+        d2 += ci * ci;
+      }
+      // NaN compares false: such an object stays in, and the fp32 tests drop it
+      if (std::sqrt(d2) - gr[G_RADIUS] > w.far_r) {
+        float* r = cen + (size_t)m * 3 * BLOCK + tid;
+        r[0] = kFarPark;
+        r[BLOCK] = 0.f;
+        r[2 * BLOCK] = 0.f;
+      }
     }
   } else {
     bp_fk(w.bp, in + c * w.dof, save + tid, BLOCK, put_j);
@@ -6427,6 +6453,25 @@ __global__ void fk_kernel(DevWorld w, const double* __restrict__ q, long long n,
   for (int l = 0; l < w.n_links; ++l) link_transform(w, st, l, out + (cfg * w.n_links + l) * 7);
 }
 
+// Worlds with free frames: the link-pose rows their pairs are evaluated from.
+// The kinematic links by FK as fk_kernel writes them, the free frames copied
+// from free_pose (row cfg * free_stride doubles in; stride 0: one pose set
+// shared by the batch) or, when free_pose is NULL, from the world's current
+// poses.  A movable object's transform is then the frame's isometry whatever
+// the source of the pose.
+__global__ void fk_free_kernel(DevWorld w, const double* __restrict__ q, long long n, double* __restrict__ out,
+                               const double* __restrict__ free_pose, long long free_stride) {
+  const long long cfg = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (cfg >= n) return;
+  FkState st;
+  forward_kinematics(w, q + cfg * w.dof, st);
+  const int nk = w.n_links - w.n_free;
+  for (int l = 0; l < nk; ++l) link_transform(w, st, l, out + (cfg * w.n_links + l) * 7);
+  const double* src = free_pose ? free_pose + cfg * free_stride : w.free_cur;
+  double* dst = out + (cfg * w.n_links + nk) * 7;
+  for (int k = 0; k < w.n_free * 7; ++k) dst[k] = src[k];
+}
+
 // ---------------------------------------------------------------------------
 // Batched motion validation (OMPL DiscreteMotionValidator over the MPlib
 // compound state space, src/ompl_planner.cpp:248-293): per edge the segment
@@ -6679,11 +6724,23 @@ struct mpg_world {
     uint32_t* cand = nullptr;       // [n_pairs * cap] worst case
     float* rq = nullptr;            // [n_moving * 4 * cap] phase-A rotations (quaternions) for the SAT stage
     double* sc = nullptr;           // [cap * dof * 2] exact joint (sin, cos) for phase B
+    double* links = nullptr;        // [links_cap * n_links * 7] link-pose rows (worlds with free frames)
+    long long links_cap = 0;
     long long cap = 0;
     uint64_t last = 0;              // LRU tick (get_workspace)
   };
   std::mutex ws_mu;
   std::map<hipStream_t, Workspace> ws;
+  // free frames: the current poses (host copy, device buffer DevWorld::free_cur
+  // points to) and the grow-only staging of host-buffer calls (host_mu)
+  std::vector<double> free_host;
+  double* free_dev = nullptr;
+  struct FreeStage {
+    double *q = nullptr, *fp = nullptr, *links = nullptr;
+    uint8_t* fl = nullptr;
+    uint32_t* mk = nullptr;
+    size_t q_cap = 0, fp_cap = 0, links_cap = 0, fl_cap = 0, mk_cap = 0;
+  } free_stage;
   // optional per-stage timing (mpg_profile_enable)
   struct Mark {
     int stage;
@@ -6727,6 +6784,8 @@ struct mpg_world {
     size_t out_cap = 0;
     double* pts = nullptr;  // device-buffer calls: points nobody asked for
     size_t pts_cap = 0;
+    double* links = nullptr;  // worlds with free frames: link-pose rows
+    size_t links_cap = 0;
     hipEvent_t last = nullptr;  // the previous call's work (scratch order across streams)
     ccdx::BigPolytope* big = nullptr;  // kBigPool EPA polytopes (distance_redo_kernel)
     size_t big_cap = 0;
@@ -6906,6 +6965,11 @@ int obj_geom_type(const mpg_world_desc* d, int id) {
   return d->geom_type[id < d->n_moving ? d->moving_geom[id] : d->static_geom[id - d->n_moving]];
 }
 
+// a movable object: a moving object whose link is a free frame
+bool desc_obj_movable(const mpg_world_desc* d, int id) {
+  return id < d->n_moving && d->link_parent[d->moving_link[id]] == MPG_LINK_FREE;
+}
+
 // FCL closed-form pair for (o1, o2) in fcl::collide argument order
 int closed_form_kind(const mpg_world_desc* d, int a, int b) {
   const int ta = obj_geom_type(d, a), tb = obj_geom_type(d, b);
@@ -6937,8 +7001,12 @@ int validate(const mpg_world_desc* d) {
       return set_error(MPG_E_INVALID, "joint_parent must reference an earlier joint (0 = universe)");
     if (d->joint_q_source[j] >= d->dof) return set_error(MPG_E_INVALID, "joint_q_source >= dof");
   }
-  for (int l = 0; l < d->n_links; ++l)
-    if (d->link_parent[l] < 0 || d->link_parent[l] > d->n_joints) return set_error(MPG_E_INVALID, "bad link_parent");
+  for (int l = 0; l < d->n_links; ++l) {
+    if (d->link_parent[l] < MPG_LINK_FREE || d->link_parent[l] > d->n_joints)
+      return set_error(MPG_E_INVALID, "bad link_parent");
+    if (l > 0 && d->link_parent[l] != MPG_LINK_FREE && d->link_parent[l - 1] == MPG_LINK_FREE)
+      return set_error(MPG_E_INVALID, "free frames (link_parent MPG_LINK_FREE) must be the trailing links");
+  }
   for (int g = 0; g < d->n_geoms; ++g) {
     const int t = d->geom_type[g];
     if (t < MPG_GEOM_CONVEX || t > MPG_GEOM_TRIANGLE) return set_error(MPG_E_UNSUPPORTED, "unsupported geometry type");
@@ -6990,6 +7058,21 @@ int validate(const mpg_world_desc* d) {
     if (d->moving_link[m] < 0 || d->moving_link[m] >= d->n_links) return set_error(MPG_E_INVALID, "bad moving_link");
     if (d->moving_geom[m] < 0 || d->moving_geom[m] >= d->n_geoms) return set_error(MPG_E_INVALID, "bad moving_geom");
   }
+  // one object per free frame, at the frame itself: its world transform is
+  // the frame's isometry, bit for bit (compound movable bodies: out of scope)
+  for (int l = 0; l < d->n_links; ++l) {
+    if (d->link_parent[l] != MPG_LINK_FREE) continue;
+    int count = 0;
+    for (int m = 0; m < d->n_moving; ++m) {
+      if (d->moving_link[m] != l) continue;
+      ++count;
+      static const double ident[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+      for (int k = 0; k < 12; ++k)
+        if (!(d->moving_offset[12 * (size_t)m + k] == ident[k]))
+          return set_error(MPG_E_INVALID, "the object of a free frame needs the identity moving_offset");
+    }
+    if (count != 1) return set_error(MPG_E_INVALID, "a free frame carries exactly one object");
+  }
   if (d->n_mesh_triangles < 0 || (d->n_mesh_triangles > 0 && !d->mesh_triangle))
     return set_error(MPG_E_INVALID, "bad mesh triangle array");
   if (d->n_octree_leaves < 0 || (d->n_octree_leaves > 0 && !d->octree_leaf))
@@ -7009,6 +7092,11 @@ int validate(const mpg_world_desc* d) {
     const int a = d->pair_a[p], b = d->pair_b[p];
     if (a < 0 || a >= nobj || b < 0 || b >= nobj) return set_error(MPG_E_INVALID, "pair object id out of range");
     if (a >= d->n_moving && b >= d->n_moving) return set_error(MPG_E_INVALID, "static-static pair");
+    // a movable object (on a free frame) only meets link-borne objects: the
+    // cull's far test drops it against the ball that holds those
+    const bool fa = desc_obj_movable(d, a), fb = desc_obj_movable(d, b);
+    if ((fa && (fb || b >= d->n_moving)) || (fb && a >= d->n_moving))
+      return set_error(MPG_E_INVALID, "a movable object pairs with link-borne objects only (not static, not movable)");
     // an OcTree may ride on a link or an attached body (attachObject takes any
     // FCL geometry, planning_world.cpp:174-191), and meet another OcTree
     // (octree_octree_wave; its contacts and distance are refused per call)
@@ -7403,6 +7491,7 @@ void free_workspace(mpg_world::Workspace& ws) {
     if (p) hipFree(p);
   if (ws.rq) hipFree(ws.rq);
   if (ws.sc) hipFree(ws.sc);
+  if (ws.links) hipFree(ws.links);
   ws = mpg_world::Workspace{};
 }
 
@@ -7772,7 +7861,7 @@ int mpg_last_error_copy(char* buf, size_t size) {
   return (int)std::min<size_t>(len, 0x7fffffff);
 }
 
-const char* mpg_version(void) { return "mpgpu 0.1 (gfx950, fp64, libccd-MPR)"; }
+const char* mpg_version(void) { return "mpgpu 0.2 (gfx950, fp64, libccd-MPR)"; }
 
 int mpg_device_count(int* count) {
   if (!count) return set_error(MPG_E_INVALID, "count is NULL");
@@ -7841,11 +7930,24 @@ int mpg_synchronize(int device) {
   return MPG_OK;
 }
 
-int mpg_world_create(const mpg_world_desc* d, int device, mpg_world** out) {
+int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
   if (!out) return set_error(MPG_E_INVALID, "out is NULL");
   *out = nullptr;
-  int rc = validate(d);
+  int rc = validate(d_in);
   if (rc) return rc;
+  // free frames: the kinematic build below (chains, broad-phase program,
+  // latency records) sees them as links fixed to the universe at their initial
+  // pose; what the kernels read for them is the pose input
+  mpg_world_desc dd = *d_in;
+  std::vector<int32_t> lp_kin(dd.link_parent, dd.link_parent + dd.n_links);
+  int n_free = 0;
+  for (int32_t& p : lp_kin)
+    if (p == MPG_LINK_FREE) {
+      p = 0;
+      ++n_free;
+    }
+  if (n_free) dd.link_parent = lp_kin.data();
+  const mpg_world_desc* d = &dd;
   std::vector<double> geom_rec((size_t)G_STRIDE * std::max(d->n_geoms, 1), 0.0);
   for (int g = 0; g < d->n_geoms; ++g) geom_record(d, g, geom_rec.data() + (size_t)G_STRIDE * g);
   std::vector<double> obb((size_t)7 * std::max(d->n_geoms, 1), 0.0);
@@ -8189,15 +8291,40 @@ int mpg_world_create(const mpg_world_desc* d, int device, mpg_world** out) {
   // origin)
   double reach_x = 0.0, geo_r = 0.0, stat_x = 0.0;
   for (int j = 0; j < d->n_joints; ++j) reach_x += std::sqrt(sq3(d->joint_placement + 12 * j + 9)) + travel[j];
-  for (int l = 0; l < d->n_links; ++l) reach_x += std::sqrt(sq3(d->link_placement + 12 * l + 9));
+  // (the kinematic links: where a free frame starts says nothing about the chain)
+  for (int l = 0; l < d->n_links - n_free; ++l) reach_x += std::sqrt(sq3(d->link_placement + 12 * l + 9));
   double off = 0.0;
   for (int m = 0; m < d->n_moving; ++m) off = std::max(off, std::sqrt(sq3(d->moving_offset + 12 * m + 9)));
   for (int g = 0; g < d->n_geoms; ++g) geo_r = std::max(geo_r, geom_rec[G_STRIDE * g + G_RADIUS] +
                                                                    std::sqrt(sq3(&geom_rec[G_STRIDE * g + G_OBB_C])));
   for (int s2 = 0; s2 < d->n_static; ++s2) stat_x = std::max(stat_x, std::sqrt(sq3(d->static_transform + 12 * s2 + 9)));
-  const double X = std::max(reach_x + off, stat_x) + geo_r;
+  double X = std::max(reach_x + off, stat_x) + geo_r;
   bp_margin = std::max(bp_margin, (float)(kFp32CullRel * X));
-  const double small_margin = may_mpr ? std::max(kSmallMargin, reach) : kSmallMargin;
+  double small_margin = may_mpr ? std::max(kSmallMargin, reach) : kSmallMargin;
+  // Movable objects (on free frames).  Every link-borne object lies in the
+  // ball of radius link_r around the origin: each coordinate of a link origin
+  // is within reach_x (FK keeps the norm there; the link-pose input forces
+  // every pair of a row beyond it), then the offset and the geometry.  A
+  // movable object whose bounding sphere is outside far_r = link_r + margin +
+  // slack (as never_near) is dropped by the cull's exact fp64 far test; one
+  // that is not has every coordinate within far_r + 2 geo_r, which X (and so
+  // the margin, which in turn moves far_r: a few rounds settle it) covers.
+  // The margins also carry the scaling a free pose's quaternion may have
+  // (kFreeQuatTol, mpgpu.h).
+  double far_r = 0.0;
+  if (n_free) {
+    const double link_r = std::sqrt(3.0) * reach_x + off + geo_r;
+    const float quat_slack = (float)(4.0 * kFreeQuatTol * geo_r);
+    bp_margin += quat_slack;
+    small_margin += 4.0 * kFreeQuatTol * geo_r;
+    for (int it = 0; it < 8; ++it) {
+      far_r = (link_r + (double)bp_margin + 1e-6 * (1.0 + X)) * (1.0 + 1e-9);
+      X = std::max(X, far_r + 2.0 * geo_r);
+      bp_margin = std::max(bp_margin, (float)(kFp32CullRel * X) + quat_slack);
+    }
+    far_r = (link_r + (double)bp_margin + 1e-6 * (1.0 + X)) * (1.0 + 1e-9);
+    X = std::max(X, far_r + 2.0 * geo_r);
+  }
   // link poses given directly (mpg_collide_link_poses): a pose beyond the
   // chain's reach falls outside the coordinate bound -> every pair
   const double pose_bound = reach_x;
@@ -8379,6 +8506,12 @@ int mpg_world_create(const mpg_world_desc* d, int device, mpg_world** out) {
   const size_t o_oli = bb.add(oct_list.data(), oct_list.size());
   const size_t o_opa = bb.add(oct_path.data(), oct_path.size());
   const size_t o_ode = bb.add(oct_depth.data(), oct_depth.size());
+  // free frame k (link n_links - n_free + k) -> its object; worlds without
+  // free frames add nothing to the snapshot (their hash stays what it was)
+  std::vector<int> free_obj(n_free, 0);
+  for (int m = 0; m < d->n_moving; ++m)
+    if (d->moving_link[m] >= d->n_links - n_free) free_obj[d->moving_link[m] - (d->n_links - n_free)] = m;
+  const size_t o_fob = n_free ? bb.add(free_obj.data(), free_obj.size()) : 0;
 
   mpg_world* w = new mpg_world();
   w->device = device;
@@ -8420,6 +8553,22 @@ int mpg_world_create(const mpg_world_desc* d, int device, mpg_world** out) {
   dw.prism_bound = to_cptr<double>(base + o_pbd);
   dw.pose_bound = pose_bound;
   dw.all_mask = to_cptr<int>(base + o_amk);
+  dw.n_free = n_free;
+  dw.far_r = far_r;
+  dw.free_obj = to_cptr<int>(base + o_fob);
+  dw.free_cur = nullptr;
+  if (n_free) {  // the current poses start at the frames' link_placement, as (p, wxyz)
+    w->free_host.resize((size_t)n_free * 7);
+    for (int k = 0; k < n_free; ++k) {
+      const double* lp = d->link_placement + 12 * (size_t)(d->n_links - n_free + k);
+      double* p7 = w->free_host.data() + 7 * (size_t)k;
+      for (int i = 0; i < 3; ++i) p7[i] = lp[9 + i];
+      mat_to_quat(lp, &p7[3], &p7[4]);
+    }
+    HIP_TRY(hipMalloc(&w->free_dev, sizeof(double) * w->free_host.size()));
+    HIP_TRY(hipMemcpy(w->free_dev, w->free_host.data(), sizeof(double) * w->free_host.size(), hipMemcpyHostToDevice));
+    dw.free_cur = w->free_dev;
+  }
 #ifdef MPG_DIAG  // ablation builds only (changes results)
   if (const char* m = std::getenv("MPG_DEBUG_MARGIN")) {
     dw.bp_margin = (float)std::atof(m);
@@ -8585,7 +8734,8 @@ int mpg_world_create(const mpg_world_desc* d, int device, mpg_world** out) {
   if (const char* e = std::getenv("MPG_SMALL_SERVER_MAX")) w->srv_max_n = std::min(kSrvN, std::max(1, std::atoi(e)));
   w->srv_lds = srv_lds_bytes(d->n_moving, d->n_pairs, d->dof, w->dw.W, d->n_joints, d->n_static);
   w->srv_ok = lat_rec_ok && !w->any_octree && !w->any_mesh && !w->any_gjk && d->dof > 0 && d->dof <= kLatScDof &&
-              d->n_pairs > 0 && w->dw.W <= kSrvMaxW && w->srv_lds <= 144 * 1024;  // + ~11 KB static LDS
+              d->n_pairs > 0 && w->dw.W <= kSrvMaxW && w->srv_lds <= 144 * 1024 &&  // + ~11 KB static LDS
+              n_free == 0;  // the resident server holds a by-value world: it would not see a pose update
   const char* own = std::getenv("MPG_OWN_STREAM");
   if (!own || std::atoi(own) != 0) HIP_TRY(hipStreamCreateWithFlags(&w->own_stream, hipStreamNonBlocking));
   *out = w;
@@ -8682,6 +8832,7 @@ int mpg_world_destroy(mpg_world* w) {
   hipFree(w->dist.q);
   hipFree(w->dist.out);
   hipFree(w->dist.pts);
+  hipFree(w->dist.links);
   if (w->dist.last) hipEventDestroy(w->dist.last);
   hipFree(w->dist.big);
   hipFree(w->dist.list);
@@ -8705,7 +8856,14 @@ int mpg_world_destroy(mpg_world* w) {
       hipFree(p);
     hipFree(kv.second.rq);
     hipFree(kv.second.sc);
+    hipFree(kv.second.links);
   }
+  hipFree(w->free_dev);
+  hipFree(w->free_stage.q);
+  hipFree(w->free_stage.fp);
+  hipFree(w->free_stage.links);
+  hipFree(w->free_stage.fl);
+  hipFree(w->free_stage.mk);
   delete w;
   return MPG_OK;
 }
@@ -8871,8 +9029,11 @@ int collide_served(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uin
 // one round trip: input to the device, one small_kernel launch writing hit
 // bytes straight into host memory, one synchronisation; the host folds the
 // hits into flags / pair masks
+// dev_in: the rows are already on the device (link poses assembled there for
+// a world with free frames); q is then not read
 template <bool FROM_POSES>
-int collide_small(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint32_t* pair_mask, hipStream_t s) {
+int collide_small(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint32_t* pair_mask, hipStream_t s,
+                  const double* dev_in = nullptr) {
   if (!FROM_POSES && w->srv_mode && w->srv_ok && n <= w->srv_max_n && !w->dw.dbg(3) && !w->dw.dbg(7) &&
       (!w->srv_broken || std::chrono::steady_clock::now() >= w->srv_retry_at)) {
     if (collide_served(w, q, n, flags, pair_mask) == MPG_OK) {
@@ -8896,8 +9057,8 @@ int collide_small(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint
   std::memset(flags, 0, (size_t)n);
   if (pair_mask) std::memset(pair_mask, 0, sizeof(uint32_t) * (size_t)n * W);
   if (P == 0) return MPG_OK;
-  const double* qin = w->small_zero_copy ? w->d_qmap : w->d_qs;
-  if (row) {  // zero-copy: the kernel reads the pinned rows directly, no copy launch
+  const double* qin = dev_in ? dev_in : w->small_zero_copy ? w->d_qmap : w->d_qs;
+  if (row && !dev_in) {  // zero-copy: the kernel reads the pinned rows directly, no copy launch
     std::memcpy(w->h_q, q, sizeof(double) * (size_t)n * row);
     if (!w->small_zero_copy)
       HIP_TRY(hipMemcpyAsync(w->d_qs, w->h_q, sizeof(double) * (size_t)n * row, hipMemcpyHostToDevice, s));
@@ -9147,14 +9308,27 @@ int collide_host_pipelined(mpg_world* w, const double* q, int64_t n, uint8_t* fl
   return rc;
 }
 
+int collide_free(mpg_world* w, const double* q, const double* free_pose, int64_t free_rows, int64_t n, uint8_t* flags,
+                 uint32_t* pair_mask, int mem, void* stream);
+int check_free_poses(const double* p7, size_t count);
+
 template <bool FROM_POSES>
 int collide_common(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint32_t* pair_mask, int mem,
                    void* stream) {
   if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  // joint-value rows of a world with free frames: at its current poses
+  if (!FROM_POSES && w->dw.n_free) return collide_free(w, q, nullptr, 0, n, flags, pair_mask, mem, stream);
   if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
   const size_t row = FROM_POSES ? (size_t)w->dw.n_links * 7 : (size_t)w->dw.dof;
   // a world without inputs (dof 0) may pass q = NULL
   if (n > 0 && ((!q && row > 0) || !flags)) return set_error(MPG_E_INVALID, "input/flags is NULL");
+  // host-memory link-pose rows: the free frames' columns are checked as every host-memory free pose is
+  if (FROM_POSES && mem == MPG_MEM_HOST && w->dw.n_free)
+    for (int64_t i = 0; i < n; ++i) {
+      const int rc = check_free_poses(q + ((size_t)i * w->dw.n_links + (w->dw.n_links - w->dw.n_free)) * 7,
+                                      (size_t)w->dw.n_free);
+      if (rc) return rc;
+    }
   HIP_TRY(hipSetDevice(w->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (mem == MPG_MEM_DEVICE) return launch_collide_overlapped<FROM_POSES>(w, q, n, flags, pair_mask, s);
@@ -9164,6 +9338,145 @@ int collide_common(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uin
   if (n == 0) return MPG_OK;
   if (n <= w->small_max) return collide_small<FROM_POSES>(w, q, n, flags, pair_mask, s);
   return collide_host_pipelined<FROM_POSES>(w, q, n, flags, pair_mask, s);
+}
+
+// ---------------------------------------------------------------------------
+// Worlds with free frames.  Every pair evaluation of such a world runs on
+// link-pose rows: fk_free_kernel writes the kinematic links' poses from q and
+// copies the free frames' poses next to them (per row, shared, or the world's
+// current ones), then the link-pose instances of the cull / narrow / small
+// kernels evaluate the rows.  Device calls keep the rows in the caller
+// stream's workspace and read the caller's pose array directly: no state in
+// the world, no synchronisation.  Worlds without free frames never come here.
+// ---------------------------------------------------------------------------
+constexpr long long kFreeChunk = 1 << 18;  // rows per pass: n_links * 56 B each
+
+// device buffers; free_pose NULL = current poses; free_stride in doubles
+int launch_collide_free(mpg_world* w, const double* q, const double* free_pose, long long free_stride, long long n,
+                        uint8_t* flags, uint32_t* masks, hipStream_t s, const ContactOut* co = nullptr) {
+  if (n == 0) return MPG_OK;
+  StreamPin pin(w, s);
+  const long long chunk = std::min<long long>(n, std::min<long long>(kFreeChunk, w->max_chunk));
+  mpg_world::Workspace* ws = nullptr;
+  int rc = get_workspace(w, s, chunk, &ws);
+  if (rc) return rc;
+  const size_t lrow = (size_t)w->dw.n_links * 7;
+  if (ws->links_cap < chunk) {  // this stream's queued work may still read the old rows
+    if (ws->links) {
+      HIP_TRY(hipStreamSynchronize(s));
+      HIP_TRY(hipFree(ws->links));
+    }
+    ws->links = nullptr;
+    ws->links_cap = 0;
+    HIP_TRY(hipMalloc(&ws->links, sizeof(double) * lrow * (size_t)chunk));
+    ws->links_cap = chunk;
+  }
+  const size_t P = (size_t)w->dw.n_pairs;
+  for (long long off = 0; off < n; off += chunk) {
+    const long long m = std::min(chunk, n - off);
+    hipLaunchKernelGGL(fk_free_kernel, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, w->dw,
+                       q ? q + (size_t)off * w->dw.dof : nullptr, m, ws->links,
+                       free_pose ? free_pose + (size_t)off * free_stride : nullptr, free_stride);
+    HIP_TRY(hipGetLastError());
+    ContactOut sub{};
+    if (co) sub = ContactOut{co->depth + off * P, co->normal + off * P * 3, co->pos + off * P * 3};
+    rc = launch_collide<true>(w, ws->links, m, flags + off, masks ? masks + (size_t)off * w->dw.W : nullptr, s,
+                              co ? &sub : nullptr);
+    if (rc) return rc;
+  }
+  return MPG_OK;
+}
+
+// joint-value rows on the device, evaluated at the world's current free poses
+int launch_collide_q(mpg_world* w, const double* q, long long n, uint8_t* flags, uint32_t* masks, hipStream_t s,
+                     const ContactOut* co = nullptr) {
+  if (w->dw.n_free) return launch_collide_free(w, q, nullptr, 0, n, flags, masks, s, co);
+  return launch_collide<false>(w, q, n, flags, masks, s, co);
+}
+
+// finite values and unit quaternions (kFreeQuatTol) of host-memory free poses
+int check_free_poses(const double* p7, size_t count) {
+  for (size_t k = 0; k < count; ++k) {
+    const double* p = p7 + 7 * k;
+    if (!finite_all(p, 7)) return set_error(MPG_E_INVALID, "non-finite free pose");
+    const double nq = std::sqrt(p[3] * p[3] + p[4] * p[4] + p[5] * p[5] + p[6] * p[6]);
+    if (!(std::fabs(nq - 1.0) <= kFreeQuatTol))
+      return set_error(MPG_E_INVALID, "free pose quaternion is not of unit norm (within 1e-6)");
+  }
+  return MPG_OK;
+}
+
+// host buffers: rows staged to the device in passes of kFreeChunk; batches up
+// to the latency path's size take its one-launch kernel on the assembled rows
+int collide_free_host(mpg_world* w, const double* q, const double* free_pose, long long free_rows, int64_t n,
+                      uint8_t* flags, uint32_t* pair_mask, hipStream_t s) {
+  auto& F = w->free_stage;
+  auto grow = [&](void** p, size_t& cap, size_t want) -> int {
+    if (cap >= want) return MPG_OK;
+    if (*p) HIP_TRY(hipFree(*p));
+    *p = nullptr;
+    cap = 0;
+    HIP_TRY(hipMalloc(p, want));
+    cap = want;
+    return MPG_OK;
+  };
+  const size_t dof = (size_t)w->dw.dof, frow = (size_t)w->dw.n_free * 7, lrow = (size_t)w->dw.n_links * 7;
+  const size_t W = (size_t)w->dw.W;
+  const long long chunk = std::min<long long>(n, kFreeChunk);
+  int rc;
+  if ((rc = grow((void**)&F.q, F.q_cap, sizeof(double) * std::max<size_t>(1, dof * chunk)))) return rc;
+  if ((rc = grow((void**)&F.fp, F.fp_cap, sizeof(double) * frow * (free_rows > 1 ? chunk : 1)))) return rc;
+  if ((rc = grow((void**)&F.links, F.links_cap, sizeof(double) * lrow * chunk))) return rc;
+  // the latency kernel reads all n rows at once: only a batch that one pass
+  // assembles (small_batch_max may be set above kFreeChunk)
+  const bool small = n <= w->small_max && n <= chunk;
+  if (!small) {
+    if ((rc = grow((void**)&F.fl, F.fl_cap, (size_t)chunk))) return rc;
+    if ((rc = grow((void**)&F.mk, F.mk_cap, sizeof(uint32_t) * W * chunk))) return rc;
+  }
+  if (free_pose && free_rows == 1)
+    HIP_TRY(hipMemcpyAsync(F.fp, free_pose, sizeof(double) * frow, hipMemcpyHostToDevice, s));
+  for (long long off = 0; off < n; off += chunk) {
+    const long long m = std::min<long long>(chunk, n - off);
+    if (dof) HIP_TRY(hipMemcpyAsync(F.q, q + (size_t)off * dof, sizeof(double) * dof * m, hipMemcpyHostToDevice, s));
+    if (free_pose && free_rows > 1)
+      HIP_TRY(hipMemcpyAsync(F.fp, free_pose + (size_t)off * frow, sizeof(double) * frow * m, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(fk_free_kernel, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, w->dw, F.q, m, F.links,
+                       free_pose ? F.fp : nullptr, free_rows > 1 ? (long long)frow : 0ll);
+    HIP_TRY(hipGetLastError());
+    if (small) return collide_small<true>(w, nullptr, n, flags, pair_mask, s, F.links);
+    rc = launch_collide<true>(w, F.links, m, F.fl, pair_mask ? F.mk : nullptr, s);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(flags + off, F.fl, (size_t)m, hipMemcpyDeviceToHost, s));
+    if (pair_mask)
+      HIP_TRY(hipMemcpyAsync(pair_mask + (size_t)off * W, F.mk, sizeof(uint32_t) * W * m, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  return MPG_OK;
+}
+
+int collide_free(mpg_world* w, const double* q, const double* free_pose, int64_t free_rows, int64_t n, uint8_t* flags,
+                 uint32_t* pair_mask, int mem, void* stream) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
+  if (n > 0 && ((!q && w->dw.dof > 0) || !flags)) return set_error(MPG_E_INVALID, "input/flags is NULL");
+  if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
+  if (free_pose && free_rows != 1 && free_rows != n)
+    return set_error(MPG_E_INVALID, "free_rows must be 1 (shared by the batch) or n (one pose set per configuration)");
+  if (free_pose && w->dw.n_free == 0) return set_error(MPG_E_INVALID, "the world has no free frames");
+  if (w->dw.n_free == 0) return collide_common<false>(w, q, n, flags, pair_mask, mem, stream);
+  HIP_TRY(hipSetDevice(w->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const long long fstride = free_rows > 1 ? (long long)w->dw.n_free * 7 : 0ll;
+  if (mem == MPG_MEM_DEVICE) return launch_collide_free(w, q, free_pose, fstride, n, flags, pair_mask, s);
+  if (free_pose) {
+    const int rc = check_free_poses(free_pose, (size_t)free_rows * w->dw.n_free);
+    if (rc) return rc;
+  }
+  std::lock_guard<std::mutex> lk(w->host_mu);
+  if (!s && w->own_stream) s = w->own_stream;
+  if (n == 0) return MPG_OK;
+  return collide_free_host(w, q, free_pose, free_rows, n, flags, pair_mask, s);
 }
 }  // namespace
 
@@ -9328,6 +9641,34 @@ int mpg_collide_link_poses(mpg_world* w, const double* link_pose, int64_t n, uin
   return collide_common<true>(w, link_pose, n, flags, pair_mask, mem, stream);
 }
 
+int mpg_collide_batch_free(mpg_world* w, const double* q, const double* free_pose, int64_t free_rows, int64_t n,
+                           uint8_t* flags, uint32_t* pair_mask, int mem, void* stream) {
+  return collide_free(w, q, free_pose, free_rows, n, flags, pair_mask, mem, stream);
+}
+
+int mpg_world_set_free_poses(mpg_world* w, const double* pose7) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  if (w->dw.n_free == 0) return set_error(MPG_E_INVALID, "the world has no free frames");
+  if (!pose7) return set_error(MPG_E_INVALID, "pose7 is NULL");
+  const int rc = check_free_poses(pose7, (size_t)w->dw.n_free);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(w->device));
+  // calls in flight read the buffer: wait for them, then overwrite it in place
+  std::lock_guard<std::mutex> lk(w->host_mu);
+  HIP_TRY(hipDeviceSynchronize());
+  std::copy(pose7, pose7 + w->free_host.size(), w->free_host.begin());
+  HIP_TRY(hipMemcpy(w->free_dev, w->free_host.data(), sizeof(double) * w->free_host.size(), hipMemcpyHostToDevice));
+  return MPG_OK;
+}
+
+int mpg_world_get_free_info(const mpg_world* w, int32_t* n_free, double* far_radius, double* pose7) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  if (n_free) *n_free = w->dw.n_free;
+  if (far_radius) *far_radius = w->dw.far_r;
+  if (pose7) std::copy(w->free_host.begin(), w->free_host.end(), pose7);
+  return MPG_OK;
+}
+
 int mpg_check_motion_batch(mpg_world* w, const double* q_from, const double* q_to, int64_t n, uint32_t so2_mask,
                            double longest_valid_segment, uint8_t* valid, int32_t* first_invalid, int32_t* segments,
                            int mem, void* stream) {
@@ -9379,7 +9720,7 @@ int mpg_check_motion_batch(mpg_world* w, const double* q_from, const double* q_t
   hipLaunchKernelGGL(motion_states_kernel, dim3(grid), dim3(256), 0, s, from, to, (long long)n, dof, so2_mask, M.segs,
                      M.offs, M.states);
   HIP_TRY(hipGetLastError());
-  rc = launch_collide<false>(w, M.states, total, M.flags, nullptr, s);
+  rc = launch_collide_q(w, M.states, total, M.flags, nullptr, s);
   if (rc) return rc;
   uint8_t* d_valid = mem == MPG_MEM_DEVICE ? valid : reinterpret_cast<uint8_t*>(M.out + n);
   int32_t* d_first = first_invalid ? (mem == MPG_MEM_DEVICE ? first_invalid : M.out) : nullptr;
@@ -9473,7 +9814,16 @@ int mpg_distance_batch_req(mpg_world* w, const double* q, int64_t n, int32_t n_s
     if (!qo) qo = D.pts + 6 * n;
   }
   const unsigned grid = (unsigned)((n + 127) / 128);
-  hipLaunchKernelGGL((pose_kernel<false>), dim3(grid), dim3(128), 0, s, w->dw, qin, (long long)n, D.poses, D.save64);
+  if (w->dw.n_free) {  // link-pose rows with the current free poses, then the objects' transforms from them
+    if ((rc = grow((void**)&D.links, D.links_cap, sizeof(double) * 7 * w->dw.n_links * n))) return rc;
+    hipLaunchKernelGGL(fk_free_kernel, dim3(grid), dim3(128), 0, s, w->dw, qin, (long long)n, D.links,
+                       (const double*)nullptr, 0ll);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL((pose_kernel<true>), dim3(grid), dim3(128), 0, s, w->dw, D.links, (long long)n, D.poses,
+                       D.save64);
+  } else {
+    hipLaunchKernelGGL((pose_kernel<false>), dim3(grid), dim3(128), 0, s, w->dw, qin, (long long)n, D.poses, D.save64);
+  }
   HIP_TRY(hipGetLastError());
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(grid), dim3(128), 0, s, w->dw, D.poses, (long long)n, n_self_pairs, tol, dtol, ds,
@@ -9545,13 +9895,20 @@ int mpg_collide_contacts(mpg_world* w, const double* input, int64_t n, int input
   if (w->octree_first)  // contact_kernel reports the (shape, octree) order PlanningWorld uses
     return set_error(MPG_E_UNSUPPORTED, "contacts for a pair whose first object is an OcTree are not implemented");
   if (n == 0) return MPG_OK;
+  // host-memory link-pose rows: the free frames' columns are checked as every host-memory free pose is
+  if (poses && mem == MPG_MEM_HOST && w->dw.n_free)
+    for (int64_t i = 0; i < n; ++i) {
+      const int rc = check_free_poses(input + ((size_t)i * w->dw.n_links + (w->dw.n_links - w->dw.n_free)) * 7,
+                                      (size_t)w->dw.n_free);
+      if (rc) return rc;
+    }
   HIP_TRY(hipSetDevice(w->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t P = (size_t)w->dw.n_pairs, W = (size_t)w->dw.W;
   if (mem == MPG_MEM_DEVICE) {
     ContactOut co{depth, normal, pos};
     return poses ? launch_collide<true>(w, input, n, flags, pair_mask, s, &co)
-                 : launch_collide<false>(w, input, n, flags, pair_mask, s, &co);
+                 : launch_collide_q(w, input, n, flags, pair_mask, s, &co);
   }
   // host buffers: grow-only device staging kept by the world (one host call
   // at a time: host_mu), no allocation per call
@@ -9583,7 +9940,7 @@ int mpg_collide_contacts(mpg_world* w, const double* input, int64_t n, int input
       break;
     }
     ContactOut co{d_out, d_out + P * n, d_out + 4 * P * n};
-    rc = poses ? launch_collide<true>(w, d_in, n, d_fl, d_mk, s, &co) : launch_collide<false>(w, d_in, n, d_fl, d_mk, s, &co);
+    rc = poses ? launch_collide<true>(w, d_in, n, d_fl, d_mk, s, &co) : launch_collide_q(w, d_in, n, d_fl, d_mk, s, &co);
     if (rc) break;
     if (hipMemcpyAsync(flags, d_fl, n, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemcpyAsync(pair_mask, d_mk, sizeof(uint32_t) * W * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -9605,7 +9962,11 @@ int mpg_fk_batch(mpg_world* w, const double* q, int64_t n, double* link_pose, in
   const size_t nout = (size_t)n * w->dw.n_links * 7;
   const unsigned grid = (unsigned)((n + 127) / 128);
   if (mem == MPG_MEM_DEVICE) {
-    if (n) hipLaunchKernelGGL(fk_kernel, dim3(grid), dim3(128), 0, s, w->dw, q, (long long)n, link_pose);
+    if (n && w->dw.n_free)
+      hipLaunchKernelGGL(fk_free_kernel, dim3(grid), dim3(128), 0, s, w->dw, q, (long long)n, link_pose,
+                         (const double*)nullptr, 0ll);
+    else if (n)
+      hipLaunchKernelGGL(fk_kernel, dim3(grid), dim3(128), 0, s, w->dw, q, (long long)n, link_pose);
     HIP_TRY(hipGetLastError());
     return MPG_OK;
   }
@@ -9615,7 +9976,11 @@ int mpg_fk_batch(mpg_world* w, const double* q, int64_t n, double* link_pose, in
   if (rc) return rc;
   if (n == 0) return MPG_OK;
   HIP_TRY(hipMemcpyAsync(w->d_q, q, sizeof(double) * n * w->dw.dof, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(fk_kernel, dim3(grid), dim3(128), 0, s, w->dw, w->d_q, (long long)n, w->d_out);
+  if (w->dw.n_free)
+    hipLaunchKernelGGL(fk_free_kernel, dim3(grid), dim3(128), 0, s, w->dw, w->d_q, (long long)n, w->d_out,
+                       (const double*)nullptr, 0ll);
+  else
+    hipLaunchKernelGGL(fk_kernel, dim3(grid), dim3(128), 0, s, w->dw, w->d_q, (long long)n, w->d_out);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(link_pose, w->d_out, sizeof(double) * nout, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -9743,7 +10108,8 @@ int mpg_collide_count(mpg_world* w, const double* lower, const double* upper, in
                          off, b.q);
       HIP_TRY(hipGetLastError());
     }
-    const int rc = launch_collide_overlapped<false>(w, b.q, m, b.fl, b.mk, s);
+    const int rc = w->dw.n_free ? launch_collide_q(w, b.q, m, b.fl, b.mk, s)
+                                : launch_collide_overlapped<false>(w, b.q, m, b.fl, b.mk, s);
     if (rc) return rc;
     const unsigned grid = (unsigned)std::min<long long>(1024, (m + 255) / 256);
     hipLaunchKernelGGL(pair_count_kernel, dim3(grid), dim3(256), sizeof(uint32_t) * P, s, b.mk, m, W, P, b.cnt);
