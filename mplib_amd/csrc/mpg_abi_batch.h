@@ -1,0 +1,663 @@
+// mpg_abi_batch.h -- C entry points of include/mpgpu.h: the batch calls
+// (collide, distance, contacts, FK, motion, sampling) and the debug entries
+// (included by mpg_kernels.hip inside extern "C", after mpg_collide_host.h).
+#pragma once
+
+int mpg_release_stream(mpg_world* w, void* stream) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  HIP_TRY(hipSetDevice(w->device));
+  std::lock_guard<std::mutex> lk(w->ws_mu);
+  const auto b = w->busy.find(static_cast<hipStream_t>(stream));
+  if (b != w->busy.end() && b->second > 0) return set_error(MPG_E_INVALID, "stream has a call in progress");
+  release_stream_locked(w, static_cast<hipStream_t>(stream));
+  return MPG_OK;
+}
+
+int mpg_set_small_batch_max(mpg_world* w, int64_t n) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
+  std::lock_guard<std::mutex> lk(w->host_mu);
+  w->small_max = n;
+  return MPG_OK;
+}
+
+int mpg_collide_batch(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint32_t* pair_mask, int mem,
+                      void* stream) {
+  return collide_common<false>(w, q, n, flags, pair_mask, mem, stream);
+}
+
+int mpg_collide_batch_multi(mpg_world* const* worlds, int32_t n_worlds, const double* q, int64_t n, uint8_t* flags,
+                            uint32_t* pair_mask) {
+  if (n_worlds <= 0 || !worlds) return set_error(MPG_E_INVALID, "no worlds");
+  if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
+  if (n > 0 && (!q || !flags)) return set_error(MPG_E_INVALID, "q / flags is NULL");
+  mpg_world_info i0{};
+  for (int k = 0; k < n_worlds; ++k) {
+    mpg_world_info ik{};
+    if (!worlds[k]) return set_error(MPG_E_INVALID, "world " + std::to_string(k) + " is NULL");
+    mpg_world_get_info(worlds[k], &ik);
+    if (k == 0) {
+      i0 = ik;
+    } else if (ik.dof != i0.dof || ik.n_pairs != i0.n_pairs || ik.mask_words != i0.mask_words ||
+               ik.n_links != i0.n_links || ik.snapshot_bytes != i0.snapshot_bytes ||
+               worlds[k]->snapshot_hash != worlds[0]->snapshot_hash) {
+      return set_error(MPG_E_INVALID, "world " + std::to_string(k) + " was not built from world 0's descriptor");
+    }
+    for (int j = 0; j < k; ++j)
+      if (worlds[j] == worlds[k]) return set_error(MPG_E_INVALID, "a world is listed twice");
+  }
+  std::vector<int> rc(n_worlds, MPG_OK);
+  std::vector<std::string> err(n_worlds);
+  auto run = [&](int k) {
+    int64_t start = 0, count = 0;
+    mpg_shard_range(n, k, n_worlds, &start, &count);
+    if (count == 0) return;
+    rc[k] = mpg_collide_batch(worlds[k], q + (size_t)start * i0.dof, count, flags + start,
+                              pair_mask ? pair_mask + (size_t)start * i0.mask_words : nullptr, MPG_MEM_HOST, nullptr);
+    if (rc[k]) err[k] = g_last_error;  // the worker thread's error text
+  };
+  std::vector<std::thread> th;
+  for (int k = 1; k < n_worlds; ++k) th.emplace_back(run, k);
+  run(0);
+  for (auto& t : th) t.join();
+  for (int k = 0; k < n_worlds; ++k)
+    if (rc[k]) return set_error(rc[k], "world " + std::to_string(k) + ": " + err[k]);
+  return MPG_OK;
+}
+
+int mpg_shard_range(int64_t n, int32_t k, int32_t n_parts, int64_t* start, int64_t* count) {
+  if (n < 0 || n_parts <= 0 || k < 0 || k >= n_parts || !start || !count)
+    return set_error(MPG_E_INVALID, "mpg_shard_range: bad arguments");
+  // contiguous shards, the first n % n_parts one row longer (mplib_amd.dist.shard_range)
+  const int64_t base = n / n_parts, rem = n % n_parts;
+  *start = k * base + std::min<int64_t>(k, rem);
+  *count = base + (k < rem ? 1 : 0);
+  return MPG_OK;
+}
+
+int mpg_collide_batch_multi_device(mpg_world* const* worlds, int32_t n_worlds, const double* const* q,
+                                   const int64_t* counts, uint8_t* const* flags, uint32_t* const* pair_mask,
+                                   void* const* streams, uint8_t* gather_flags, uint32_t* gather_masks) {
+  if (n_worlds <= 0 || !worlds) return set_error(MPG_E_INVALID, "no worlds");
+  if (!counts || !q || !flags) return set_error(MPG_E_INVALID, "counts / q / flags array is NULL");
+  if (gather_masks && !pair_mask) return set_error(MPG_E_INVALID, "gather_masks needs pair_mask");
+  for (int k = 0; k < n_worlds; ++k) {
+    if (!worlds[k]) return set_error(MPG_E_INVALID, "world " + std::to_string(k) + " is NULL");
+    if (counts[k] < 0) return set_error(MPG_E_INVALID, "counts[" + std::to_string(k) + "] < 0");
+    for (int j = 0; j < k; ++j)
+      if (worlds[j] == worlds[k]) return set_error(MPG_E_INVALID, "a world is listed twice");
+  }
+  const mpg_world* w0 = worlds[0];
+  for (int k = 0; k < n_worlds; ++k) {
+    const mpg_world* wk = worlds[k];
+    if (wk->dw.dof != w0->dw.dof || wk->dw.n_pairs != w0->dw.n_pairs || wk->dw.W != w0->dw.W ||
+        wk->blob_bytes != w0->blob_bytes || wk->snapshot_hash != w0->snapshot_hash)
+      return set_error(MPG_E_INVALID, "world " + std::to_string(k) + " was not built from world 0's descriptor");
+    if (counts[k] > 0 && ((!q[k] && wk->dw.dof > 0) || !flags[k]))
+      return set_error(MPG_E_INVALID, "shard " + std::to_string(k) + ": q / flags is NULL");
+    if (counts[k] > 0 && gather_masks && !pair_mask[k])
+      return set_error(MPG_E_INVALID, "shard " + std::to_string(k) + ": gather_masks needs its pair_mask");
+  }
+  const int W = w0->dw.W;
+  std::vector<int64_t> off(n_worlds + 1, 0);
+  for (int k = 0; k < n_worlds; ++k) off[k + 1] = off[k] + counts[k];
+  const bool gather = gather_flags || gather_masks;
+  if (gather) {  // direct peer copies over xGMI from every other device into device 0
+    HIP_TRY(hipSetDevice(w0->device));
+    for (int k = 1; k < n_worlds; ++k) {
+      if (worlds[k]->device == w0->device) continue;
+      int can = 0;
+      HIP_TRY(hipDeviceCanAccessPeer(&can, w0->device, worlds[k]->device));
+      if (!can) continue;  // hipMemcpyPeerAsync still works, staged by the runtime
+      const hipError_t e = hipDeviceEnablePeerAccess(worlds[k]->device, 0);
+      if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled)
+        return set_error(MPG_E_HIP, std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e));
+      (void)hipGetLastError();
+    }
+  }
+  std::vector<int> rc(n_worlds, MPG_OK);
+  std::vector<std::string> err(n_worlds);
+  auto run = [&](int k) {
+    mpg_world* w = worlds[k];
+    hipStream_t s = streams ? static_cast<hipStream_t>(streams[k]) : nullptr;
+    uint32_t* mk = pair_mask ? pair_mask[k] : nullptr;
+    auto fail = [&](int code, const std::string& m) {
+      rc[k] = code;
+      err[k] = m;
+    };
+    if (hipSetDevice(w->device) != hipSuccess) return fail(MPG_E_HIP, "hipSetDevice failed");
+    if (counts[k] > 0) {
+      const int r = mpg_collide_batch(w, q[k], counts[k], flags[k], mk, MPG_MEM_DEVICE, s);
+      if (r) return fail(r, g_last_error);
+    }
+    if (!gather) return;
+    hipError_t e = hipSuccess;
+    if (counts[k] > 0 && gather_flags)
+      e = hipMemcpyPeerAsync(gather_flags + off[k], w0->device, flags[k], w->device, (size_t)counts[k], s);
+    if (e == hipSuccess && counts[k] > 0 && gather_masks)
+      e = hipMemcpyPeerAsync(gather_masks + off[k] * W, w0->device, mk, w->device,
+                             sizeof(uint32_t) * (size_t)counts[k] * W, s);
+    if (e == hipSuccess && k > 0) {
+      if (!w->gather_ev) e = hipEventCreateWithFlags(&w->gather_ev, hipEventDisableTiming);
+      if (e == hipSuccess) e = hipEventRecord(w->gather_ev, s);
+    }
+    if (e != hipSuccess) return fail(MPG_E_HIP, std::string("gather: ") + hipGetErrorString(e));
+  };
+  std::vector<std::thread> th;
+  for (int k = 1; k < n_worlds; ++k) th.emplace_back(run, k);
+  run(0);
+  for (auto& t : th) t.join();
+  for (int k = 0; k < n_worlds; ++k)
+    if (rc[k]) return set_error(rc[k], "world " + std::to_string(k) + ": " + err[k]);
+  if (gather) {  // streams[0] orders after every shard's copies
+    HIP_TRY(hipSetDevice(w0->device));
+    hipStream_t s0 = streams ? static_cast<hipStream_t>(streams[0]) : nullptr;
+    for (int k = 1; k < n_worlds; ++k) HIP_TRY(hipStreamWaitEvent(s0, worlds[k]->gather_ev, 0));
+  }
+  return MPG_OK;
+}
+
+int mpg_collide_link_poses(mpg_world* w, const double* link_pose, int64_t n, uint8_t* flags, uint32_t* pair_mask,
+                           int mem, void* stream) {
+  return collide_common<true>(w, link_pose, n, flags, pair_mask, mem, stream);
+}
+
+int mpg_collide_batch_free(mpg_world* w, const double* q, const double* free_pose, int64_t free_rows, int64_t n,
+                           uint8_t* flags, uint32_t* pair_mask, int mem, void* stream) {
+  return collide_free(w, q, free_pose, free_rows, n, flags, pair_mask, mem, stream);
+}
+
+int mpg_world_set_free_poses(mpg_world* w, const double* pose7) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  if (w->dw.n_free == 0) return set_error(MPG_E_INVALID, "the world has no free frames");
+  if (!pose7) return set_error(MPG_E_INVALID, "pose7 is NULL");
+  const int rc = check_free_poses(pose7, (size_t)w->dw.n_free);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(w->device));
+  // calls in flight read the buffer: wait for them, then overwrite it in place
+  std::lock_guard<std::mutex> lk(w->host_mu);
+  HIP_TRY(hipDeviceSynchronize());
+  std::copy(pose7, pose7 + w->free_host.size(), w->free_host.begin());
+  HIP_TRY(hipMemcpy(w->free_dev, w->free_host.data(), sizeof(double) * w->free_host.size(), hipMemcpyHostToDevice));
+  return MPG_OK;
+}
+
+int mpg_world_get_free_info(const mpg_world* w, int32_t* n_free, double* far_radius, double* pose7) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  if (n_free) *n_free = w->dw.n_free;
+  if (far_radius) *far_radius = w->dw.far_r;
+  if (pose7) std::copy(w->free_host.begin(), w->free_host.end(), pose7);
+  return MPG_OK;
+}
+
+int mpg_check_motion_batch(mpg_world* w, const double* q_from, const double* q_to, int64_t n, uint32_t so2_mask,
+                           double longest_valid_segment, uint8_t* valid, int32_t* first_invalid, int32_t* segments,
+                           int mem, void* stream) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
+  if (n > 0 && (!q_from || !q_to || !valid)) return set_error(MPG_E_INVALID, "from/to/valid is NULL");
+  if (!(longest_valid_segment > 0.0)) return set_error(MPG_E_INVALID, "longest_valid_segment must be > 0");
+  if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
+  if (w->dw.dof > 32) return set_error(MPG_E_UNSUPPORTED, "motion validation supports dof <= 32");
+  if (n == 0) return MPG_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(w->motion_mu);
+  const int dof = w->dw.dof;
+  const size_t eb = sizeof(double) * (size_t)n * dof;
+  auto& M = w->motion;
+  auto grow = [&](void** p, size_t& cap, size_t want) { return scratch_grow(M.last, p, cap, want); };
+  int rc = scratch_begin(M.last, s);
+  if (rc) return rc;
+  if ((rc = grow((void**)&M.edges, M.edges_cap, 2 * eb))) return rc;
+  if ((rc = grow((void**)&M.segs, M.segs_cap, sizeof(int32_t) * n))) return rc;
+  if ((rc = grow((void**)&M.offs, M.offs_cap, sizeof(long long) * n))) return rc;
+  if ((rc = grow((void**)&M.out, M.out_cap, (sizeof(int32_t) + 1) * n))) return rc;
+  const double* from = q_from;
+  const double* to = q_to;
+  if (mem == MPG_MEM_HOST) {
+    HIP_TRY(hipMemcpyAsync(M.edges, q_from, eb, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(M.edges + (size_t)n * dof, q_to, eb, hipMemcpyHostToDevice, s));
+    from = M.edges;
+    to = M.edges + (size_t)n * dof;
+  }
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  hipLaunchKernelGGL(motion_count_kernel, dim3(grid), dim3(256), 0, s, from, to, (long long)n, dof, so2_mask,
+                     longest_valid_segment, M.segs);
+  HIP_TRY(hipGetLastError());
+  // the state count decides the allocation: one synchronisation per call
+  std::vector<int32_t> segs((size_t)n);
+  HIP_TRY(hipMemcpyAsync(segs.data(), M.segs, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  std::vector<long long> offs((size_t)n);
+  long long total = 0;
+  for (int64_t e = 0; e < n; ++e) {
+    offs[e] = total;
+    total += segs[e];
+  }
+  HIP_TRY(hipMemcpyAsync(M.offs, offs.data(), sizeof(long long) * n, hipMemcpyHostToDevice, s));
+  if ((rc = grow((void**)&M.states, M.states_cap, sizeof(double) * (size_t)total * dof))) return rc;
+  if ((rc = grow((void**)&M.flags, M.flags_cap, (size_t)total))) return rc;
+  hipLaunchKernelGGL(motion_states_kernel, dim3(grid), dim3(256), 0, s, from, to, (long long)n, dof, so2_mask, M.segs,
+                     M.offs, M.states);
+  HIP_TRY(hipGetLastError());
+  rc = launch_collide_q(w, M.states, total, M.flags, nullptr, s);
+  if (rc) return rc;
+  uint8_t* d_valid = mem == MPG_MEM_DEVICE ? valid : reinterpret_cast<uint8_t*>(M.out + n);
+  int32_t* d_first = first_invalid ? (mem == MPG_MEM_DEVICE ? first_invalid : M.out) : nullptr;
+  hipLaunchKernelGGL(motion_reduce_kernel, dim3(grid), dim3(256), 0, s, M.flags, (long long)n, M.segs, M.offs, d_valid,
+                     d_first);
+  HIP_TRY(hipGetLastError());
+  if (mem == MPG_MEM_HOST) {
+    HIP_TRY(hipMemcpyAsync(valid, d_valid, n, hipMemcpyDeviceToHost, s));
+    if (first_invalid) HIP_TRY(hipMemcpyAsync(first_invalid, d_first, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (segments) std::memcpy(segments, segs.data(), sizeof(int32_t) * n);
+  } else if (segments) {
+    HIP_TRY(hipMemcpyAsync(segments, M.segs, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, s));
+  }
+  HIP_TRY(hipEventRecord(M.last, s));
+  return MPG_OK;
+}
+
+int mpg_distance_batch(mpg_world* w, const double* q, int64_t n, int32_t n_self_pairs, double* d_self,
+                       int32_t* p_self, double* d_others, int32_t* p_others, int mem, void* stream) {
+  return mpg_distance_batch_ex(w, q, n, n_self_pairs, 0, d_self, p_self, nullptr, d_others, p_others, nullptr, mem,
+                               stream);
+}
+
+int mpg_distance_batch_ex(mpg_world* w, const double* q, int64_t n, int32_t n_self_pairs, int32_t flags,
+                          double* d_self, int32_t* p_self, double* pts_self, double* d_others, int32_t* p_others,
+                          double* pts_others, int mem, void* stream) {
+  mpg_distance_request req;
+  req.flags = flags;
+  req.distance_tolerance = 1e-6;
+  return mpg_distance_batch_req(w, q, n, n_self_pairs, &req, d_self, p_self, pts_self, d_others, p_others, pts_others,
+                                mem, stream);
+}
+
+int mpg_distance_batch_req(mpg_world* w, const double* q, int64_t n, int32_t n_self_pairs,
+                           const mpg_distance_request* req, double* d_self, int32_t* p_self, double* pts_self,
+                           double* d_others, int32_t* p_others, double* pts_others, int mem, void* stream) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  if (!req) return set_error(MPG_E_INVALID, "request is NULL");
+  if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
+  if (n_self_pairs < 0 || n_self_pairs > w->dw.n_pairs) return set_error(MPG_E_INVALID, "bad n_self_pairs");
+  if (n > 0 && ((!q && w->dw.dof > 0) || !d_self || !p_self || !d_others || !p_others))
+    return set_error(MPG_E_INVALID, "NULL buffer");
+  if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
+  const int32_t flags = req->flags;
+  if (flags & ~(MPG_DISTANCE_SIGNED | MPG_DISTANCE_NEAREST_POINTS | MPG_DISTANCE_GJK_INDEP))
+    return set_error(MPG_E_INVALID, "bad flags");
+  if (!(req->distance_tolerance >= 0.0)) return set_error(MPG_E_INVALID, "bad distance_tolerance");
+  if (w->has_octree2)
+    return set_error(MPG_E_UNSUPPORTED, "distance for a pair of two OcTrees (OcTreeDistanceRecurse) is not implemented");
+  const bool indep = (flags & MPG_DISTANCE_GJK_INDEP) != 0;
+  if (indep && (flags & MPG_DISTANCE_SIGNED))
+    return set_error(MPG_E_UNSUPPORTED, "signed distance with GST_INDEP (FCL's EPA) is not implemented");
+  if (indep && (w->has_mesh || w->has_octree))
+    return set_error(MPG_E_UNSUPPORTED, "distance with GST_INDEP for an OcTree or BVH mesh pair is not implemented");
+  const ccd_real tol = (ccd_real)req->distance_tolerance;  // GJKSolver_libccd::distance_tolerance -> ccd.dist_tolerance
+  const double dtol = req->distance_tolerance;              // GJKSolver_indep::gjk_tolerance (distance-inl.h)
+  const bool want_pts = pts_self || pts_others;
+  const int mode = (want_pts || (flags & (MPG_DISTANCE_SIGNED | MPG_DISTANCE_NEAREST_POINTS)) ? MPG_DIST_POINTS : 0) |
+                   (flags & MPG_DISTANCE_SIGNED ? MPG_DIST_SIGNED : 0) |
+                   (flags & MPG_DISTANCE_NEAREST_POINTS ? MPG_DIST_NP : 0) | (indep ? MPG_DIST_INDEP : 0);
+  if (n == 0) return MPG_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(w->dist_mu);
+  auto& D = w->dist;
+  auto grow = [&](void** p, size_t& cap, size_t want) { return scratch_grow(D.last, p, cap, want); };
+  int rc = scratch_begin(D.last, s);
+  if (rc) return rc;
+  const size_t nm = std::max(w->dw.n_moving, 1), ns = std::max(w->dw.bp.n_saves, 1);
+  if ((rc = grow((void**)&D.poses, D.poses_cap, sizeof(double) * kPoseStride * nm * n))) return rc;
+  if ((rc = grow((void**)&D.save64, D.save_cap, sizeof(double) * 12 * ns * n))) return rc;
+  const double* qin = q;
+  double *ds = d_self, *dd = d_others, *qs = pts_self, *qo = pts_others;
+  int32_t *ps = p_self, *po = p_others;
+  const size_t out_bytes = (2 * sizeof(double) + 2 * sizeof(int32_t) + (mode ? 12 * sizeof(double) : 0)) * n;
+  if (mem == MPG_MEM_HOST) {
+    if ((rc = grow((void**)&D.q, D.q_cap, sizeof(double) * std::max(w->dw.dof, 1) * n))) return rc;
+    if ((rc = grow((void**)&D.out, D.out_cap, out_bytes))) return rc;
+    if (w->dw.dof) HIP_TRY(hipMemcpyAsync(D.q, q, sizeof(double) * w->dw.dof * n, hipMemcpyHostToDevice, s));
+    qin = D.q;
+    ds = reinterpret_cast<double*>(D.out);
+    dd = ds + n;
+    qs = dd + n;
+    qo = qs + (mode ? 6 * n : 0);
+    ps = reinterpret_cast<int32_t*>(qo + (mode ? 6 * n : 0));
+    po = ps + n;
+  } else if (mode && (!qs || !qo)) {  // device buffers: scratch for the points nobody asked for
+    if ((rc = grow((void**)&D.pts, D.pts_cap, 12 * sizeof(double) * n))) return rc;
+    if (!qs) qs = D.pts;
+    if (!qo) qo = D.pts + 6 * n;
+  }
+  const unsigned grid = (unsigned)((n + 127) / 128);
+  if (w->dw.n_free) {  // link-pose rows with the current free poses, then the objects' transforms from them
+    if ((rc = grow((void**)&D.links, D.links_cap, sizeof(double) * 7 * w->dw.n_links * n))) return rc;
+    hipLaunchKernelGGL(fk_free_kernel, dim3(grid), dim3(128), 0, s, w->dw, qin, (long long)n, D.links,
+                       (const double*)nullptr, 0ll);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL((pose_kernel<true>), dim3(grid), dim3(128), 0, s, w->dw, D.links, (long long)n, D.poses,
+                       D.save64);
+  } else {
+    hipLaunchKernelGGL((pose_kernel<false>), dim3(grid), dim3(128), 0, s, w->dw, qin, (long long)n, D.poses, D.save64);
+  }
+  HIP_TRY(hipGetLastError());
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(128), 0, s, w->dw, D.poses, (long long)n, n_self_pairs, tol, dtol, ds,
+                       ps, dd, po, qs, qo);
+    return hipGetLastError();
+  };
+  constexpr int P = MPG_DIST_POINTS, SG = MPG_DIST_SIGNED, NPF = MPG_DIST_NP, IN = MPG_DIST_INDEP;
+  switch (mode) {
+    case 0: HIP_TRY(launch(distance_kernel<0>)); break;
+    case P: HIP_TRY(launch(distance_kernel<P>)); break;
+    case P | NPF: HIP_TRY(launch(distance_kernel<P | NPF>)); break;
+    case P | SG: HIP_TRY(launch(distance_kernel<P | SG>)); break;
+    case P | SG | NPF: HIP_TRY(launch(distance_kernel<P | SG | NPF>)); break;
+    case IN: HIP_TRY(launch(distance_kernel<IN>)); break;
+    case P | IN: HIP_TRY(launch(distance_kernel<P | IN>)); break;
+    default: HIP_TRY(launch(distance_kernel<P | NPF | IN>)); break;
+  }
+  if (mode & SG) {  // EPAs past the private polytope: again with a big one from the pool
+    if ((rc = grow((void**)&D.big, D.big_cap, sizeof(ccdx::BigPolytope) * kBigPool))) return rc;
+    if ((rc = grow((void**)&D.list, D.list_cap, sizeof(unsigned) * (n + 1)))) return rc;
+    HIP_TRY(hipMemsetAsync(D.list, 0, sizeof(unsigned), s));
+    hipLaunchKernelGGL(overflow_list_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ps, (long long)n,
+                       D.list);
+    HIP_TRY(hipGetLastError());
+    auto redo = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(1), dim3(kBigPool), 0, s, w->dw, D.poses, (long long)n, n_self_pairs, tol, dtol,
+                         ds, ps, dd, po, qs, qo, D.big, D.list);
+      return hipGetLastError();
+    };
+    if (mode & NPF) HIP_TRY(redo(distance_redo_kernel<P | SG | NPF>));
+    else HIP_TRY(redo(distance_redo_kernel<P | SG>));
+  }
+  HIP_TRY(hipEventRecord(D.last, s));
+  if (mem == MPG_MEM_HOST) {
+    HIP_TRY(hipMemcpyAsync(d_self, ds, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(d_others, dd, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(p_self, ps, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(p_others, po, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+    if (mode && pts_self) HIP_TRY(hipMemcpyAsync(pts_self, qs, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, s));
+    if (mode && pts_others) HIP_TRY(hipMemcpyAsync(pts_others, qo, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int64_t i = 0; i < n; ++i) {
+      if (p_self[i] == MPG_DISTANCE_FCL_THROWS)
+        return set_error(MPG_E_FAILED, "configuration " + std::to_string(i) +
+                                           ": FCL's libccd EPA throws here (FCL_THROW_FAILED_AT_THIS_CONFIGURATION)");
+      if (p_self[i] == MPG_DISTANCE_EPA_CAPACITY)
+        return set_error(MPG_E_UNSUPPORTED, "configuration " + std::to_string(i) +
+                                                ": EPA polytope beyond the device capacity (" +
+                                                std::to_string(ccdx::kBigPtV) + " vertices)");
+    }
+  }
+  return MPG_OK;
+}
+
+int mpg_collide_contacts(mpg_world* w, const double* input, int64_t n, int input_kind, uint8_t* flags,
+                         uint32_t* pair_mask, double* depth, double* normal, double* pos, int mem, void* stream) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
+  if (input_kind != MPG_INPUT_Q && input_kind != MPG_INPUT_LINK_POSES) return set_error(MPG_E_INVALID, "bad input_kind");
+  const bool poses = input_kind == MPG_INPUT_LINK_POSES;
+  const size_t row = poses ? (size_t)w->dw.n_links * 7 : (size_t)w->dw.dof;
+  if (n > 0 && ((!input && row > 0) || !flags || !pair_mask || !depth || !normal || !pos))
+    return set_error(MPG_E_INVALID, "NULL buffer");
+  if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
+  if (w->any_gjk)
+    return set_error(MPG_E_UNSUPPORTED, "contacts with gjk_solver MPG_GJK_INDEP (FCL's EPA) are not implemented");
+  if (w->has_octree2)
+    return set_error(MPG_E_UNSUPPORTED, "contacts for a pair of two OcTrees are not implemented");
+  if (w->octree_first)  // contact_kernel reports the (shape, octree) order PlanningWorld uses
+    return set_error(MPG_E_UNSUPPORTED, "contacts for a pair whose first object is an OcTree are not implemented");
+  if (n == 0) return MPG_OK;
+  // host-memory link-pose rows: the free frames' columns are checked as every host-memory free pose is
+  if (poses && mem == MPG_MEM_HOST && w->dw.n_free)
+    for (int64_t i = 0; i < n; ++i) {
+      const int rc = check_free_poses(input + ((size_t)i * w->dw.n_links + (w->dw.n_links - w->dw.n_free)) * 7,
+                                      (size_t)w->dw.n_free);
+      if (rc) return rc;
+    }
+  HIP_TRY(hipSetDevice(w->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t P = (size_t)w->dw.n_pairs, W = (size_t)w->dw.W;
+  if (mem == MPG_MEM_DEVICE) {
+    ContactOut co{depth, normal, pos};
+    return poses ? launch_collide<true>(w, input, n, flags, pair_mask, s, &co)
+                 : launch_collide_q(w, input, n, flags, pair_mask, s, &co);
+  }
+  // host buffers: grow-only device staging kept by the world (one host call
+  // at a time: host_mu), no allocation per call
+  std::lock_guard<std::mutex> lk(w->host_mu);
+  if (!s && w->own_stream) s = w->own_stream;
+  auto grow = [&](void** p, size_t& cap, size_t want) -> bool {
+    if (cap >= want) return true;
+    if (*p) hipFree(*p);
+    *p = nullptr;
+    cap = 0;
+    if (hipMalloc(p, want) != hipSuccess) return false;
+    cap = want;
+    return true;
+  };
+  auto& C = w->contact;
+  int rc = MPG_OK;
+  do {
+    if (!grow((void**)&C.in, C.in_cap, sizeof(double) * std::max<size_t>(1, row * n)) ||
+        !grow((void**)&C.out, C.out_cap, sizeof(double) * 7 * P * n) || !grow((void**)&C.fl, C.fl_cap, n) ||
+        !grow((void**)&C.mk, C.mk_cap, sizeof(uint32_t) * W * n)) {
+      rc = set_error(MPG_E_NOMEM, "contact staging buffers");
+      break;
+    }
+    double *d_in = C.in, *d_out = C.out;
+    uint8_t* d_fl = C.fl;
+    uint32_t* d_mk = C.mk;
+    if (row && hipMemcpyAsync(d_in, input, sizeof(double) * row * n, hipMemcpyHostToDevice, s) != hipSuccess) {
+      rc = set_error(MPG_E_HIP, "copy input");
+      break;
+    }
+    ContactOut co{d_out, d_out + P * n, d_out + 4 * P * n};
+    rc = poses ? launch_collide<true>(w, d_in, n, d_fl, d_mk, s, &co) : launch_collide_q(w, d_in, n, d_fl, d_mk, s, &co);
+    if (rc) break;
+    if (hipMemcpyAsync(flags, d_fl, n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(pair_mask, d_mk, sizeof(uint32_t) * W * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(depth, co.depth, sizeof(double) * P * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(normal, co.normal, sizeof(double) * 3 * P * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(pos, co.pos, sizeof(double) * 3 * P * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+      rc = set_error(MPG_E_HIP, "copy contact results");
+  } while (false);
+  return rc;
+}
+
+int mpg_fk_batch(mpg_world* w, const double* q, int64_t n, double* link_pose, int mem, void* stream) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
+  if (n > 0 && (!q || !link_pose)) return set_error(MPG_E_INVALID, "q/link_pose is NULL");
+  HIP_TRY(hipSetDevice(w->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t nout = (size_t)n * w->dw.n_links * 7;
+  const unsigned grid = (unsigned)((n + 127) / 128);
+  if (mem == MPG_MEM_DEVICE) {
+    if (n && w->dw.n_free)
+      hipLaunchKernelGGL(fk_free_kernel, dim3(grid), dim3(128), 0, s, w->dw, q, (long long)n, link_pose,
+                         (const double*)nullptr, 0ll);
+    else if (n)
+      hipLaunchKernelGGL(fk_kernel, dim3(grid), dim3(128), 0, s, w->dw, q, (long long)n, link_pose);
+    HIP_TRY(hipGetLastError());
+    return MPG_OK;
+  }
+  if (mem != MPG_MEM_HOST) return set_error(MPG_E_INVALID, "bad mem kind");
+  std::lock_guard<std::mutex> lk(w->host_mu);
+  int rc = ensure_staging(w, (size_t)n, std::max<size_t>(nout, 1));
+  if (rc) return rc;
+  if (n == 0) return MPG_OK;
+  HIP_TRY(hipMemcpyAsync(w->d_q, q, sizeof(double) * n * w->dw.dof, hipMemcpyHostToDevice, s));
+  if (w->dw.n_free)
+    hipLaunchKernelGGL(fk_free_kernel, dim3(grid), dim3(128), 0, s, w->dw, w->d_q, (long long)n, w->d_out,
+                       (const double*)nullptr, 0ll);
+  else
+    hipLaunchKernelGGL(fk_kernel, dim3(grid), dim3(128), 0, s, w->dw, w->d_q, (long long)n, w->d_out);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(link_pose, w->d_out, sizeof(double) * nout, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return MPG_OK;
+}
+
+int mpg_debug_collide_pairs(mpg_world* w, int32_t geom_a, int32_t geom_b, int64_t n, const double* Ta,
+                            const double* Tb, uint8_t* hit) {
+  if (!w || n < 0 || (n > 0 && (!Ta || !Tb || !hit))) return set_error(MPG_E_INVALID, "bad arguments");
+  if (geom_a < 0 || geom_b < 0 || geom_a >= w->n_geoms || geom_b >= w->n_geoms)
+    return set_error(MPG_E_INVALID, "geometry index out of range");
+  if (n == 0) return MPG_OK;
+  const int ta = w->geom_type_h[geom_a], tb = w->geom_type_h[geom_b];
+  int cf = CF_NONE;
+  if (ta == MPG_GEOM_MESH || tb == MPG_GEOM_MESH) cf = CF_MESH;
+  else if (ta == MPG_GEOM_OCTREE || tb == MPG_GEOM_OCTREE) cf = CF_OCTREE;
+  else if (ta == MPG_GEOM_BOX && tb == MPG_GEOM_BOX) cf = CF_BOX_BOX;
+  else if (ta == MPG_GEOM_SPHERE && tb == MPG_GEOM_SPHERE) cf = CF_SPHERE_SPHERE;
+  else if (ta == MPG_GEOM_SPHERE && tb == MPG_GEOM_BOX) cf = CF_SPHERE_BOX;
+  else if (ta == MPG_GEOM_BOX && tb == MPG_GEOM_SPHERE) cf = CF_BOX_SPHERE;
+  else if (ta == MPG_GEOM_SPHERE && tb == MPG_GEOM_CAPSULE) cf = CF_SPHERE_CAPSULE;
+  else if (ta == MPG_GEOM_CAPSULE && tb == MPG_GEOM_SPHERE) cf = CF_CAPSULE_SPHERE;
+  else if (ta == MPG_GEOM_SPHERE && tb == MPG_GEOM_CYLINDER) cf = CF_SPHERE_CYLINDER;
+  else if (ta == MPG_GEOM_CYLINDER && tb == MPG_GEOM_SPHERE) cf = CF_CYLINDER_SPHERE;
+  if ((cf == CF_OCTREE && ta == tb) || (cf == CF_MESH && (ta == MPG_GEOM_OCTREE || tb == MPG_GEOM_OCTREE)))
+    return set_error(MPG_E_UNSUPPORTED, "geometry pair not supported");
+  HIP_TRY(hipSetDevice(w->device));
+  struct Guard {  // every exit path frees the buffers and the private stream
+    double *dA = nullptr, *dB = nullptr;
+    uint8_t* dh = nullptr;
+    hipStream_t s = nullptr;
+    ~Guard() {
+      if (s) hipStreamSynchronize(s);
+      hipFree(dA);
+      hipFree(dB);
+      hipFree(dh);
+      if (s) hipStreamDestroy(s);
+    }
+  } g;
+  HIP_TRY(hipStreamCreateWithFlags(&g.s, hipStreamNonBlocking));
+  HIP_TRY(hipMalloc(&g.dA, sizeof(double) * 12 * n));
+  HIP_TRY(hipMalloc(&g.dB, sizeof(double) * 12 * n));
+  HIP_TRY(hipMalloc(&g.dh, (size_t)n));
+  HIP_TRY(hipMemcpyAsync(g.dA, Ta, sizeof(double) * 12 * n, hipMemcpyHostToDevice, g.s));
+  HIP_TRY(hipMemcpyAsync(g.dB, Tb, sizeof(double) * 12 * n, hipMemcpyHostToDevice, g.s));
+  // (walk_wave_eval finds the octree / mesh argument itself)
+  hipLaunchKernelGGL(debug_pairs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.s, w->dw, geom_a, geom_b, cf,
+                     (long long)n, g.dA, g.dB, g.dh);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(hit, g.dh, (size_t)n, hipMemcpyDeviceToHost, g.s));
+  HIP_TRY(hipStreamSynchronize(g.s));
+  return MPG_OK;
+}
+
+int mpg_sample_uniform(const double* lower, const double* upper, int32_t dof, int64_t n, uint64_t seed,
+                       int64_t row_offset, double* q, int device) {
+  if (dof < 0 || dof > kSampleMaxDof) return set_error(MPG_E_INVALID, "dof out of range [0, 64]");
+  if (n < 0 || row_offset < 0 || (n > 0 && dof > 0 && (!lower || !upper || !q)))
+    return set_error(MPG_E_INVALID, "bad arguments");
+  if (n == 0 || dof == 0) return MPG_OK;
+  SampleRange r{};
+  for (int k = 0; k < dof; ++k) {
+    if (!(std::isfinite(lower[k]) && std::isfinite(upper[k]) && lower[k] <= upper[k]))
+      return set_error(MPG_E_INVALID, "sampling range must be finite with lower <= upper");
+    r.lo[k] = lower[k];
+    r.hi[k] = upper[k];
+  }
+  HIP_TRY(hipSetDevice(device));
+  double* d = nullptr;
+  HIP_TRY(hipMalloc(&d, sizeof(double) * (size_t)n * dof));
+  const long long tot = (long long)n * dof;
+  hipLaunchKernelGGL(sample_uniform_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, 0, r, (int)dof,
+                     (long long)n, seed, (long long)row_offset, d);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpy(q, d, sizeof(double) * (size_t)tot, hipMemcpyDeviceToHost);
+  hipFree(d);
+  if (e != hipSuccess) return set_error(MPG_E_HIP, std::string("mpg_sample_uniform: ") + hipGetErrorString(e));
+  return MPG_OK;
+}
+
+int mpg_collide_count(mpg_world* w, const double* lower, const double* upper, int64_t n, uint64_t seed,
+                      int64_t* counts, void* stream) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  const int dof = w->dw.dof, P = w->dw.n_pairs, W = w->dw.W;
+  if (dof > kSampleMaxDof) return set_error(MPG_E_UNSUPPORTED, "mpg_collide_count supports dof <= 64");
+  if (n < 0 || (P > 0 && !counts) || (dof > 0 && (!lower || !upper))) return set_error(MPG_E_INVALID, "bad arguments");
+  if ((size_t)P * sizeof(uint32_t) > 64 * 1024) return set_error(MPG_E_UNSUPPORTED, "mpg_collide_count supports <= 16384 pairs");
+  for (int p = 0; p < P; ++p) counts[p] = 0;
+  if (n == 0 || P == 0) return MPG_OK;
+  SampleRange r{};
+  for (int k = 0; k < dof; ++k) {
+    if (!(std::isfinite(lower[k]) && std::isfinite(upper[k]) && lower[k] <= upper[k]))
+      return set_error(MPG_E_INVALID, "sampling range must be finite with lower <= upper");
+    r.lo[k] = lower[k];
+    r.hi[k] = upper[k];
+  }
+  HIP_TRY(hipSetDevice(w->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const long long chunk = std::min<long long>(n, w->max_chunk);
+  struct Bufs {  // freed on every exit path, after the stream drained
+    double* q = nullptr;
+    uint8_t* fl = nullptr;
+    uint32_t* mk = nullptr;
+    unsigned long long* cnt = nullptr;
+    hipStream_t s = nullptr;
+    ~Bufs() {
+      hipStreamSynchronize(s);
+      hipFree(q);
+      hipFree(fl);
+      hipFree(mk);
+      hipFree(cnt);
+    }
+  } b;
+  b.s = s;
+  HIP_TRY(hipMalloc(&b.q, sizeof(double) * (size_t)chunk * std::max(dof, 1)));
+  HIP_TRY(hipMalloc(&b.fl, (size_t)chunk));
+  HIP_TRY(hipMalloc(&b.mk, sizeof(uint32_t) * (size_t)chunk * W));
+  HIP_TRY(hipMalloc(&b.cnt, sizeof(unsigned long long) * P));
+  HIP_TRY(hipMemsetAsync(b.cnt, 0, sizeof(unsigned long long) * P, s));
+  for (long long off = 0; off < n; off += chunk) {
+    const long long m = std::min(chunk, n - off);
+    if (dof > 0) {
+      const long long tot = m * dof;
+      hipLaunchKernelGGL(sample_uniform_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, r, dof, m, seed,
+                         off, b.q);
+      HIP_TRY(hipGetLastError());
+    }
+    const int rc = w->dw.n_free ? launch_collide_q(w, b.q, m, b.fl, b.mk, s)
+                                : launch_collide_overlapped<false>(w, b.q, m, b.fl, b.mk, s);
+    if (rc) return rc;
+    const unsigned grid = (unsigned)std::min<long long>(1024, (m + 255) / 256);
+    hipLaunchKernelGGL(pair_count_kernel, dim3(grid), dim3(256), sizeof(uint32_t) * P, s, b.mk, m, W, P, b.cnt);
+    HIP_TRY(hipGetLastError());
+  }
+  std::vector<unsigned long long> h(P);
+  HIP_TRY(hipMemcpyAsync(h.data(), b.cnt, sizeof(unsigned long long) * P, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int p = 0; p < P; ++p) counts[p] = (int64_t)h[p];
+  return MPG_OK;
+}
+
+int mpg_debug_sincos(const double* x, int64_t n, double* s, double* c, int device) {
+  if (n < 0 || (n > 0 && (!x || !s || !c))) return set_error(MPG_E_INVALID, "bad arguments");
+  if (n == 0) return MPG_OK;
+  HIP_TRY(hipSetDevice(device));
+  double *dx = nullptr, *ds = nullptr, *dc = nullptr;
+  HIP_TRY(hipMalloc(&dx, sizeof(double) * n));
+  HIP_TRY(hipMalloc(&ds, sizeof(double) * n));
+  HIP_TRY(hipMalloc(&dc, sizeof(double) * n));
+  HIP_TRY(hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(sincos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dx, (long long)n, ds, dc);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(s, ds, sizeof(double) * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(c, dc, sizeof(double) * n, hipMemcpyDeviceToHost));
+  hipFree(dx);
+  hipFree(ds);
+  hipFree(dc);
+  return MPG_OK;
+}

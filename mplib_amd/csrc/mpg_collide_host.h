@@ -1,0 +1,600 @@
+// mpg_collide_host.h -- host side of the latency path, the overlapped launch,
+// the host pipeline and the free-frame path (included by
+// mpg_kernels.hip in an anonymous namespace, after mpg_abi_world.h).
+#pragma once
+
+// pinned input rows (ncfg * row doubles: q rows or link poses), hit bytes
+// (n_pairs * ncfg) and joint sincos: the input capacity is tracked in doubles,
+// since the same buffers serve q rows (dof) and link-pose rows (n_links * 7)
+int ensure_small(mpg_world* w, size_t ncfg, size_t row) {
+  const size_t want_q = ncfg * std::max<size_t>(row, 1);
+  if (ncfg <= w->small_cap && want_q <= w->small_qcap) return MPG_OK;
+  ncfg = std::max(ncfg, w->small_cap);
+  const size_t qcap = std::max(want_q, w->small_qcap);
+  if (w->h_q) hipHostFree(w->h_q);
+  if (w->h_hits) hipHostFree(w->h_hits);
+  if (w->d_qs) hipFree(w->d_qs);
+  if (w->d_ssc) hipFree(w->d_ssc);
+  if (w->h_ssc) hipHostFree(w->h_ssc);
+  w->d_ssc = nullptr;
+  w->h_ssc = nullptr;
+  w->h_q = nullptr;
+  w->h_hits = nullptr;
+  w->d_qs = nullptr;
+  w->small_cap = 0;
+  w->small_qcap = 0;
+  const size_t P = (size_t)std::max(w->dw.n_pairs, 1);
+  HIP_TRY(hipHostMalloc((void**)&w->h_q, sizeof(double) * qcap, hipHostMallocMapped | hipHostMallocCoherent));
+  HIP_TRY(hipHostGetDevicePointer((void**)&w->d_qmap, w->h_q, 0));
+  HIP_TRY(hipHostMalloc((void**)&w->h_hits, P * ncfg, hipHostMallocMapped | hipHostMallocCoherent));
+  HIP_TRY(hipHostGetDevicePointer((void**)&w->d_hits, w->h_hits, 0));
+  HIP_TRY(hipMalloc(&w->d_qs, sizeof(double) * qcap));
+  HIP_TRY(hipMalloc(&w->d_ssc, sizeof(double) * 2 * ncfg * std::max<int>(w->dw.dof, 1)));
+  HIP_TRY(hipHostMalloc((void**)&w->h_ssc, sizeof(double) * 2 * ncfg * std::max<int>(w->dw.dof, 1),
+                        hipHostMallocMapped | hipHostMallocCoherent));
+  HIP_TRY(hipHostGetDevicePointer((void**)&w->d_sscmap, w->h_ssc, 0));
+  w->small_cap = ncfg;
+  w->small_qcap = qcap;
+  return MPG_OK;
+}
+
+// (re)start the latency server; it takes `done` as the last batch served
+int srv_start(mpg_world* w) {
+  if (!w->srv_h) {
+    HIP_TRY(hipHostMalloc((void**)&w->srv_h, sizeof(SrvCtl), hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(w->srv_h, 0, sizeof(SrvCtl));
+    HIP_TRY(hipHostGetDevicePointer((void**)&w->srv_d, w->srv_h, 0));
+    HIP_TRY(hipStreamCreateWithFlags(&w->srv_stream, hipStreamNonBlocking));
+    HIP_TRY(hipFuncSetAttribute((const void*)lat_server_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)w->srv_lds));
+  }
+  for (int k = 0; k < kSrvMaxG; ++k) __atomic_store_n(&w->srv_h->gone[k], 0ull, __ATOMIC_RELAXED);
+  __atomic_store_n(&w->srv_h->quit, 0ull, __ATOMIC_RELEASE);
+  ++w->srv_starts;
+  hipLaunchKernelGGL(lat_server_kernel, dim3(w->srv_g), dim3(kSrvThreads), w->srv_lds, w->srv_stream, w->dw, w->srv_d,
+                     (unsigned long long)w->srv_idle_us * 100ull, w->srv_stats ? 1 : 0);
+  HIP_TRY(hipGetLastError());
+  w->srv_running = true;
+  return MPG_OK;
+}
+
+// one batch through the resident server: rows (q, host sin/cos) into the
+// control block, seq bumped, the host spins on `done`.  The server may have
+// left (idle) before it saw the request: every 50 us the host looks for
+// workgroups that have left (`gone`) without answering -- all of them (stream
+// complete): start it again; some of them: stop the rest and start all again.
+// Workgroups that are only slow (another stream sharing the GPU) are waited
+// for.  No answer within 2 s: the server is stopped, MPG_E_HIP (the caller
+// launches instead for a while, then tries the server again).
+int collide_served(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint32_t* pair_mask) {
+  if (w->srv_running && w->srv_quitting) {  // told to quit after a missed answer
+    if (hipStreamQuery(w->srv_stream) != hipSuccess) return set_error(MPG_E_HIP, "latency server has not left yet");
+    w->srv_running = false;
+    w->srv_quitting = false;
+  }
+  if (!w->srv_running) {
+    const int rc = srv_start(w);
+    if (rc) return rc;
+  }
+  SrvCtl* C = w->srv_h;
+  const int dof = w->dw.dof, W = w->dw.W;
+  for (int64_t c = 0; c < n; ++c) {
+    double* r = C->rows + c * 3 * dof;
+    std::memcpy(r, q + c * dof, sizeof(double) * (size_t)dof);
+    for (const int src : w->h_rev_src) mpg_sincos(q[c * dof + src], &r[dof + 2 * src], &r[dof + 2 * src + 1]);
+  }
+  const unsigned long long seq = (++w->srv_seq << 8) | (unsigned long long)n;
+  __atomic_store_n(&C->seq, seq, __ATOMIC_RELEASE);
+  const auto t0 = std::chrono::steady_clock::now();
+  long long next_us = 50;
+  bool forced = false;
+  auto all_done = [&] {
+    for (int k = 0; k < w->srv_g; ++k)
+      if (__atomic_load_n(&C->done[k], __ATOMIC_ACQUIRE) != seq) return false;
+    return true;
+  };
+  while (!all_done()) {
+    __builtin_ia32_pause();
+    const long long us =
+        std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+    if (us < next_us) continue;
+    next_us = us + 50;
+    hipError_t e = hipStreamQuery(w->srv_stream);
+    bool partial = false;  // a workgroup left before this request, others are still resident
+    for (int k = 0; k < w->srv_g && e == hipErrorNotReady; ++k)
+      partial |= __atomic_load_n(&C->gone[k], __ATOMIC_ACQUIRE) != 0ull &&
+                 __atomic_load_n(&C->done[k], __ATOMIC_ACQUIRE) != seq;
+    if (partial && !forced) {
+      // stop the ones still polling and start all again (once per request);
+      // they see quit within one poll, so this wait is short
+      __atomic_store_n(&C->quit, 1ull, __ATOMIC_RELEASE);
+      e = hipStreamSynchronize(w->srv_stream);
+      forced = true;
+    }
+    if (e == hipSuccess) {  // it left before this request: start it again
+      w->srv_running = false;
+      const int rc = srv_start(w);
+      if (rc) return rc;
+    } else if (e != hipErrorNotReady || us > 2000000) {
+      __atomic_store_n(&C->quit, 1ull, __ATOMIC_RELEASE);
+      w->srv_quitting = true;  // not waited for here: the next try checks that it has left
+      return set_error(MPG_E_HIP, "latency server did not answer");
+    }
+  }
+  ++w->srv_served;
+  if (w->prof) {  // a served batch counts as one narrow-stage "launch" of its post -> done time
+    std::lock_guard<std::mutex> lk(w->prof_mu);
+    w->prof_ms[MPG_STAGE_NARROW] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    w->prof_n[MPG_STAGE_NARROW] += 1;
+    w->prof_cfg += n;
+  }
+  if (w->srv_stats) {  // MPG_STATS: phase sums (rows, fk, spheres, narrow, publish), us
+    w->srv_stat[5] += 1.0;
+    for (int k = 0; k < 5; ++k) w->srv_stat[k] += (double)(C->phase[k + 1] - C->phase[k]) / 100.0;
+    w->srv_stat[6] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+  }
+  for (int64_t c = 0; c < n; ++c) {
+    uint32_t any = 0;
+    for (int k = 0; k < W; ++k) {
+      uint32_t v = 0;
+      for (int gg = 0; gg < w->srv_g; ++gg) v |= __atomic_load_n(&C->out[gg][c * W + k], __ATOMIC_RELAXED);
+      any |= v;
+      if (pair_mask) pair_mask[c * W + k] = v;
+    }
+    flags[c] = any ? 1 : 0;
+  }
+  return MPG_OK;
+}
+
+// one round trip: input to the device, one small_kernel launch writing hit
+// bytes straight into host memory, one synchronisation; the host folds the
+// hits into flags / pair masks
+// dev_in: the rows are already on the device (link poses assembled there for
+// a world with free frames); q is then not read
+template <bool FROM_POSES>
+int collide_small(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint32_t* pair_mask, hipStream_t s,
+                  const double* dev_in = nullptr) {
+  if (!FROM_POSES && w->srv_mode && w->srv_ok && n <= w->srv_max_n && !w->dw.dbg(3) && !w->dw.dbg(7) &&
+      (!w->srv_broken || std::chrono::steady_clock::now() >= w->srv_retry_at)) {
+    if (collide_served(w, q, n, flags, pair_mask) == MPG_OK) {
+      w->srv_broken = false;
+      return MPG_OK;
+    }
+    // the server could not be started or did not answer: launches for the
+    // next second, then the server is tried again
+    std::fprintf(stderr, "mplib_amd: latency server unavailable (%s); one launch per batch for 1 s\n",
+                 g_last_error.c_str());
+    w->srv_broken = true;
+    ++w->srv_fallbacks;
+    w->srv_retry_at = std::chrono::steady_clock::now() + std::chrono::seconds(1);
+    (void)hipGetLastError();
+  }
+  const size_t row = FROM_POSES ? (size_t)w->dw.n_links * 7 : (size_t)w->dw.dof;
+  const size_t cap = std::max<size_t>((size_t)n, std::min<size_t>((size_t)w->small_max, 256));
+  int rc = ensure_small(w, cap, row);
+  if (rc) return rc;
+  const int P = w->dw.n_pairs, W = w->dw.W;
+  std::memset(flags, 0, (size_t)n);
+  if (pair_mask) std::memset(pair_mask, 0, sizeof(uint32_t) * (size_t)n * W);
+  if (P == 0) return MPG_OK;
+  const double* qin = dev_in ? dev_in : w->small_zero_copy ? w->d_qmap : w->d_qs;
+  if (row && !dev_in) {  // zero-copy: the kernel reads the pinned rows directly, no copy launch
+    std::memcpy(w->h_q, q, sizeof(double) * (size_t)n * row);
+    if (!w->small_zero_copy)
+      HIP_TRY(hipMemcpyAsync(w->d_qs, w->h_q, sizeof(double) * (size_t)n * row, hipMemcpyHostToDevice, s));
+  }
+  const int n_tiles = (int)((n + 63) / 64);
+  const long long waves = (long long)P * n_tiles;
+  StageTimer t_small(w, s, MPG_STAGE_NARROW);
+  if (w->prof) w->prof_cfg += n;
+  // the smallest batches: joint sin/cos on the host (mpg_sincos, the device's
+  // own restatement of glibc's, bit for bit) into pinned mapped memory, one
+  // launch without the sin/cos work; up to small_inline_sc states: one launch
+  // with sin/cos inline; larger: a sin/cos launch first
+  const bool host_sc = !FROM_POSES && w->dw.dof > 0 && n <= w->small_host_sc;
+  const bool inline_sc = !host_sc && (FROM_POSES || (n <= w->small_inline_sc && w->dw.dof <= kLatScDof));
+  double* sc_src = w->d_ssc;
+  if (host_sc) {
+    const int dof = w->dw.dof;
+    for (int64_t c = 0; c < n; ++c)
+      for (const int src : w->h_rev_src) {
+        double sv, cv;
+        mpg_sincos(q[c * dof + src], &sv, &cv);
+        w->h_ssc[(c * dof + src) * 2] = sv;
+        w->h_ssc[(c * dof + src) * 2 + 1] = cv;
+      }
+    sc_src = w->d_sscmap;
+  }
+  if (!inline_sc && !host_sc && w->dw.dof > 0) {
+    const long long nt = n * w->dw.dof;
+    hipLaunchKernelGGL(small_sincos_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, w->dw, qin,
+                       (long long)n, w->d_ssc);
+    HIP_TRY(hipGetLastError());
+  }
+  const dim3 grid((unsigned)((waves + 3) / 4));
+  const bool host_staged = host_sc && w->dw.dof <= kLatScDof && w->dw.lat_rec_ok;
+  // the fewest states: their rows travel in the kernel arguments
+  const bool by_args = host_staged && n * 3 * (int64_t)w->dw.dof <= kLatIn && w->small_args;
+  LatIn args{};
+  if (by_args) {
+    const int dof = w->dw.dof;
+    for (int64_t c = 0; c < n; ++c) {
+      double* r = args.d + c * 3 * dof;
+      std::memcpy(r, q + c * dof, sizeof(double) * (size_t)dof);
+      std::memcpy(r + dof, w->h_ssc + c * 2 * dof, sizeof(double) * 2 * (size_t)dof);
+    }
+  }
+  auto launch = [&](auto kern) {  // every class instance reads the same sin/cos source
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, w->dw, qin, (long long)n, n_tiles, w->d_hits, sc_src, args);
+    return hipGetLastError();
+  };
+  auto pick = [&](auto k0, auto k1, auto k2, auto k3) {
+    return inline_sc ? launch(k1) : by_args ? launch(k3) : host_staged ? launch(k2) : launch(k0);
+  };
+  HIP_TRY(pick(small_kernel<FROM_POSES, CLS_CLOSED, 0>, small_kernel<FROM_POSES, CLS_CLOSED, 1>,
+               small_kernel<FROM_POSES, CLS_CLOSED, 2>, small_kernel<FROM_POSES, CLS_CLOSED, 3>));
+  if (w->any_octree)
+    HIP_TRY(pick(small_kernel<FROM_POSES, CLS_OCTREE, 0>, small_kernel<FROM_POSES, CLS_OCTREE, 1>,
+                 small_kernel<FROM_POSES, CLS_OCTREE, 2>, small_kernel<FROM_POSES, CLS_OCTREE, 3>));
+  if (w->any_mesh)
+    HIP_TRY(pick(small_kernel<FROM_POSES, CLS_MESH, 0>, small_kernel<FROM_POSES, CLS_MESH, 1>,
+                 small_kernel<FROM_POSES, CLS_MESH, 2>, small_kernel<FROM_POSES, CLS_MESH, 3>));
+  if (w->any_gjk)
+    HIP_TRY(pick(small_kernel<FROM_POSES, CLS_GJK, 0>, small_kernel<FROM_POSES, CLS_GJK, 1>,
+                 small_kernel<FROM_POSES, CLS_GJK, 2>, small_kernel<FROM_POSES, CLS_GJK, 3>));
+  t_small.stop();
+  HIP_TRY(hipStreamSynchronize(s));
+  const uint8_t* h = w->h_hits;
+  for (int p = 0; p < P; ++p) {
+    const uint8_t* hp = h + (size_t)p * n;
+    const uint32_t bit = 1u << (p & 31);
+    for (int64_t c = 0; c < n; ++c)
+      if (hp[c]) {
+        flags[c] = 1;
+        if (pair_mask) pair_mask[(size_t)c * W + (p >> 5)] |= bit;
+      }
+  }
+  return MPG_OK;
+}
+
+// stream-ordered for the caller: the side stream waits for everything queued
+// on `s` before the call, and `s` waits for the side stream's half
+template <bool FROM_POSES>
+int launch_collide_overlapped(mpg_world* w, const double* in, long long n, uint8_t* flags, uint32_t* masks,
+                              hipStream_t s) {
+  StreamPin pin(w, s);
+  // one chunk or less runs on the caller's stream alone: its two halves'
+  // cull and narrow kernels each fill the chip and are latency-bound, so on a
+  // second stream they only time-share the CUs (cfg3, 2^20: single stream
+  // +0.7-1.3 %; cfg4, 4 chunks: overlapped +16 %, profiles/r05a/overlap_ab.txt)
+  if (w->overlap_min <= 0 || n < w->overlap_min || n <= w->max_chunk)
+    return launch_collide<FROM_POSES>(w, in, n, flags, masks, s);
+  // one side stream and fork/join event pair per caller stream: callers on
+  // different streams (one host thread each, include/mpgpu.h) never record
+  // into or wait on each other's events, and each side stream has its own
+  // workspace (get_workspace keys by stream)
+  mpg_world::Side sd;
+  {
+    std::lock_guard<std::mutex> lk(w->ws_mu);
+    auto it = w->sides.find(s);
+    if (it == w->sides.end()) {
+      if (w->ws.find(s) == w->ws.end()) evict_streams_locked(w);
+      mpg_world::Side n{};
+      HIP_TRY(hipStreamCreateWithFlags(&n.side, hipStreamNonBlocking));
+      HIP_TRY(hipEventCreateWithFlags(&n.fork, hipEventDisableTiming));
+      HIP_TRY(hipEventCreateWithFlags(&n.join, hipEventDisableTiming));
+      it = w->sides.emplace(s, n).first;
+    }
+    it->second.last = ++w->ws_tick;
+    sd = it->second;
+  }
+  const size_t row = FROM_POSES ? (size_t)w->dw.n_links * 7 : (size_t)w->dw.dof;
+  // parts alternate between the caller's stream and the side stream
+  const int parts = std::max(2, w->overlap_parts);
+  const long long step = ((n + parts - 1) / parts + 63) / 64 * 64;
+  HIP_TRY(hipEventRecord(sd.fork, s));
+  HIP_TRY(hipStreamWaitEvent(sd.side, sd.fork, 0));
+  int k = 0;
+  for (long long off = 0; off < n; off += step, ++k) {
+    const long long m = std::min(step, n - off);
+    const int rc = launch_collide<FROM_POSES>(w, in + (size_t)off * row, m, flags + off,
+                                              masks ? masks + (size_t)off * w->dw.W : nullptr, (k & 1) ? sd.side : s);
+    if (rc) return rc;
+  }
+  HIP_TRY(hipEventRecord(sd.join, sd.side));
+  HIP_TRY(hipStreamWaitEvent(s, sd.join, 0));
+  return MPG_OK;
+}
+
+// Host buffers above the latency path's sizes (mpg_hostpipe.h): per chunk,
+// the rows are copied from the caller's (pageable) buffer on the ring's copy
+// stream by the feeder thread; the compute stream waits for them, runs the
+// collide pipeline into the slot's device outputs, packs the colliding
+// configurations' mask rows straight into pinned host memory and copies the
+// flags back; the issuing thread unpacks a finished chunk into the caller's
+// buffers while the next chunks are in flight.  PCIe carries the rows in
+// (8 * row B per configuration) and 1 + 4W B per colliding configuration
+// back instead of 1 + 4W B per configuration.  Caller holds host_mu.
+template <bool FROM_POSES>
+struct HostPipeOps {
+  mpg_world* w;
+  const double* q;
+  uint8_t* flags;
+  uint32_t* pair_mask;
+  hipStream_t s;
+  size_t row;
+  // the first error text of the feeder / issuer threads (g_last_error is per
+  // thread); finish() runs on the caller's thread and sets g_last_error itself
+  std::mutex err_mu;
+  std::string thread_err;
+  bool fin_failed = false;
+
+  int thread_fail(int rc, const std::string& msg) {
+    std::lock_guard<std::mutex> lk(err_mu);
+    if (thread_err.empty()) thread_err = msg;
+    return rc;
+  }
+  int bind_thread() {
+    if (hipSetDevice(w->device) != hipSuccess) return thread_fail(MPG_E_HIP, "hipSetDevice failed in a pipeline thread");
+    return MPG_OK;
+  }
+  double t_in = 0, t_issue = 0, t_wait = 0, t_unpack = 0;
+  static double us_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+  }
+  int h2d(int64_t, int j, int64_t start, int64_t m) {
+    auto& R = w->ring;
+    const auto t0 = std::chrono::steady_clock::now();
+    hipError_t e = hipSuccess;
+    if (row) e = hipMemcpyAsync(R.d_in[j], q + (size_t)start * row, sizeof(double) * (size_t)m * row,
+                                hipMemcpyHostToDevice, R.h2d);
+    if (e == hipSuccess) e = hipEventRecord(R.e_in[j], R.h2d);
+    t_in += us_since(t0);
+    if (e != hipSuccess) return thread_fail(MPG_E_HIP, std::string("host pipeline input copy failed: ") + hipGetErrorString(e));
+    return MPG_OK;
+  }
+  int issue(int64_t k, int j, int64_t start, int64_t m) {
+    const int rc = issue_chunk(k, j, start, m);
+    return rc ? thread_fail(rc, g_last_error) : MPG_OK;  // g_last_error of this (issuer) thread
+  }
+  int issue_chunk(int64_t k, int j, int64_t, int64_t m) {
+    auto& R = w->ring;
+    const auto t0 = std::chrono::steady_clock::now();
+    const hipStream_t cs = (w->ring_streams > 1 && (k & 1)) ? R.side : s;
+    HIP_TRY(hipStreamWaitEvent(cs, R.e_in[j], 0));
+    const int rc = launch_collide<FROM_POSES>(w, R.d_in[j], m, R.d_fl[j], R.d_mk[j], cs);
+    if (rc) return rc;
+    // results straight into pinned host memory: the flags, and with masks the
+    // block counts and the packed rows (no copy launches)
+    const int Wp = pair_mask ? w->dw.W : 0;
+    const unsigned nb = (unsigned)((m + kPackCfg - 1) / kPackCfg);
+    if (Wp > 0) {
+      hipLaunchKernelGGL(flag_count_kernel, dim3(nb), dim3(256), 0, cs, R.d_fl[j], (long long)m, R.d_bcnt[j],
+                         R.h_bcnt_d[j]);
+      HIP_TRY(hipGetLastError());
+    }
+    const size_t lds = sizeof(uint32_t) * 256 * (size_t)Wp;
+    if (lds <= 64 * 1024)
+      hipLaunchKernelGGL(mask_pack_kernel<true>, dim3(nb), dim3(256), lds, cs, R.d_fl[j], R.d_mk[j], (long long)m, Wp,
+                         R.d_bcnt[j], R.h_mk_d[j], R.h_fl_d[j]);
+    else
+      hipLaunchKernelGGL(mask_pack_kernel<false>, dim3(nb), dim3(256), 0, cs, R.d_fl[j], R.d_mk[j], (long long)m, Wp,
+                         R.d_bcnt[j], R.h_mk_d[j], R.h_fl_d[j]);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(R.e_done[j], cs));
+    t_issue += us_since(t0);
+    return MPG_OK;
+  }
+  int finish(int64_t, int j, int64_t start, int64_t m) {
+    auto& R = w->ring;
+    const auto t0 = std::chrono::steady_clock::now();
+    const hipError_t e = hipEventSynchronize(R.e_done[j]);
+    if (e != hipSuccess) {
+      fin_failed = true;
+      return set_error(MPG_E_HIP, std::string("host pipeline: ") + hipGetErrorString(e));
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    t_wait += std::chrono::duration<double, std::micro>(t1 - t0).count();
+    mpg_hostpipe::unpack_chunk(w->pool.get(), R.h_fl[j], R.h_mk[j], R.h_bcnt[j], kPackCfg, m, w->dw.W, flags + start,
+                               pair_mask && w->dw.W > 0 ? pair_mask + (size_t)start * w->dw.W : nullptr);
+    t_unpack += us_since(t1);
+    return MPG_OK;
+  }
+  void drain() {
+    hipStreamSynchronize(w->ring.h2d);
+    hipStreamSynchronize(w->ring.side);
+    hipStreamSynchronize(s);
+  }
+};
+
+template <bool FROM_POSES>
+int collide_host_pipelined(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint32_t* pair_mask,
+                           hipStream_t s) {
+  const mpg_hostpipe::Plan p =
+      mpg_hostpipe::plan(n, w->ring_chunk, 1 << 15, mpg_world::kRing, w->ring_head, w->ring_tail);
+  const size_t row = FROM_POSES ? (size_t)w->dw.n_links * 7 : (size_t)w->dw.dof;
+  int rc = ensure_ring(w, (size_t)p.chunk, row);
+  if (rc) return rc;
+  if (!w->pool && w->host_threads > 1 && p.chunk >= 2 * kPackCfg)
+    w->pool.reset(new mpg_hostpipe::Pool(w->host_threads - 1));
+  HostPipeOps<FROM_POSES> ops{w, q, flags, pair_mask, s, row};
+  const auto t0 = std::chrono::steady_clock::now();
+  rc = mpg_hostpipe::run(p, n, ops);
+  if (w->srv_stats) {
+    const double v[6] = {1.0, ops.t_in, ops.t_issue, ops.t_wait, ops.t_unpack, HostPipeOps<FROM_POSES>::us_since(t0)};
+    for (int k = 0; k < 6; ++k) w->hp_stat[k] += v[k];
+  }
+  if (rc && !ops.fin_failed) return set_error(rc, ops.thread_err);
+  return rc;
+}
+
+int collide_free(mpg_world* w, const double* q, const double* free_pose, int64_t free_rows, int64_t n, uint8_t* flags,
+                 uint32_t* pair_mask, int mem, void* stream);
+int check_free_poses(const double* p7, size_t count);
+
+template <bool FROM_POSES>
+int collide_common(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint32_t* pair_mask, int mem,
+                   void* stream) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  // joint-value rows of a world with free frames: at its current poses
+  if (!FROM_POSES && w->dw.n_free) return collide_free(w, q, nullptr, 0, n, flags, pair_mask, mem, stream);
+  if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
+  const size_t row = FROM_POSES ? (size_t)w->dw.n_links * 7 : (size_t)w->dw.dof;
+  // a world without inputs (dof 0) may pass q = NULL
+  if (n > 0 && ((!q && row > 0) || !flags)) return set_error(MPG_E_INVALID, "input/flags is NULL");
+  // host-memory link-pose rows: the free frames' columns are checked as every host-memory free pose is
+  if (FROM_POSES && mem == MPG_MEM_HOST && w->dw.n_free)
+    for (int64_t i = 0; i < n; ++i) {
+      const int rc = check_free_poses(q + ((size_t)i * w->dw.n_links + (w->dw.n_links - w->dw.n_free)) * 7,
+                                      (size_t)w->dw.n_free);
+      if (rc) return rc;
+    }
+  HIP_TRY(hipSetDevice(w->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (mem == MPG_MEM_DEVICE) return launch_collide_overlapped<FROM_POSES>(w, q, n, flags, pair_mask, s);
+  if (mem != MPG_MEM_HOST) return set_error(MPG_E_INVALID, "bad mem kind");
+  std::lock_guard<std::mutex> lk(w->host_mu);
+  if (!s && w->own_stream) s = w->own_stream;
+  if (n == 0) return MPG_OK;
+  if (n <= w->small_max) return collide_small<FROM_POSES>(w, q, n, flags, pair_mask, s);
+  return collide_host_pipelined<FROM_POSES>(w, q, n, flags, pair_mask, s);
+}
+
+// ---------------------------------------------------------------------------
+// Worlds with free frames.  Every pair evaluation of such a world runs on
+// link-pose rows: fk_free_kernel writes the kinematic links' poses from q and
+// copies the free frames' poses next to them (per row, shared, or the world's
+// current ones), then the link-pose instances of the cull / narrow / small
+// kernels evaluate the rows.  Device calls keep the rows in the caller
+// stream's workspace and read the caller's pose array directly: no state in
+// the world, no synchronisation.  Worlds without free frames never come here.
+// ---------------------------------------------------------------------------
+constexpr long long kFreeChunk = 1 << 18;  // rows per pass: n_links * 56 B each
+
+// device buffers; free_pose NULL = current poses; free_stride in doubles
+int launch_collide_free(mpg_world* w, const double* q, const double* free_pose, long long free_stride, long long n,
+                        uint8_t* flags, uint32_t* masks, hipStream_t s, const ContactOut* co = nullptr) {
+  if (n == 0) return MPG_OK;
+  StreamPin pin(w, s);
+  const long long chunk = std::min<long long>(n, std::min<long long>(kFreeChunk, w->max_chunk));
+  mpg_world::Workspace* ws = nullptr;
+  int rc = get_workspace(w, s, chunk, &ws);
+  if (rc) return rc;
+  const size_t lrow = (size_t)w->dw.n_links * 7;
+  if (ws->links_cap < chunk) {  // this stream's queued work may still read the old rows
+    if (ws->links) {
+      HIP_TRY(hipStreamSynchronize(s));
+      HIP_TRY(hipFree(ws->links));
+    }
+    ws->links = nullptr;
+    ws->links_cap = 0;
+    HIP_TRY(hipMalloc(&ws->links, sizeof(double) * lrow * (size_t)chunk));
+    ws->links_cap = chunk;
+  }
+  const size_t P = (size_t)w->dw.n_pairs;
+  for (long long off = 0; off < n; off += chunk) {
+    const long long m = std::min(chunk, n - off);
+    hipLaunchKernelGGL(fk_free_kernel, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, w->dw,
+                       q ? q + (size_t)off * w->dw.dof : nullptr, m, ws->links,
+                       free_pose ? free_pose + (size_t)off * free_stride : nullptr, free_stride);
+    HIP_TRY(hipGetLastError());
+    ContactOut sub{};
+    if (co) sub = ContactOut{co->depth + off * P, co->normal + off * P * 3, co->pos + off * P * 3};
+    rc = launch_collide<true>(w, ws->links, m, flags + off, masks ? masks + (size_t)off * w->dw.W : nullptr, s,
+                              co ? &sub : nullptr);
+    if (rc) return rc;
+  }
+  return MPG_OK;
+}
+
+// joint-value rows on the device, evaluated at the world's current free poses
+int launch_collide_q(mpg_world* w, const double* q, long long n, uint8_t* flags, uint32_t* masks, hipStream_t s,
+                     const ContactOut* co = nullptr) {
+  if (w->dw.n_free) return launch_collide_free(w, q, nullptr, 0, n, flags, masks, s, co);
+  return launch_collide<false>(w, q, n, flags, masks, s, co);
+}
+
+// finite values and unit quaternions (kFreeQuatTol) of host-memory free poses
+int check_free_poses(const double* p7, size_t count) {
+  for (size_t k = 0; k < count; ++k) {
+    const double* p = p7 + 7 * k;
+    if (!finite_all(p, 7)) return set_error(MPG_E_INVALID, "non-finite free pose");
+    const double nq = std::sqrt(p[3] * p[3] + p[4] * p[4] + p[5] * p[5] + p[6] * p[6]);
+    if (!(std::fabs(nq - 1.0) <= kFreeQuatTol))
+      return set_error(MPG_E_INVALID, "free pose quaternion is not of unit norm (within 1e-6)");
+  }
+  return MPG_OK;
+}
+
+// host buffers: rows staged to the device in passes of kFreeChunk; batches up
+// to the latency path's size take its one-launch kernel on the assembled rows
+int collide_free_host(mpg_world* w, const double* q, const double* free_pose, long long free_rows, int64_t n,
+                      uint8_t* flags, uint32_t* pair_mask, hipStream_t s) {
+  auto& F = w->free_stage;
+  auto grow = [&](void** p, size_t& cap, size_t want) -> int {
+    if (cap >= want) return MPG_OK;
+    if (*p) HIP_TRY(hipFree(*p));
+    *p = nullptr;
+    cap = 0;
+    HIP_TRY(hipMalloc(p, want));
+    cap = want;
+    return MPG_OK;
+  };
+  const size_t dof = (size_t)w->dw.dof, frow = (size_t)w->dw.n_free * 7, lrow = (size_t)w->dw.n_links * 7;
+  const size_t W = (size_t)w->dw.W;
+  const long long chunk = std::min<long long>(n, kFreeChunk);
+  int rc;
+  if ((rc = grow((void**)&F.q, F.q_cap, sizeof(double) * std::max<size_t>(1, dof * chunk)))) return rc;
+  if ((rc = grow((void**)&F.fp, F.fp_cap, sizeof(double) * frow * (free_rows > 1 ? chunk : 1)))) return rc;
+  if ((rc = grow((void**)&F.links, F.links_cap, sizeof(double) * lrow * chunk))) return rc;
+  // the latency kernel reads all n rows at once: only a batch that one pass
+  // assembles (small_batch_max may be set above kFreeChunk)
+  const bool small = n <= w->small_max && n <= chunk;
+  if (!small) {
+    if ((rc = grow((void**)&F.fl, F.fl_cap, (size_t)chunk))) return rc;
+    if ((rc = grow((void**)&F.mk, F.mk_cap, sizeof(uint32_t) * W * chunk))) return rc;
+  }
+  if (free_pose && free_rows == 1)
+    HIP_TRY(hipMemcpyAsync(F.fp, free_pose, sizeof(double) * frow, hipMemcpyHostToDevice, s));
+  for (long long off = 0; off < n; off += chunk) {
+    const long long m = std::min<long long>(chunk, n - off);
+    if (dof) HIP_TRY(hipMemcpyAsync(F.q, q + (size_t)off * dof, sizeof(double) * dof * m, hipMemcpyHostToDevice, s));
+    if (free_pose && free_rows > 1)
+      HIP_TRY(hipMemcpyAsync(F.fp, free_pose + (size_t)off * frow, sizeof(double) * frow * m, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(fk_free_kernel, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, w->dw, F.q, m, F.links,
+                       free_pose ? F.fp : nullptr, free_rows > 1 ? (long long)frow : 0ll);
+    HIP_TRY(hipGetLastError());
+    if (small) return collide_small<true>(w, nullptr, n, flags, pair_mask, s, F.links);
+    rc = launch_collide<true>(w, F.links, m, F.fl, pair_mask ? F.mk : nullptr, s);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(flags + off, F.fl, (size_t)m, hipMemcpyDeviceToHost, s));
+    if (pair_mask)
+      HIP_TRY(hipMemcpyAsync(pair_mask + (size_t)off * W, F.mk, sizeof(uint32_t) * W * m, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  return MPG_OK;
+}
+
+int collide_free(mpg_world* w, const double* q, const double* free_pose, int64_t free_rows, int64_t n, uint8_t* flags,
+                 uint32_t* pair_mask, int mem, void* stream) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
+  if (n > 0 && ((!q && w->dw.dof > 0) || !flags)) return set_error(MPG_E_INVALID, "input/flags is NULL");
+  if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
+  if (free_pose && free_rows != 1 && free_rows != n)
+    return set_error(MPG_E_INVALID, "free_rows must be 1 (shared by the batch) or n (one pose set per configuration)");
+  if (free_pose && w->dw.n_free == 0) return set_error(MPG_E_INVALID, "the world has no free frames");
+  if (w->dw.n_free == 0) return collide_common<false>(w, q, n, flags, pair_mask, mem, stream);
+  HIP_TRY(hipSetDevice(w->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const long long fstride = free_rows > 1 ? (long long)w->dw.n_free * 7 : 0ll;
+  if (mem == MPG_MEM_DEVICE) return launch_collide_free(w, q, free_pose, fstride, n, flags, pair_mask, s);
+  if (free_pose) {
+    const int rc = check_free_poses(free_pose, (size_t)free_rows * w->dw.n_free);
+    if (rc) return rc;
+  }
+  std::lock_guard<std::mutex> lk(w->host_mu);
+  if (!s && w->own_stream) s = w->own_stream;
+  if (n == 0) return MPG_OK;
+  return collide_free_host(w, q, free_pose, free_rows, n, flags, pair_mask, s);
+}

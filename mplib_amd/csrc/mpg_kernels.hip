@@ -6695,3450 +6695,29 @@ __global__ __launch_bounds__(256) void mask_pack_kernel(const uint8_t* __restric
 // ---------------------------------------------------------------------------
 // host side: snapshot build + C ABI
 // ---------------------------------------------------------------------------
-struct mpg_world {
-  int device = 0;
-  DevWorld dw{};
-  int n_geoms = 0;
-  std::vector<int> geom_type_h;  // host copy of the geometry kinds (diagnostics)
-  void* blob = nullptr;
-  size_t blob_bytes = 0;
-  uint64_t snapshot_hash = 0;  // FNV-1a of the snapshot blob (mpg_collide_batch_multi's same-scene check)
-  hipEvent_t gather_ev = nullptr;  // mpg_collide_batch_multi_device: this shard's gather copies are queued
-  int block = 128;
-  size_t lds_bytes = 0;
-  // staging for MPG_MEM_HOST
-  std::mutex host_mu;
-  double* d_q = nullptr;
-  uint8_t* d_flags = nullptr;
-  uint32_t* d_masks = nullptr;
-  double* d_out = nullptr;
-  size_t cap_cfg = 0;
-  size_t cap_out = 0;
-  // phase A/B workspace, one per stream so concurrent streams never share it
-  struct Workspace {
-    uint32_t* surv = nullptr;       // [W * cap] survivor bits, word-major
-    uint32_t* cnt = nullptr;        // [n_pairs * n_tiles] tile counts -> offsets
-    uint32_t* seg_len = nullptr;    // [n_pairs]
-    uint32_t* seg_start = nullptr;  // [n_pairs]
-    uint32_t* prefix = nullptr;     // [n_pairs + 2] task prefix + task counter
-    uint32_t* cand = nullptr;       // [n_pairs * cap] worst case
-    float* rq = nullptr;            // [n_moving * 4 * cap] phase-A rotations (quaternions) for the SAT stage
-    double* sc = nullptr;           // [cap * dof * 2] exact joint (sin, cos) for phase B
-    double* links = nullptr;        // [links_cap * n_links * 7] link-pose rows (worlds with free frames)
-    long long links_cap = 0;
-    long long cap = 0;
-    uint64_t last = 0;              // LRU tick (get_workspace)
-  };
-  std::mutex ws_mu;
-  std::map<hipStream_t, Workspace> ws;
-  // free frames: the current poses (host copy, device buffer DevWorld::free_cur
-  // points to) and the grow-only staging of host-buffer calls (host_mu)
-  std::vector<double> free_host;
-  double* free_dev = nullptr;
-  struct FreeStage {
-    double *q = nullptr, *fp = nullptr, *links = nullptr;
-    uint8_t* fl = nullptr;
-    uint32_t* mk = nullptr;
-    size_t q_cap = 0, fp_cap = 0, links_cap = 0, fl_cap = 0, mk_cap = 0;
-  } free_stage;
-  // optional per-stage timing (mpg_profile_enable)
-  struct Mark {
-    int stage;
-    hipEvent_t a, b;
-  };
-  // batched motion validation buffers (grow-only)
-  struct Motion {
-    double* edges = nullptr;
-    size_t edges_cap = 0;
-    int32_t* segs = nullptr;
-    size_t segs_cap = 0;
-    long long* offs = nullptr;
-    size_t offs_cap = 0;
-    int32_t* out = nullptr;  // staging: first_invalid[n] then valid[n] bytes
-    size_t out_cap = 0;
-    double* states = nullptr;
-    size_t states_cap = 0;
-    uint8_t* flags = nullptr;
-    size_t flags_cap = 0;
-    hipEvent_t last = nullptr;  // the previous call's work (scratch order across streams)
-  } motion;
-  std::mutex motion_mu;
-  bool has_closed_form = false;  // a non-allowed pair uses an FCL closed form
-  bool has_octree = false;       // a non-allowed pair involves an octree
-  bool octree_first = false;     // a non-allowed pair has its octree as o1 (C ABI only; pymp puts it second)
-  bool any_closed_form = false;  // some pair (allowed or not) does, octrees aside
-  bool any_octree = false;       // some pair involves an octree
-  bool has_mesh = false;         // a non-allowed pair involves a BVH mesh
-  bool any_mesh = false;         // some pair involves a BVH mesh
-  bool any_gjk = false;          // GST_INDEP world: some pair runs FCL's own GJK (CF_GJK)
-  bool has_octree2 = false;      // a non-allowed pair of two OcTrees
-  // batched distance buffers (grow-only)
-  struct Dist {
-    double* poses = nullptr;
-    size_t poses_cap = 0;
-    double* save64 = nullptr;
-    size_t save_cap = 0;
-    double* q = nullptr;
-    size_t q_cap = 0;
-    char* out = nullptr;
-    size_t out_cap = 0;
-    double* pts = nullptr;  // device-buffer calls: points nobody asked for
-    size_t pts_cap = 0;
-    double* links = nullptr;  // worlds with free frames: link-pose rows
-    size_t links_cap = 0;
-    hipEvent_t last = nullptr;  // the previous call's work (scratch order across streams)
-    ccdx::BigPolytope* big = nullptr;  // kBigPool EPA polytopes (distance_redo_kernel)
-    size_t big_cap = 0;
-    unsigned* list = nullptr;  // overflowed configurations: [count, ids...]
-    size_t list_cap = 0;
-  } dist;
-  // host-buffer contact calls: grow-only device staging (guarded by host_mu)
-  struct ContactStage {
-    double *in = nullptr, *out = nullptr;
-    uint8_t* fl = nullptr;
-    uint32_t* mk = nullptr;
-    size_t in_cap = 0, out_cap = 0, fl_cap = 0, mk_cap = 0;
-  } contact;
-  std::mutex dist_mu;
-  std::mutex prof_mu;
-  bool prof = false;
-  std::vector<Mark> marks;
-  std::vector<hipEvent_t> ev_pool;
-  double prof_ms[MPG_NUM_STAGES] = {0, 0, 0};
-  int64_t prof_n[MPG_NUM_STAGES] = {0, 0, 0};
-  int64_t prof_cfg = 0;                       // configurations launched while profiling
-  unsigned long long* prof_units = nullptr;   // device counter: narrow candidates
-  long long max_chunk = 1 << 20;
-  int narrow_blocks = 1024;
-  // large batches: two halves, the second on an internal stream, so one
-  // half's latency-bound bucketing overlaps the other's compute
-  long long overlap_min = 1 << 18;  // 0 disables (env MPG_OVERLAP_MIN)
-  int overlap_parts = 2;             // env MPG_OVERLAP_PARTS
-  // large batches: half of the parts on a side stream (per caller stream)
-  struct Side {
-    hipStream_t side;
-    hipEvent_t fork, join;
-    uint64_t last;
-  };
-  std::map<hipStream_t, Side> sides;  // guarded by ws_mu
-  // per-stream state (workspaces, side streams) is kept for at most
-  // kMaxStreamState caller streams, least recently used evicted first;
-  // mpg_release_stream drops one explicitly
-  static constexpr size_t kMaxStreamState = 32;
-  uint64_t ws_tick = 0;
-  // caller streams with a call in progress (StreamPin): never evicted, so no
-  // thread frees a workspace or side stream another thread is using
-  std::map<hipStream_t, int> busy;  // guarded by ws_mu
-  // small-batch latency path (host buffers, n <= small_max): pinned input
-  // staging + host-mapped hit bytes written by small_kernel
-  long long small_max = 1024;
-  double* h_q = nullptr;       // pinned, [small cap * row]
-  uint8_t* h_hits = nullptr;   // pinned coherent host-mapped, [n_pairs * small cap]
-  uint8_t* d_hits = nullptr;   // device alias of h_hits
-  double* d_qs = nullptr;      // device input of the latency path
-  double* d_qmap = nullptr;    // h_q as the device sees it (zero-copy input)
-  double* d_ssc = nullptr;     // latency path joint (sin, cos) [small cap * dof * 2]
-  double* h_ssc = nullptr;     // pinned host-mapped twin: sin/cos computed on the host (small batches)
-  double* d_sscmap = nullptr;  // h_ssc as the device sees it
-  int64_t small_host_sc = 64;  // latency batches up to this size: sin/cos on the host (MPG_SMALL_HOST_SC)
-  bool small_args = true;      // the fewest states' rows in the kernel arguments (MPG_SMALL_ARGS=0: off)
-  std::vector<int> h_rev_src;  // move-group slots of revolute joints (host copy of the snapshot's rule)
-  // host-buffer calls without a stream run on this non-blocking stream (not
-  // the legacy default stream, whose synchronisation covers every blocking
-  // stream of the device); MPG_OWN_STREAM=0 keeps the caller's NULL stream
-  hipStream_t own_stream = nullptr;
-  bool small_zero_copy = true; // MPG_SMALL_ZEROCOPY=0: stage through d_qs
-  int64_t small_inline_sc = 256;  // latency batches up to this size: sin/cos inline (MPG_SMALL_INLINE_SC)
-  // latency server (lat_server_kernel): control block in host-mapped memory,
-  // its own stream; started on demand, leaves after srv_idle_us idle
-  SrvCtl* srv_h = nullptr;
-  SrvCtl* srv_d = nullptr;
-  hipStream_t srv_stream = nullptr;
-  unsigned long long srv_seq = 0;
-  bool srv_running = false;
-  bool srv_ok = false;      // the world fits the server (closed-form / MPR pairs only, records, LDS)
-  bool srv_broken = false;  // it failed to answer: launches until srv_retry_at
-  std::chrono::steady_clock::time_point srv_retry_at{};
-  bool srv_quitting = false;  // quit was set after a missed answer; the stream may still run
-  int64_t srv_served = 0, srv_starts = 0, srv_fallbacks = 0;  // mpg_latency_server_stats
-  int srv_mode = 1;         // MPG_SMALL_SERVER=0: off
-  long long srv_idle_us = 1000;
-  int srv_g = 8;            // workgroups (MPG_SMALL_SERVER_WG)
-  int srv_max_n = kSrvN;    // batches up to this size go to the server (MPG_SMALL_SERVER_MAX)
-  size_t srv_lds = 0;
-  bool srv_stats = false;
-  double srv_stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  size_t small_cap = 0;   // configurations (hit bytes per pair)
-  size_t small_qcap = 0;  // input doubles (h_q, d_qs)
-  // host-buffer batches above small_max (collide_host_pipelined): chunks
-  // through a ring of slots -- the input of one chunk crosses PCIe while the
-  // previous one computes and the one before is unpacked on the host.
-  // Grow-only, guarded by host_mu.
-  static constexpr int kRing = 3;
-  struct Ring {
-    double* d_in[kRing] = {};
-    uint8_t* d_fl[kRing] = {};
-    uint32_t* d_mk[kRing] = {};
-    uint32_t* d_bcnt[kRing] = {};  // colliding configurations per kPackCfg block
-    uint8_t* h_fl[kRing] = {};     // pinned, host-mapped: the chunk's flags (mask_pack_kernel)
-    uint32_t* h_mk[kRing] = {};    // pinned, host-mapped: packed mask rows (mask_pack_kernel)
-    uint32_t* h_mk_d[kRing] = {};  // h_mk as the device sees it
-    uint32_t* h_bcnt[kRing] = {};  // pinned, host-mapped copy of d_bcnt (where each block's packed rows start)
-    uint8_t* h_fl_d[kRing] = {};   // device aliases of h_fl, h_bcnt
-    uint32_t* h_bcnt_d[kRing] = {};
-    hipEvent_t e_in[kRing] = {}, e_done[kRing] = {};
-    hipStream_t h2d = nullptr;     // input copies
-    hipStream_t side = nullptr;    // odd chunks compute here (one chunk's narrow tail overlaps the next's cull)
-    size_t cap = 0;                // configurations per slot
-    size_t in_cap = 0;             // input doubles per slot
-  } ring;
-  // chunk sizes: profiles/r06a/host_ab*.txt (2^18 / 2^19 chunks, head and
-  // tail sizes within +-3 % of each other on cfg3 2^20; this is the best seen)
-  long long ring_chunk = 1 << 19;  // largest chunk (env MPG_HOST_CHUNK)
-  int ring_streams = 2;            // compute streams of the pipeline (env MPG_HOST_STREAMS: 1 or 2)
-  int host_threads = 8;            // threads unpacking a finished chunk (env MPG_HOST_THREADS)
-  long long ring_head = 1 << 17, ring_tail = 1 << 16;  // smaller first / last chunk (env MPG_HOST_HEAD / _TAIL)
-  std::unique_ptr<mpg_hostpipe::Pool> pool;
-  // MPG_STATS: host pipeline phase sums (us): calls, input copy, issue,
-  // result wait, unpack, whole call
-  double hp_stat[6] = {0, 0, 0, 0, 0, 0};
-};
+#include "mpg_world.h"
 
 namespace {
 
-// Spatial clusters of one mesh's triangle records: the leaves of a median
-// split (centroids, longest axis) with at most `leaf` triangles each, in
-// order; triangle k of the clusters' ranges is rec[order[k]].
-void mesh_build_clusters(const std::vector<double>& rec, std::vector<int>& order, int lo, int hi, int leaf, int rec0,
-                         std::vector<double>& box, std::vector<int>& link) {
-  auto cen = [&](int t, int k) {
-    const double* r = rec.data() + (size_t)TR_STRIDE * t;
-    return r[TR_LO + k] + r[TR_HI + k];
-  };
-  if (hi - lo <= leaf) {
-    double blo[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, bhi[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
-    for (int i = lo; i < hi; ++i) {
-      const double* r = rec.data() + (size_t)TR_STRIDE * order[i];
-      for (int k = 0; k < 3; ++k) {
-        blo[k] = std::min(blo[k], r[TR_LO + k]);
-        bhi[k] = std::max(bhi[k], r[TR_HI + k]);
-      }
-    }
-    box.insert(box.end(), {blo[0], blo[1], blo[2], bhi[0], bhi[1], bhi[2]});
-    link.insert(link.end(), {rec0 + lo, hi - lo});
-    return;
-  }
-  double clo[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, chi[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
-  for (int i = lo; i < hi; ++i)
-    for (int k = 0; k < 3; ++k) {
-      clo[k] = std::min(clo[k], cen(order[i], k));
-      chi[k] = std::max(chi[k], cen(order[i], k));
-    }
-  int ax = 0;
-  for (int k = 1; k < 3; ++k)
-    if (chi[k] - clo[k] > chi[ax] - clo[ax]) ax = k;
-  const int mid = (lo + hi) / 2;
-  std::nth_element(order.begin() + lo, order.begin() + mid, order.begin() + hi,
-                   [&](int a, int b) { return cen(a, ax) < cen(b, ax) || (cen(a, ax) == cen(b, ax) && a < b); });
-  mesh_build_clusters(rec, order, lo, mid, leaf, rec0, box, link);
-  mesh_build_clusters(rec, order, mid, hi, leaf, rec0, box, link);
-}
-
-struct BlobBuilder {
-  std::vector<char> bytes;
-  template <class T>
-  size_t add(const T* data, size_t count) {
-    size_t off = (bytes.size() + 15) & ~size_t(15);
-    bytes.resize(off + sizeof(T) * std::max<size_t>(count, 1), 0);
-    if (count) std::memcpy(bytes.data() + off, data, sizeof(T) * count);
-    return off;
-  }
-};
-
-bool finite_all(const double* p, size_t n) {
-  for (size_t i = 0; i < n; ++i)
-    if (!std::isfinite(p[i])) return false;
-  return true;
-}
-
-int obj_geom_type(const mpg_world_desc* d, int id) {
-  return d->geom_type[id < d->n_moving ? d->moving_geom[id] : d->static_geom[id - d->n_moving]];
-}
-
-// a movable object: a moving object whose link is a free frame
-bool desc_obj_movable(const mpg_world_desc* d, int id) {
-  return id < d->n_moving && d->link_parent[d->moving_link[id]] == MPG_LINK_FREE;
-}
-
-// FCL closed-form pair for (o1, o2) in fcl::collide argument order
-int closed_form_kind(const mpg_world_desc* d, int a, int b) {
-  const int ta = obj_geom_type(d, a), tb = obj_geom_type(d, b);
-  if (ta == MPG_GEOM_MESH || tb == MPG_GEOM_MESH) return CF_MESH;
-  if (ta == MPG_GEOM_OCTREE || tb == MPG_GEOM_OCTREE) return CF_OCTREE;
-  if (ta == MPG_GEOM_BOX && tb == MPG_GEOM_BOX) return CF_BOX_BOX;
-  if (ta == MPG_GEOM_SPHERE && tb == MPG_GEOM_SPHERE) return CF_SPHERE_SPHERE;
-  if (ta == MPG_GEOM_SPHERE && tb == MPG_GEOM_BOX) return CF_SPHERE_BOX;
-  if (ta == MPG_GEOM_BOX && tb == MPG_GEOM_SPHERE) return CF_BOX_SPHERE;
-  if (ta == MPG_GEOM_SPHERE && tb == MPG_GEOM_CAPSULE) return CF_SPHERE_CAPSULE;
-  if (ta == MPG_GEOM_CAPSULE && tb == MPG_GEOM_SPHERE) return CF_CAPSULE_SPHERE;
-  if (ta == MPG_GEOM_SPHERE && tb == MPG_GEOM_CYLINDER) return CF_SPHERE_CYLINDER;
-  if (ta == MPG_GEOM_CYLINDER && tb == MPG_GEOM_SPHERE) return CF_CYLINDER_SPHERE;
-  return CF_NONE;
-}
-
-int validate(const mpg_world_desc* d) {
-  if (!d) return set_error(MPG_E_INVALID, "desc is NULL");
-  if (d->gjk_solver != MPG_GJK_LIBCCD && d->gjk_solver != MPG_GJK_INDEP)
-    return set_error(MPG_E_INVALID, "gjk_solver must be MPG_GJK_LIBCCD or MPG_GJK_INDEP");
-  if (d->n_joints < 0 || d->n_joints > kMaxJoints) return set_error(MPG_E_INVALID, "n_joints out of range [0, 32]");
-  if (d->dof < 0) return set_error(MPG_E_INVALID, "dof < 0");
-  if (d->n_links < 0 || d->n_geoms < 0 || d->n_moving < 0 || d->n_static < 0 || d->n_pairs < 0)
-    return set_error(MPG_E_INVALID, "negative count");
-  for (int j = 0; j < d->n_joints; ++j) {
-    if (d->joint_type[j] < 0 || d->joint_type[j] > MPG_JOINT_RUB_UNALIGNED)
-      return set_error(MPG_E_INVALID, "bad joint type");
-    if (d->joint_parent[j] < 0 || d->joint_parent[j] > j)
-      return set_error(MPG_E_INVALID, "joint_parent must reference an earlier joint (0 = universe)");
-    if (d->joint_q_source[j] >= d->dof) return set_error(MPG_E_INVALID, "joint_q_source >= dof");
-  }
-  for (int l = 0; l < d->n_links; ++l) {
-    if (d->link_parent[l] < MPG_LINK_FREE || d->link_parent[l] > d->n_joints)
-      return set_error(MPG_E_INVALID, "bad link_parent");
-    if (l > 0 && d->link_parent[l] != MPG_LINK_FREE && d->link_parent[l - 1] == MPG_LINK_FREE)
-      return set_error(MPG_E_INVALID, "free frames (link_parent MPG_LINK_FREE) must be the trailing links");
-  }
-  for (int g = 0; g < d->n_geoms; ++g) {
-    const int t = d->geom_type[g];
-    if (t < MPG_GEOM_CONVEX || t > MPG_GEOM_TRIANGLE) return set_error(MPG_E_UNSUPPORTED, "unsupported geometry type");
-    if (t == MPG_GEOM_TRIANGLE && (d->geom_vertex_count[g] != 3 || d->geom_vertex_start[g] < 0 ||
-                                   (int64_t)d->geom_vertex_start[g] + 3 > d->n_vertices))
-      return set_error(MPG_E_INVALID, "a TriangleP needs 3 vertices inside the vertex array");
-    if (t == MPG_GEOM_ELLIPSOID || t == MPG_GEOM_CONE) {
-      const double* p = d->geom_param + 4 * g;
-      const int np = t == MPG_GEOM_ELLIPSOID ? 3 : 2;
-      for (int k = 0; k < np; ++k)
-        if (!(p[k] > 0.0 && std::isfinite(p[k])))
-          return set_error(MPG_E_INVALID, "ellipsoid radii / cone radius and lz must be positive and finite");
-    }
-    if (t == MPG_GEOM_CONVEX || t == MPG_GEOM_MESH) {
-      if (d->geom_vertex_count[g] <= 0 || d->geom_vertex_start[g] < 0 ||
-          (int64_t)d->geom_vertex_start[g] + d->geom_vertex_count[g] > d->n_vertices)
-        return set_error(MPG_E_INVALID, "convex vertex range out of bounds");
-    }
-    if (t == MPG_GEOM_CONVEX) {  // faces (FCL layout) inside convex_face, indices inside the hull
-      const double f0 = d->geom_param[4 * g], fn = d->geom_param[4 * g + 1];
-      if (!(f0 >= 0 && fn >= 0 && f0 == std::floor(f0) && fn == std::floor(fn)))
-        return set_error(MPG_E_INVALID, "convex face range out of bounds");
-      if (fn > 0) {
-        if (!d->convex_face) return set_error(MPG_E_INVALID, "bad convex face array");
-        int64_t i = (int64_t)f0;
-        for (int64_t f = 0; f < (int64_t)fn; ++f) {
-          if (i >= d->n_convex_face_ints) return set_error(MPG_E_INVALID, "convex face range out of bounds");
-          const int cnt = d->convex_face[i];
-          if (cnt < 1 || i + cnt >= d->n_convex_face_ints) return set_error(MPG_E_INVALID, "convex face range out of bounds");
-          for (int k = 1; k <= cnt; ++k)
-            if (d->convex_face[i + k] < 0 || d->convex_face[i + k] >= d->geom_vertex_count[g])
-              return set_error(MPG_E_INVALID, "convex face vertex index out of range");
-          i += cnt + 1;
-        }
-      }
-    }
-    if (t == MPG_GEOM_MESH) {
-      const double t0 = d->geom_param[4 * g], tn = d->geom_param[4 * g + 1];
-      if (!(t0 >= 0 && tn >= 0 && t0 == std::floor(t0) && tn == std::floor(tn) && t0 + tn <= (double)d->n_mesh_triangles))
-        return set_error(MPG_E_INVALID, "mesh triangle range out of bounds");
-      if (tn > 0 && !d->mesh_triangle) return set_error(MPG_E_INVALID, "bad mesh triangle array");
-      for (int64_t i = (int64_t)t0; i < (int64_t)(t0 + tn); ++i)
-        for (int k = 0; k < 3; ++k)
-          if (d->mesh_triangle[3 * i + k] < 0 || d->mesh_triangle[3 * i + k] >= d->geom_vertex_count[g])
-            return set_error(MPG_E_INVALID, "mesh triangle vertex index out of range");
-    }
-  }
-  for (int m = 0; m < d->n_moving; ++m) {
-    if (d->moving_link[m] < 0 || d->moving_link[m] >= d->n_links) return set_error(MPG_E_INVALID, "bad moving_link");
-    if (d->moving_geom[m] < 0 || d->moving_geom[m] >= d->n_geoms) return set_error(MPG_E_INVALID, "bad moving_geom");
-  }
-  // one object per free frame, at the frame itself: its world transform is
-  // the frame's isometry, bit for bit (compound movable bodies: out of scope)
-  for (int l = 0; l < d->n_links; ++l) {
-    if (d->link_parent[l] != MPG_LINK_FREE) continue;
-    int count = 0;
-    for (int m = 0; m < d->n_moving; ++m) {
-      if (d->moving_link[m] != l) continue;
-      ++count;
-      static const double ident[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
-      for (int k = 0; k < 12; ++k)
-        if (!(d->moving_offset[12 * (size_t)m + k] == ident[k]))
-          return set_error(MPG_E_INVALID, "the object of a free frame needs the identity moving_offset");
-    }
-    if (count != 1) return set_error(MPG_E_INVALID, "a free frame carries exactly one object");
-  }
-  if (d->n_mesh_triangles < 0 || (d->n_mesh_triangles > 0 && !d->mesh_triangle))
-    return set_error(MPG_E_INVALID, "bad mesh triangle array");
-  if (d->n_octree_leaves < 0 || (d->n_octree_leaves > 0 && !d->octree_leaf))
-    return set_error(MPG_E_INVALID, "bad octree leaf array");
-  for (int g = 0; g < d->n_geoms; ++g) {
-    if (d->geom_type[g] != MPG_GEOM_OCTREE) continue;
-    const double l0 = d->geom_param[4 * g], ln = d->geom_param[4 * g + 1];
-    if (!(l0 >= 0 && ln >= 0 && l0 == std::floor(l0) && ln == std::floor(ln) && l0 + ln <= (double)d->n_octree_leaves))
-      return set_error(MPG_E_INVALID, "octree leaf range out of bounds");
-  }
-  if (!finite_all(d->octree_leaf, 6 * (size_t)d->n_octree_leaves))
-    return set_error(MPG_E_INVALID, "non-finite octree leaf");
-  for (int s = 0; s < d->n_static; ++s)
-    if (d->static_geom[s] < 0 || d->static_geom[s] >= d->n_geoms) return set_error(MPG_E_INVALID, "bad static_geom");
-  const int nobj = d->n_moving + d->n_static;
-  for (int p = 0; p < d->n_pairs; ++p) {
-    const int a = d->pair_a[p], b = d->pair_b[p];
-    if (a < 0 || a >= nobj || b < 0 || b >= nobj) return set_error(MPG_E_INVALID, "pair object id out of range");
-    if (a >= d->n_moving && b >= d->n_moving) return set_error(MPG_E_INVALID, "static-static pair");
-    // a movable object (on a free frame) only meets link-borne objects: the
-    // cull's far test drops it against the ball that holds those
-    const bool fa = desc_obj_movable(d, a), fb = desc_obj_movable(d, b);
-    if ((fa && (fb || b >= d->n_moving)) || (fb && a >= d->n_moving))
-      return set_error(MPG_E_INVALID, "a movable object pairs with link-borne objects only (not static, not movable)");
-    // an OcTree may ride on a link or an attached body (attachObject takes any
-    // FCL geometry, planning_world.cpp:174-191), and meet another OcTree
-    // (octree_octree_wave; its contacts and distance are refused per call)
-    // FCL 0.7.0 GJKSolver_libccd: box-box, sphere-sphere, sphere-box,
-    // sphere-capsule and sphere-cylinder have closed forms (all on the
-    // device, closed_form_kind); every other shape pair is MPR
-    if (!(d->pair_allowed && d->pair_allowed[p])) {
-      const int ta = obj_geom_type(d, a), tb = obj_geom_type(d, b);
-      const bool tri = ta == MPG_GEOM_TRIANGLE || tb == MPG_GEOM_TRIANGLE;
-      if (tri && (ta == MPG_GEOM_MESH || tb == MPG_GEOM_MESH || ta == MPG_GEOM_OCTREE || tb == MPG_GEOM_OCTREE))
-        return set_error(MPG_E_UNSUPPORTED, "a TriangleP paired with an OcTree or BVH mesh is not implemented");
-    }
-    if (d->gjk_solver == MPG_GJK_INDEP && !(d->pair_allowed && d->pair_allowed[p])) {
-      const int ta = obj_geom_type(d, a), tb = obj_geom_type(d, b);
-      if (ta == MPG_GEOM_MESH || tb == MPG_GEOM_MESH || ta == MPG_GEOM_OCTREE || tb == MPG_GEOM_OCTREE)
-        return set_error(MPG_E_UNSUPPORTED,
-                         "gjk_solver MPG_GJK_INDEP with an OcTree or BVH mesh in a pair is not implemented");
-    }
-  }
-  if (!finite_all(d->joint_placement, 12 * (size_t)d->n_joints) || !finite_all(d->link_placement, 12 * (size_t)d->n_links) ||
-      !finite_all(d->vertices, 3 * (size_t)d->n_vertices))
-    return set_error(MPG_E_INVALID, "non-finite value in descriptor");
-  if (!(d->gjk_tolerance > 0)) return set_error(MPG_E_INVALID, "gjk_tolerance must be > 0");
-  return MPG_OK;
-}
-
-void geom_record(const mpg_world_desc* d, int g, double* rec) {
-  for (int k = 0; k < G_STRIDE; ++k) rec[k] = 0.0;
-  for (int k = 0; k < 4; ++k) rec[G_PARAM + k] = d->geom_param[4 * g + k];
-  const int t = d->geom_type[g];
-  double lo[3], hi[3];
-  if (t == MPG_GEOM_CONVEX || t == MPG_GEOM_MESH) {
-    const double* V = d->vertices + 3 * (size_t)d->geom_vertex_start[g];
-    const int nv = d->geom_vertex_count[g];
-    // FCL 0.7.0 Convex: interior point = (sum of vertices) * (1.0 / n)
-    double s[3] = {0.0, 0.0, 0.0};
-    for (int i = 0; i < nv; ++i) {
-      s[0] += V[3 * i];
-      s[1] += V[3 * i + 1];
-      s[2] += V[3 * i + 2];
-    }
-    const double inv = 1.0 / (double)nv;
-    for (int k = 0; k < 3; ++k) rec[G_INTERIOR + k] = s[k] * inv;
-    for (int k = 0; k < 3; ++k) lo[k] = hi[k] = V[k];
-    for (int i = 1; i < nv; ++i)
-      for (int k = 0; k < 3; ++k) {
-        lo[k] = std::min(lo[k], V[3 * i + k]);
-        hi[k] = std::max(hi[k], V[3 * i + k]);
-      }
-  } else if (t == MPG_GEOM_BOX) {
-    for (int k = 0; k < 3; ++k) {
-      hi[k] = d->geom_param[4 * g + k] / 2.0;
-      lo[k] = -hi[k];
-    }
-  } else if (t == MPG_GEOM_SPHERE) {
-    for (int k = 0; k < 3; ++k) {
-      hi[k] = d->geom_param[4 * g];
-      lo[k] = -hi[k];
-    }
-  } else if (t == MPG_GEOM_TRIANGLE) {  // triCreateGJKObject: centre ((a + b) + c) / 3
-    const double* V = d->vertices + 3 * (size_t)d->geom_vertex_start[g];
-    for (int k = 0; k < 3; ++k) {
-      rec[G_INTERIOR + k] = (V[k] + V[3 + k] + V[6 + k]) / 3;
-      lo[k] = std::min(V[k], std::min(V[3 + k], V[6 + k]));
-      hi[k] = std::max(V[k], std::max(V[3 + k], V[6 + k]));
-    }
-  } else if (t == MPG_GEOM_ELLIPSOID) {
-    for (int k = 0; k < 3; ++k) {
-      hi[k] = d->geom_param[4 * g + k];
-      lo[k] = -hi[k];
-    }
-  } else if (t == MPG_GEOM_OCTREE) {  // union of the occupied leaf boxes (octree frame)
-    const int64_t l0 = (int64_t)d->geom_param[4 * g], ln = (int64_t)d->geom_param[4 * g + 1];
-    for (int k = 0; k < 3; ++k) {
-      lo[k] = ln > 0 ? DBL_MAX : 0.0;
-      hi[k] = ln > 0 ? -DBL_MAX : 0.0;
-    }
-    for (int64_t i = l0; i < l0 + ln; ++i)
-      for (int k = 0; k < 3; ++k) {
-        lo[k] = std::min(lo[k], d->octree_leaf[6 * i + k]);
-        hi[k] = std::max(hi[k], d->octree_leaf[6 * i + 3 + k]);
-      }
-  } else {  // capsule / cylinder / cone along z
-    const double r = d->geom_param[4 * g], hz = d->geom_param[4 * g + 1] / 2.0 + (t == MPG_GEOM_CAPSULE ? r : 0.0);
-    lo[0] = lo[1] = -r;
-    hi[0] = hi[1] = r;
-    lo[2] = -hz;
-    hi[2] = hz;
-  }
-  // local box, widened by a relative epsilon so rounding never shrinks it
-  double r2 = 0.0;
-  for (int k = 0; k < 3; ++k) {
-    const double c = 0.5 * (lo[k] + hi[k]);
-    const double e = 0.5 * (hi[k] - lo[k]);
-    rec[G_OBB_C + k] = c;
-    rec[G_OBB_E + k] = e * (1.0 + 1e-12) + 1e-12;
-    rec[G_AABB_E + k] = (hi[k] - lo[k]) * 0.5;
-    r2 += rec[G_OBB_E + k] * rec[G_OBB_E + k];
-  }
-  if (t == MPG_GEOM_CONVEX || t == MPG_GEOM_MESH || t == MPG_GEOM_TRIANGLE) {  // bounding sphere about the box centre: farthest vertex
-    const double* V = d->vertices + 3 * (size_t)d->geom_vertex_start[g];
-    r2 = 0.0;
-    for (int i = 0; i < d->geom_vertex_count[g]; ++i) {
-      double s2 = 0.0;
-      for (int k = 0; k < 3; ++k) {
-        const double dv = V[3 * i + k] - rec[G_OBB_C + k];
-        s2 += dv * dv;
-      }
-      r2 = std::max(r2, s2);
-    }
-  }
-  rec[G_RADIUS] = std::sqrt(r2) * (1.0 + 1e-12) + 1e-12;
-  double vmax = 0.0;
-  if (t == MPG_GEOM_CONVEX) {
-    const double* V = d->vertices + 3 * (size_t)d->geom_vertex_start[g];
-    for (int i = 0; i < 3 * d->geom_vertex_count[g]; ++i) vmax = std::max(vmax, std::fabs(V[i]));
-  }
-  rec[G_VMAX] = vmax;
-}
-
-// ---------------------------------------------------------------------------
-// FCL 0.7.0 BVHModel<OBBRSS>::endModel -> buildTree for the meshes
-// (load_mesh_as_BVH, src/urdf_utils.cpp:136-155) [ext FCL BVH_model-inl.h,
-// BV_fitter-inl.h, BV_splitter-inl.h, math/geometry-inl.h; restated, FCL is
-// not under /root/reference]: BVFitter<OBBRSS>::fit (covariance of the
-// node's triangle vertices, Jacobi eigen_old, axisFromEigen, extent and
-// centre of the projections; only the OBB half decides collisions), the
-// SPLIT_METHOD_MEAN rule along the first axis (centroid . axis > mean goes
-// right, the rest are swapped to the front; an empty side -> n / 2), child
-// pairs allocated at num_bvs before recursing.  The oracle builds the same
-// tree from its own code (oracle/collide_oracle.c orc_bvh_build).
-// ---------------------------------------------------------------------------
-struct FclBvh {
-  std::vector<double> box;  // [n][FB_STRIDE]
-  std::vector<int> link;    // [n][3]
-  int max_depth = 0;        // deepest leaf (root = 0), bounds the device gates' descent
-};
-
-// eigen_old: Jacobi rotations; vout(r, c) = v[c][r], dout = eigenvalues
-void fcl_eigen_old(const double m[9], double dout[3], double vout[9]) {
-  double R[3][3] = {{m[0], m[1], m[2]}, {m[3], m[4], m[5]}, {m[6], m[7], m[8]}};
-  double b[3], z[3], v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, d[3];
-  for (int ip = 0; ip < 3; ++ip) {
-    b[ip] = d[ip] = R[ip][ip];
-    z[ip] = 0;
-  }
-  for (int i = 0; i < 50; ++i) {
-    double sm = 0;
-    for (int ip = 0; ip < 3; ++ip)
-      for (int iq = ip + 1; iq < 3; ++iq) sm += std::fabs(R[ip][iq]);
-    if (sm == 0.0) {
-      for (int c = 0; c < 3; ++c)
-        for (int r = 0; r < 3; ++r) vout[3 * r + c] = v[c][r];
-      for (int k = 0; k < 3; ++k) dout[k] = d[k];
-      return;
-    }
-    const double tresh = i < 3 ? 0.2 * sm / (3 * 3) : 0.0;
-    for (int ip = 0; ip < 3; ++ip)
-      for (int iq = ip + 1; iq < 3; ++iq) {
-        double g = 100.0 * std::fabs(R[ip][iq]);
-        if (i > 3 && std::fabs(d[ip]) + g == std::fabs(d[ip]) && std::fabs(d[iq]) + g == std::fabs(d[iq])) {
-          R[ip][iq] = 0.0;
-        } else if (std::fabs(R[ip][iq]) > tresh) {
-          double h = d[iq] - d[ip], t;
-          if (std::fabs(h) + g == std::fabs(h)) {
-            t = R[ip][iq] / h;
-          } else {
-            const double theta = 0.5 * h / R[ip][iq];
-            t = 1.0 / (std::fabs(theta) + std::sqrt(1.0 + theta * theta));
-            if (theta < 0.0) t = -t;
-          }
-          const double c = 1.0 / std::sqrt(1 + t * t), s = t * c, tau = s / (1.0 + c);
-          h = t * R[ip][iq];
-          z[ip] -= h;
-          z[iq] += h;
-          d[ip] -= h;
-          d[iq] += h;
-          R[ip][iq] = 0.0;
-          auto rot = [&](double& x, double& y) {
-            const double gg = x, hh = y;
-            x = gg - s * (hh + gg * tau);
-            y = hh + s * (gg - hh * tau);
-          };
-          for (int j = 0; j < ip; ++j) rot(R[j][ip], R[j][iq]);
-          for (int j = ip + 1; j < iq; ++j) rot(R[ip][j], R[j][iq]);
-          for (int j = iq + 1; j < 3; ++j) rot(R[ip][j], R[iq][j]);
-          for (int j = 0; j < 3; ++j) rot(v[j][ip], v[j][iq]);
-        }
-      }
-    for (int ip = 0; ip < 3; ++ip) {
-      b[ip] += z[ip];
-      d[ip] = b[ip];
-      z[ip] = 0.0;
-    }
-  }
-}
-
-// covariance sums -> M -> eigen -> axisFromEigen -> extent / centre of pts
-void fcl_fit_obb(const double S1[3], const double S2[6], double n_points, const std::vector<const double*>& pts,
-                 double* box) {
-  double M[9], E[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, ev[3] = {0, 0, 0};
-  M[0] = S2[0] - S1[0] * S1[0] / n_points;
-  M[4] = S2[1] - S1[1] * S1[1] / n_points;
-  M[8] = S2[2] - S1[2] * S1[2] / n_points;
-  M[1] = M[3] = S2[3] - S1[0] * S1[1] / n_points;
-  M[5] = M[7] = S2[5] - S1[1] * S1[2] / n_points;
-  M[2] = M[6] = S2[4] - S1[0] * S1[2] / n_points;
-  fcl_eigen_old(M, ev, E);
-  int mn, mid, mx;
-  if (ev[0] > ev[1]) {
-    mx = 0;
-    mn = 1;
-  } else {
-    mn = 0;
-    mx = 1;
-  }
-  if (ev[2] < ev[mn]) {
-    mid = mn;
-    mn = 2;
-  } else if (ev[2] > ev[mx]) {
-    mid = mx;
-    mx = 2;
-  } else {
-    mid = 2;
-  }
-  double* ax = box + FB_AXIS;
-  for (int r = 0; r < 3; ++r) {
-    ax[3 * r] = E[3 * mx + r];
-    ax[3 * r + 1] = E[3 * mid + r];
-  }
-  ax[2] = ax[3] * ax[7] - ax[6] * ax[4];
-  ax[5] = ax[6] * ax[1] - ax[0] * ax[7];
-  ax[8] = ax[0] * ax[4] - ax[3] * ax[1];
-  double lo[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, hi[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
-  for (const double* p : pts)
-    for (int k = 0; k < 3; ++k) {
-      const double pr = (ax[k] * p[0] + ax[3 + k] * p[1]) + ax[6 + k] * p[2];
-      if (pr > hi[k]) hi[k] = pr;
-      if (pr < lo[k]) lo[k] = pr;
-    }
-  double o[3];
-  for (int k = 0; k < 3; ++k) o[k] = (hi[k] + lo[k]) / 2;
-  for (int i = 0; i < 3; ++i) box[FB_TO + i] = (ax[3 * i] * o[0] + ax[3 * i + 1] * o[1]) + ax[3 * i + 2] * o[2];
-  for (int k = 0; k < 3; ++k) box[FB_EXT + k] = (hi[k] - lo[k]) * 0.5;
-}
-
-void fcl_bvh_node(FclBvh& B, const double* V, const int32_t* tri, std::vector<int>& prim, int id, int first, int n,
-                  int base, int depth = 0) {
-  if (depth > B.max_depth) B.max_depth = depth;
-  int* cur = prim.data() + first;
-  double S1[3] = {0, 0, 0}, S2[6] = {0, 0, 0, 0, 0, 0};
-  std::vector<const double*> pts;
-  pts.reserve(3 * (size_t)n);
-  for (int i = 0; i < n; ++i) {
-    const int32_t* t = tri + 3 * cur[i];
-    const double *p1 = V + 3 * t[0], *p2 = V + 3 * t[1], *p3 = V + 3 * t[2];
-    for (int k = 0; k < 3; ++k) S1[k] += (p1[k] + p2[k]) + p3[k];
-    S2[0] += (p1[0] * p1[0] + p2[0] * p2[0]) + p3[0] * p3[0];
-    S2[1] += (p1[1] * p1[1] + p2[1] * p2[1]) + p3[1] * p3[1];
-    S2[2] += (p1[2] * p1[2] + p2[2] * p2[2]) + p3[2] * p3[2];
-    S2[3] += (p1[0] * p1[1] + p2[0] * p2[1]) + p3[0] * p3[1];
-    S2[4] += (p1[0] * p1[2] + p2[0] * p2[2]) + p3[0] * p3[2];
-    S2[5] += (p1[1] * p1[2] + p2[1] * p2[2]) + p3[1] * p3[2];
-    pts.push_back(p1);
-    pts.push_back(p2);
-    pts.push_back(p3);
-  }
-  double* box = B.box.data() + (size_t)FB_STRIDE * (base + id);
-  fcl_fit_obb(S1, S2, 3.0 * n, pts, box);
-  int* lk = B.link.data() + 3 * (size_t)(base + id);
-  lk[1] = first;
-  lk[2] = n;
-  if (n == 1) {
-    lk[0] = -(cur[0] + 1);
-    return;
-  }
-  const double sv[3] = {box[FB_AXIS], box[FB_AXIS + 3], box[FB_AXIS + 6]};
-  double c[3] = {0, 0, 0};
-  for (int i = 0; i < n; ++i) {
-    const int32_t* t = tri + 3 * cur[i];
-    for (int k = 0; k < 3; ++k) c[k] += (V[3 * t[0] + k] + V[3 * t[1] + k]) + V[3 * t[2] + k];
-  }
-  const double split = ((c[0] * sv[0] + c[1] * sv[1]) + c[2] * sv[2]) / (3 * n);
-  const int child = (int)(B.link.size() / 3) - base;  // num_bvs
-  lk[0] = base + child;
-  B.box.resize(B.box.size() + 2 * FB_STRIDE);
-  B.link.resize(B.link.size() + 6);
-  int c1 = 0;
-  for (int i = 0; i < n; ++i) {
-    const int32_t* t = tri + 3 * cur[i];
-    double p[3];
-    for (int k = 0; k < 3; ++k) p[k] = ((V[3 * t[0] + k] + V[3 * t[1] + k]) + V[3 * t[2] + k]) / 3.0;
-    if (!(((sv[0] * p[0] + sv[1] * p[1]) + sv[2] * p[2]) > split)) std::swap(cur[i], cur[c1++]);
-  }
-  if (c1 == 0 || c1 == n) c1 = n / 2;
-  fcl_bvh_node(B, V, tri, prim, child, first, c1, base, depth + 1);
-  fcl_bvh_node(B, V, tri, prim, child + 1, first + c1, n - c1, base, depth + 1);
-}
-
-// computeBV<OBB>(shape, identity): box I / side/2; sphere I / r; capsule
-// I / (r, r, lz/2 + r); cylinder and cone I / (r, r, lz/2); ellipsoid I /
-// radii; convex: fitn over the
-// vertices (covariance of the points)
-void fcl_shape_obb(const mpg_world_desc* d, int g, double* o) {
-  std::fill(o, o + FB_STRIDE, 0.0);
-  o[FB_AXIS] = o[FB_AXIS + 4] = o[FB_AXIS + 8] = 1.0;
-  const double* p = d->geom_param + 4 * g;
-  switch (d->geom_type[g]) {
-    case MPG_GEOM_BOX:
-      for (int k = 0; k < 3; ++k) o[FB_EXT + k] = p[k] * 0.5;
-      break;
-    case MPG_GEOM_SPHERE:
-      o[FB_EXT] = o[FB_EXT + 1] = o[FB_EXT + 2] = p[0];
-      break;
-    case MPG_GEOM_CAPSULE:
-      o[FB_EXT] = o[FB_EXT + 1] = p[0];
-      o[FB_EXT + 2] = p[1] / 2 + p[0];
-      break;
-    case MPG_GEOM_CYLINDER:
-    case MPG_GEOM_CONE:
-      o[FB_EXT] = o[FB_EXT + 1] = p[0];
-      o[FB_EXT + 2] = p[1] / 2;
-      break;
-    case MPG_GEOM_ELLIPSOID:
-      for (int k = 0; k < 3; ++k) o[FB_EXT + k] = p[k];
-      break;
-    case MPG_GEOM_CONVEX: {
-      const double* V = d->vertices + 3 * (size_t)d->geom_vertex_start[g];
-      const int nv = d->geom_vertex_count[g];
-      double S1[3] = {0, 0, 0}, S2[6] = {0, 0, 0, 0, 0, 0};
-      std::vector<const double*> pts;
-      for (int i = 0; i < nv; ++i) {
-        const double* q = V + 3 * i;
-        for (int k = 0; k < 3; ++k) S1[k] += q[k];
-        S2[0] += q[0] * q[0];
-        S2[1] += q[1] * q[1];
-        S2[2] += q[2] * q[2];
-        S2[3] += q[0] * q[1];
-        S2[4] += q[0] * q[2];
-        S2[5] += q[1] * q[2];
-        pts.push_back(q);
-      }
-      if (nv > 0) fcl_fit_obb(S1, S2, (double)nv, pts, o);
-      break;
-    }
-    default:
-      break;
-  }
-}
-
-void static_record(const mpg_world_desc* d, int s, const double* geom_rec_all, double* rec) {
-  const double* T = d->static_transform + 12 * s;
-  const CQ4 r = gjk_rot_from_matrix(T);  // the ccd_real rotation MPR uses
-  const CQ4 ri = quat_invert2(r);
-  rec[S_ROT] = r.x; rec[S_ROT + 1] = r.y; rec[S_ROT + 2] = r.z; rec[S_ROT + 3] = r.w;
-  rec[S_ROTINV] = ri.x; rec[S_ROTINV + 1] = ri.y; rec[S_ROTINV + 2] = ri.z; rec[S_ROTINV + 3] = ri.w;
-  rec[S_POS] = T[9]; rec[S_POS + 1] = T[10]; rec[S_POS + 2] = T[11];
-  // broad-phase OBB from the same rotation MPR uses
-  double R[9];
-  quat_to_mat(r.w, r.x, r.y, r.z, R);
-  const double* g = geom_rec_all + G_STRIDE * d->static_geom[s];
-  for (int i = 0; i < 3; ++i)
-    rec[S_OBBC + i] = ((R[3 * i] * g[G_OBB_C] + R[3 * i + 1] * g[G_OBB_C + 1]) + R[3 * i + 2] * g[G_OBB_C + 2]) + T[9 + i];
-  for (int k = 0; k < 9; ++k) rec[S_R + k] = R[k];
-}
-
-// phase A LDS bytes per thread: records + FK save slots + survivor words + queue share
-size_t cull_lds_per_thread(int n_moving, int n_saves, int W) {
-  return (size_t)std::max(n_moving, 1) * 3 * sizeof(float) + (size_t)std::max(n_saves - kRegSaves, 0) * 12 * sizeof(float) +
-         (size_t)W * sizeof(uint32_t) + (kQueue / 64) * sizeof(uint32_t);
-}
-
-// block size that keeps the most waves resident per CU (160 KiB of LDS),
-// ties to the larger block; -1 if even one wave does not fit
-int choose_block(size_t per_thread, size_t* lds) {
-  int best = -1, best_waves = 0;
-  for (int b : {256, 128, 64}) {
-    const size_t bytes = per_thread * b;
-    if (bytes > 160 * 1024) continue;
-    const int waves = std::min(32, (int)(160 * 1024 / bytes) * (b / 64));
-    if (waves > best_waves) {
-      best_waves = waves;
-      best = b;
-    }
-  }
-  if (best > 0) *lds = per_thread * best;
-  return best;
-}
-
-void free_workspace(mpg_world::Workspace& ws) {
-  for (uint32_t* p : {ws.surv, ws.cnt, ws.seg_len, ws.seg_start, ws.prefix, ws.cand})
-    if (p) hipFree(p);
-  if (ws.rq) hipFree(ws.rq);
-  if (ws.sc) hipFree(ws.sc);
-  if (ws.links) hipFree(ws.links);
-  ws = mpg_world::Workspace{};
-}
-
-// drops the state kept for caller stream s (its workspace, its side stream
-// and the side stream's workspace); the device is synchronised first, so no
-// queued kernel still uses the buffers.  Caller holds ws_mu.
-void release_stream_locked(mpg_world* w, hipStream_t s) {
-  const auto wi = w->ws.find(s);
-  const auto si = w->sides.find(s);
-  if (wi == w->ws.end() && si == w->sides.end()) return;
-  hipDeviceSynchronize();
-  if (wi != w->ws.end()) {
-    free_workspace(wi->second);
-    w->ws.erase(wi);
-  }
-  if (si != w->sides.end()) {
-    const auto sw = w->ws.find(si->second.side);
-    if (sw != w->ws.end()) {
-      free_workspace(sw->second);
-      w->ws.erase(sw);
-    }
-    hipStreamDestroy(si->second.side);
-    hipEventDestroy(si->second.fork);
-    hipEventDestroy(si->second.join);
-    w->sides.erase(si);
-  }
-}
-
-// evicts the least recently used caller stream's state when a new stream
-// would exceed kMaxStreamState (side-stream workspaces are owned by their
-// caller stream's entry).  Caller holds ws_mu.
-void evict_streams_locked(mpg_world* w) {
-  std::map<hipStream_t, uint64_t> callers;
-  for (auto& kv : w->ws) callers[kv.first] = kv.second.last;
-  for (auto& kv : w->sides) {
-    callers.erase(kv.second.side);
-    uint64_t& t = callers[kv.first];
-    t = std::max(t, kv.second.last);
-  }
-  for (auto& kv : w->busy)
-    if (kv.second > 0) callers.erase(kv.first);  // in use by a call: not evictable
-  size_t pinned = 0;
-  for (auto& kv : w->busy) pinned += kv.second > 0;
-  while (!callers.empty() && callers.size() + pinned >= mpg_world::kMaxStreamState) {
-    auto lru = callers.begin();
-    for (auto it = callers.begin(); it != callers.end(); ++it)
-      if (it->second < lru->second) lru = it;
-    release_stream_locked(w, lru->first);
-    callers.erase(lru);
-  }
-}
-
-// keeps a caller stream's state (workspace, side stream) from eviction for
-// the duration of one call
-struct StreamPin {
-  mpg_world* w;
-  hipStream_t s;
-  StreamPin(mpg_world* w_, hipStream_t s_) : w(w_), s(s_) {
-    std::lock_guard<std::mutex> lk(w->ws_mu);
-    ++w->busy[s];
-  }
-  ~StreamPin() {
-    std::lock_guard<std::mutex> lk(w->ws_mu);
-    if (--w->busy[s] <= 0) w->busy.erase(s);
-  }
-};
-
-bool is_side_stream_locked(const mpg_world* w, hipStream_t s) {
-  for (auto& kv : w->sides)
-    if (kv.second.side == s) return true;
-  return false;
-}
-
-int get_workspace(mpg_world* w, hipStream_t s, long long want, mpg_world::Workspace** out) {
-  std::lock_guard<std::mutex> lk(w->ws_mu);
-  if (w->ws.find(s) == w->ws.end() && !is_side_stream_locked(w, s) && w->sides.find(s) == w->sides.end())
-    evict_streams_locked(w);
-  auto& ws = w->ws[s];
-  ws.last = ++w->ws_tick;
-  const long long np = std::max(w->dw.n_pairs, 1);
-  if (ws.cap < want) {
-    free_workspace(ws);
-    ws.last = w->ws_tick;
-    const long long tiles = (want + 63) / 64;
-    HIP_TRY(hipMalloc(&ws.surv, sizeof(uint32_t) * w->dw.W * want));
-    HIP_TRY(hipMalloc(&ws.cnt, sizeof(uint32_t) * np * tiles));
-    HIP_TRY(hipMalloc(&ws.seg_len, sizeof(uint32_t) * np));
-    HIP_TRY(hipMalloc(&ws.seg_start, sizeof(uint32_t) * np));
-    HIP_TRY(hipMalloc(&ws.prefix, sizeof(uint32_t) * (np + 4)));
-    HIP_TRY(hipMalloc(&ws.cand, sizeof(uint32_t) * np * want));
-    HIP_TRY(hipMalloc(&ws.rq, sizeof(float) * 4 * std::max(w->dw.n_moving, 1) * want));
-    HIP_TRY(hipMalloc(&ws.sc, sizeof(double) * 2 * std::max(w->dw.dof, 1) * want));
-    ws.cap = want;
-  }
-  *out = &ws;
-  return MPG_OK;
-}
-
-hipEvent_t prof_event(mpg_world* w) {
-  if (!w->ev_pool.empty()) {
-    hipEvent_t e = w->ev_pool.back();
-    w->ev_pool.pop_back();
-    return e;
-  }
-  hipEvent_t e = nullptr;
-  if (hipEventCreate(&e) != hipSuccess) return nullptr;
-  return e;
-}
-
-// records the start of a stage on `stream` when profiling is on
-struct StageTimer {
-  mpg_world* w;
-  hipStream_t s;
-  int stage;
-  hipEvent_t a = nullptr;
-  StageTimer(mpg_world* w_, hipStream_t s_, int st) : w(w_), s(s_), stage(st) {
-    if (!w->prof) return;
-    std::lock_guard<std::mutex> lk(w->prof_mu);
-    a = prof_event(w);
-    if (a) hipEventRecord(a, s);
-  }
-  void stop() {
-    if (!a) return;
-    std::lock_guard<std::mutex> lk(w->prof_mu);
-    hipEvent_t b = prof_event(w);
-    if (!b) return;
-    hipEventRecord(b, s);
-    w->marks.push_back({stage, a, b});
-    a = nullptr;
-  }
-  ~StageTimer() { stop(); }
-};
-
-struct ContactOut {
-  double *depth, *normal, *pos;  // [n*P], [n*P*3], [n*P*3]
-};
-
-template <bool FROM_POSES>
-int launch_collide(mpg_world* w, const double* in, long long n, uint8_t* flags, uint32_t* masks, hipStream_t stream,
-                   const ContactOut* co = nullptr) {
-  if (n == 0) return MPG_OK;
-  StreamPin pin(w, stream);
-  const long long chunk = std::min<long long>(n, w->max_chunk);
-  mpg_world::Workspace* ws = nullptr;
-  int rc = get_workspace(w, stream, chunk, &ws);
-  if (rc) return rc;
-  const size_t row = FROM_POSES ? (size_t)w->dw.n_links * 7 : (size_t)w->dw.dof;
-  for (long long off = 0; off < n; off += chunk) {
-    const long long m = std::min(chunk, n - off);
-    const double* qin = in + off * row;
-    uint8_t* fl = flags + off;
-    uint32_t* mk = masks ? masks + off * w->dw.W : nullptr;
-    const unsigned grid = (unsigned)((m + w->block - 1) / w->block);
-    const int n_tiles = (int)((m + 63) / 64);
-    StageTimer t_cull(w, stream, MPG_STAGE_CULL);
-    if (w->prof) w->prof_cfg += m;
-    HIP_TRY(hipMemsetAsync(ws->cnt, 0, sizeof(uint32_t) * std::max(w->dw.n_pairs, 1) * (size_t)n_tiles, stream));
-    switch (w->block) {
-      case 256:
-        hipLaunchKernelGGL((cull_kernel<256, FROM_POSES>), dim3(grid), dim3(256), w->lds_bytes, stream, w->dw, qin,
-                           m, fl, mk, ws->surv, ws->rq, ws->sc, ws->cap, ws->cnt, n_tiles);
-        break;
-      case 128:
-        hipLaunchKernelGGL((cull_kernel<128, FROM_POSES>), dim3(grid), dim3(128), w->lds_bytes, stream, w->dw, qin,
-                           m, fl, mk, ws->surv, ws->rq, ws->sc, ws->cap, ws->cnt, n_tiles);
-        break;
-      default:
-        hipLaunchKernelGGL((cull_kernel<64, FROM_POSES>), dim3(grid), dim3(64), w->lds_bytes, stream, w->dw, qin, m,
-                           fl, mk, ws->surv, ws->rq, ws->sc, ws->cap, ws->cnt, n_tiles);
-        break;
-    }
-    HIP_TRY(hipGetLastError());
-    t_cull.stop();
-    StageTimer t_bucket(w, stream, MPG_STAGE_BUCKET);
-    const long long tw = (long long)n_tiles * w->dw.W;  // one wave per (word, tile)
-    const unsigned gb = (unsigned)((tw + 3) / 4);
-    if (w->dw.n_pairs > 0) {
-      hipLaunchKernelGGL(pair_scan_kernel, dim3(w->dw.n_pairs), dim3(1024), 0, stream, ws->cnt, n_tiles, ws->seg_len);
-      HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(chunk_scan_kernel, dim3(1), dim3(256), 0, stream, ws->seg_len, w->dw.n_pairs, ws->seg_start,
-                       ws->prefix, w->prof ? w->prof_units : nullptr, (uint32_t)(4 * w->narrow_blocks));
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(scatter_kernel, dim3(gb), dim3(256), 0, stream, ws->surv, m, ws->cap, w->dw.n_pairs, w->dw.W,
-                       n_tiles, ws->cnt, ws->seg_start, ws->cand);
-    HIP_TRY(hipGetLastError());
-    t_bucket.stop();
-    StageTimer t_narrow(w, stream, MPG_STAGE_NARROW);
-    // persistent narrow phase: enough waves to fill the chip, fewer for tiny batches
-    const long long want_waves = (m * std::max(w->dw.n_pairs, 1) + kTaskMin - 1) / kTaskMin;
-    const unsigned nb = (unsigned)std::max<long long>(1, std::min<long long>(w->narrow_blocks, (want_waves + 3) / 4));
-    hipLaunchKernelGGL((narrow_kernel<FROM_POSES>), dim3(nb), dim3(256), 0, stream, w->dw, qin, ws->seg_len,
-                       ws->seg_start, ws->prefix, ws->cand, fl, mk, ws->prefix + w->dw.n_pairs + 1, ws->sc);
-    HIP_TRY(hipGetLastError());
-    if (w->any_closed_form) {
-      hipLaunchKernelGGL((closed_form_kernel<FROM_POSES, CLS_CLOSED>), dim3(w->narrow_blocks), dim3(256), 0, stream,
-                         w->dw, qin, ws->seg_len, ws->seg_start, ws->prefix, ws->cand, fl, mk, ws->sc);
-      HIP_TRY(hipGetLastError());
-    }
-    if (w->any_octree) {
-      hipLaunchKernelGGL((closed_form_kernel<FROM_POSES, CLS_OCTREE>), dim3(w->narrow_blocks), dim3(256), 0, stream,
-                         w->dw, qin, ws->seg_len, ws->seg_start, ws->prefix, ws->cand, fl, mk, ws->sc);
-      HIP_TRY(hipGetLastError());
-    }
-    if (w->any_mesh) {
-      hipLaunchKernelGGL((closed_form_kernel<FROM_POSES, CLS_MESH>), dim3(w->narrow_blocks), dim3(256), 0, stream,
-                         w->dw, qin, ws->seg_len, ws->seg_start, ws->prefix, ws->cand, fl, mk, ws->sc);
-      HIP_TRY(hipGetLastError());
-    }
-    if (w->any_gjk) {
-      hipLaunchKernelGGL((closed_form_kernel<FROM_POSES, CLS_GJK>), dim3(w->narrow_blocks), dim3(256), 0, stream,
-                         w->dw, qin, ws->seg_len, ws->seg_start, ws->prefix, ws->cand, fl, mk, ws->sc);
-      HIP_TRY(hipGetLastError());
-    }
-    if (co) {  // penetration info of the reported pairs (enable_contact)
-      const size_t P = (size_t)w->dw.n_pairs;
-      HIP_TRY(hipMemsetAsync(co->depth + off * P, 0, sizeof(double) * m * P, stream));
-      HIP_TRY(hipMemsetAsync(co->normal + off * P * 3, 0, sizeof(double) * m * P * 3, stream));
-      HIP_TRY(hipMemsetAsync(co->pos + off * P * 3, 0, sizeof(double) * m * P * 3, stream));
-      hipLaunchKernelGGL((contact_kernel<FROM_POSES>), dim3(nb), dim3(256), 0, stream, w->dw, qin, ws->seg_len,
-                         ws->seg_start, ws->prefix, ws->cand, mk, ws->sc, co->depth + off * P, co->normal + off * P * 3,
-                         co->pos + off * P * 3);
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  return MPG_OK;
-}
-
-int ensure_staging(mpg_world* w, size_t ncfg, size_t nout) {
-  if (ncfg > w->cap_cfg) {
-    hipFree(w->d_q);
-    hipFree(w->d_flags);
-    hipFree(w->d_masks);
-    w->d_q = nullptr;
-    w->d_flags = nullptr;
-    w->d_masks = nullptr;
-    HIP_TRY(hipMalloc(&w->d_q, sizeof(double) * std::max<size_t>(1, ncfg * std::max(w->dw.dof, 1))));
-    HIP_TRY(hipMalloc(&w->d_flags, std::max<size_t>(1, ncfg)));
-    HIP_TRY(hipMalloc(&w->d_masks, sizeof(uint32_t) * std::max<size_t>(1, ncfg * w->dw.W)));
-    w->cap_cfg = ncfg;
-  }
-  if (nout > w->cap_out) {
-    hipFree(w->d_out);
-    w->d_out = nullptr;
-    HIP_TRY(hipMalloc(&w->d_out, sizeof(double) * nout));
-    w->cap_out = nout;
-  }
-  return MPG_OK;
-}
-
-// the host pipeline's slot buffers (not its stream and events)
-void free_ring(mpg_world* w) {
-  auto& R = w->ring;
-  for (int j = 0; j < mpg_world::kRing; ++j) {
-    if (R.d_in[j]) hipFree(R.d_in[j]);
-    if (R.d_fl[j]) hipFree(R.d_fl[j]);
-    if (R.d_mk[j]) hipFree(R.d_mk[j]);
-    if (R.d_bcnt[j]) hipFree(R.d_bcnt[j]);
-    if (R.h_fl[j]) hipHostFree(R.h_fl[j]);
-    if (R.h_mk[j]) hipHostFree(R.h_mk[j]);
-    if (R.h_bcnt[j]) hipHostFree(R.h_bcnt[j]);
-    R.h_bcnt[j] = nullptr;
-    R.h_fl_d[j] = nullptr;
-    R.h_bcnt_d[j] = nullptr;
-    R.d_in[j] = nullptr;
-    R.d_fl[j] = nullptr;
-    R.d_mk[j] = nullptr;
-    R.d_bcnt[j] = nullptr;
-    R.h_fl[j] = nullptr;
-    R.h_mk[j] = nullptr;
-    R.h_mk_d[j] = nullptr;
-  }
-  R.cap = 0;
-  R.in_cap = 0;
-}
-
-// World-owned scratch (distance, motion validation) used by calls on any
-// stream: a call's work waits for the previous call's (`last`, whatever its
-// stream), and a buffer is freed to grow only after that work has finished,
-// so two host threads on two streams never run over the same buffers at once
-// (calls on one world are serialised on the device; their enqueueing already
-// is, by the world's mutex).  Caller holds the scratch's mutex.
-int scratch_begin(hipEvent_t& last, hipStream_t s) {
-  if (!last) HIP_TRY(hipEventCreateWithFlags(&last, hipEventDisableTiming));
-  else HIP_TRY(hipStreamWaitEvent(s, last, 0));
-  return MPG_OK;
-}
-int scratch_grow(hipEvent_t last, void** p, size_t& cap, size_t want) {
-  if (cap >= want) return MPG_OK;
-  if (*p) {
-    if (last) HIP_TRY(hipEventSynchronize(last));
-    HIP_TRY(hipFree(*p));
-  }
-  *p = nullptr;
-  cap = 0;
-  HIP_TRY(hipMalloc(p, want));
-  cap = want;
-  return MPG_OK;
-}
-
-// slots of `cap` configurations with `row` input doubles each (grow-only)
-int ensure_ring(mpg_world* w, size_t cap, size_t row) {
-  auto& R = w->ring;
-  if (!R.h2d) {
-    HIP_TRY(hipStreamCreateWithFlags(&R.h2d, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&R.side, hipStreamNonBlocking));
-    for (int j = 0; j < mpg_world::kRing; ++j) {
-      HIP_TRY(hipEventCreateWithFlags(&R.e_in[j], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&R.e_done[j], hipEventDisableTiming));
-    }
-  }
-  const size_t in = cap * std::max<size_t>(row, 1);
-  if (cap <= R.cap && in <= R.in_cap) return MPG_OK;
-  cap = std::max(cap, R.cap);
-  const size_t in_cap = std::max(in, R.in_cap);
-  free_ring(w);
-  const size_t W = (size_t)std::max(w->dw.W, 1);
-  for (int j = 0; j < mpg_world::kRing; ++j) {
-    HIP_TRY(hipMalloc(&R.d_in[j], sizeof(double) * in_cap));
-    HIP_TRY(hipMalloc(&R.d_fl[j], cap));
-    HIP_TRY(hipMalloc(&R.d_mk[j], sizeof(uint32_t) * W * cap));
-    HIP_TRY(hipMalloc(&R.d_bcnt[j], sizeof(uint32_t) * ((cap + kPackCfg - 1) / kPackCfg)));
-    HIP_TRY(hipHostMalloc((void**)&R.h_fl[j], cap, hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void**)&R.h_fl_d[j], R.h_fl[j], 0));
-    HIP_TRY(hipHostMalloc((void**)&R.h_mk[j], sizeof(uint32_t) * W * cap, hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void**)&R.h_mk_d[j], R.h_mk[j], 0));
-    HIP_TRY(hipHostMalloc((void**)&R.h_bcnt[j], sizeof(uint32_t) * ((cap + kPackCfg - 1) / kPackCfg),
-                          hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void**)&R.h_bcnt_d[j], R.h_bcnt[j], 0));
-  }
-  R.cap = cap;
-  R.in_cap = in_cap;
-  return MPG_OK;
-}
+#include "mpg_snapshot_host.h"
+#include "mpg_streams_host.h"
 
 }  // namespace
 
 extern "C" {
 
-const char* mpg_last_error(void) { return g_last_error.c_str(); }
-
-int mpg_fcl_bvh_build(const double* vertices, int32_t n_vertices, const int32_t* triangles, int32_t n_triangles,
-                      double* boxes, int32_t* links, int32_t* leaf_order) {
-  if (n_triangles <= 0 || !vertices || !triangles || !boxes || !links || !leaf_order)
-    return set_error(MPG_E_INVALID, "mpg_fcl_bvh_build: empty mesh or NULL buffer");
-  for (int64_t i = 0; i < 3 * (int64_t)n_triangles; ++i)
-    if (triangles[i] < 0 || triangles[i] >= n_vertices) return set_error(MPG_E_INVALID, "triangle vertex out of range");
-  FclBvh B;
-  B.box.resize(FB_STRIDE);
-  B.link.resize(3);
-  std::vector<int> prim((size_t)n_triangles);
-  for (int t = 0; t < n_triangles; ++t) prim[t] = t;
-  fcl_bvh_node(B, vertices, triangles, prim, 0, 0, n_triangles, 0);
-  std::copy(B.box.begin(), B.box.end(), boxes);
-  std::copy(B.link.begin(), B.link.end(), links);
-  std::copy(prim.begin(), prim.end(), leaf_order);
-  return (int)(B.link.size() / 3);
-}
-
-int mpg_last_error_copy(char* buf, size_t size) {
-  const size_t len = g_last_error.size();
-  if (buf && size > 0) {
-    const size_t k = std::min(len, size - 1);
-    std::memcpy(buf, g_last_error.data(), k);
-    buf[k] = '\0';
-  }
-  return (int)std::min<size_t>(len, 0x7fffffff);
-}
-
-const char* mpg_version(void) { return "mpgpu 0.2 (gfx950, fp64, libccd-MPR)"; }
-
-int mpg_device_count(int* count) {
-  if (!count) return set_error(MPG_E_INVALID, "count is NULL");
-  HIP_TRY(hipGetDeviceCount(count));
-  return MPG_OK;
-}
-
-int mpg_profile_enable(mpg_world* w, int enable) {
-  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
-  HIP_TRY(hipSetDevice(w->device));
-  std::lock_guard<std::mutex> lk(w->prof_mu);
-  if (enable && !w->prof_units) {
-    HIP_TRY(hipMalloc(&w->prof_units, sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(w->prof_units, 0, sizeof(unsigned long long)));
-  }
-  w->prof = enable != 0;
-  return MPG_OK;
-}
-
-int mpg_profile_read(mpg_world* w, double* ms, int64_t* launches, int64_t* units, int n_stages) {
-  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
-  HIP_TRY(hipSetDevice(w->device));
-  std::lock_guard<std::mutex> lk(w->prof_mu);
-  unsigned long long cand = 0;
-  if (w->prof_units) {
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(&cand, w->prof_units, sizeof(cand), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(w->prof_units, 0, sizeof(cand)));
-  }
-  const int64_t u[MPG_NUM_STAGES] = {w->prof_cfg, w->prof_cfg, (int64_t)cand};
-  w->prof_cfg = 0;
-  for (auto& mk : w->marks) {
-    HIP_TRY(hipEventSynchronize(mk.b));
-    float t = 0.f;
-    HIP_TRY(hipEventElapsedTime(&t, mk.a, mk.b));
-    w->prof_ms[mk.stage] += t;
-    w->prof_n[mk.stage] += 1;
-    w->ev_pool.push_back(mk.a);
-    w->ev_pool.push_back(mk.b);
-  }
-  w->marks.clear();
-  for (int k = 0; k < MPG_NUM_STAGES; ++k) {
-    if (k < n_stages) {
-      if (ms) ms[k] = w->prof_ms[k];
-      if (launches) launches[k] = w->prof_n[k];
-      if (units) units[k] = u[k];
-    }
-    w->prof_ms[k] = 0.0;
-    w->prof_n[k] = 0;
-  }
-  return MPG_OK;
-}
-
-int mpg_latency_server_stats(mpg_world* w, int64_t* served, int64_t* starts, int64_t* fallbacks, int32_t* state) {
-  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
-  if (served) *served = w->srv_served;
-  if (starts) *starts = w->srv_starts;
-  if (fallbacks) *fallbacks = w->srv_fallbacks;
-  if (state) *state = !(w->srv_mode && w->srv_ok) ? 0 : w->srv_broken ? 2 : 1;
-  return MPG_OK;
-}
-
-int mpg_synchronize(int device) {
-  HIP_TRY(hipSetDevice(device));
-  HIP_TRY(hipDeviceSynchronize());
-  return MPG_OK;
-}
-
-int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
-  if (!out) return set_error(MPG_E_INVALID, "out is NULL");
-  *out = nullptr;
-  int rc = validate(d_in);
-  if (rc) return rc;
-  // free frames: the kinematic build below (chains, broad-phase program,
-  // latency records) sees them as links fixed to the universe at their initial
-  // pose; what the kernels read for them is the pose input
-  mpg_world_desc dd = *d_in;
-  std::vector<int32_t> lp_kin(dd.link_parent, dd.link_parent + dd.n_links);
-  int n_free = 0;
-  for (int32_t& p : lp_kin)
-    if (p == MPG_LINK_FREE) {
-      p = 0;
-      ++n_free;
-    }
-  if (n_free) dd.link_parent = lp_kin.data();
-  const mpg_world_desc* d = &dd;
-  std::vector<double> geom_rec((size_t)G_STRIDE * std::max(d->n_geoms, 1), 0.0);
-  for (int g = 0; g < d->n_geoms; ++g) geom_record(d, g, geom_rec.data() + (size_t)G_STRIDE * g);
-  std::vector<double> obb((size_t)7 * std::max(d->n_geoms, 1), 0.0);
-  for (int g = 0; g < d->n_geoms; ++g) {
-    const double* r = geom_rec.data() + (size_t)G_STRIDE * g;
-    for (int k = 0; k < 3; ++k) obb[7 * g + k] = r[G_OBB_C + k];
-    for (int k = 0; k < 3; ++k) obb[7 * g + 3 + k] = r[G_OBB_E + k];
-    obb[7 * g + 6] = r[G_RADIUS];
-  }
-  BpProgram bpp;
-  bp_build(d, obb, bpp);
-  size_t lds = 0;
-  const int W = std::max(1, (d->n_pairs + 31) / 32);
-  const int block = choose_block(cull_lds_per_thread(d->n_moving, bpp.n_saves, W), &lds);
-  if (block < 0) return set_error(MPG_E_UNSUPPORTED, "world too large for the phase-A LDS budget");
-  HIP_TRY(hipSetDevice(device));
-
-  std::vector<double> static_rec((size_t)S_STRIDE * std::max(d->n_static, 1), 0.0);
-  for (int s = 0; s < d->n_static; ++s) static_record(d, s, geom_rec.data(), static_rec.data() + (size_t)S_STRIDE * s);
-  // hulls in AoSoA-4 groups, padded with copies of the hull's first vertex
-  std::vector<int> gstart(std::max(d->n_geoms, 1), 0), ngroups(std::max(d->n_geoms, 1), 0);
-  std::vector<double> hull;
-  std::vector<int> cbase(std::max(d->n_geoms, 1), -1), geom_nbr(std::max(d->n_geoms, 1), -1), hull_nbr, wcell_end, wcell_end2, wcell_pre;
-  std::vector<double> cell_rec, cell_ovf, wcell_rec, wcell_ovf, wcell_aux, nbr_ent;
-  const int walk_subk =
-      std::getenv("MPG_WALK_SUBK") ? std::max(1, std::min(8, std::atoi(std::getenv("MPG_WALK_SUBK")))) : kSubK;
-  int big_words = 0;  // walk hulls above kMaxWalkVerts: the widest visited set
-  for (int g = 0; g < d->n_geoms; ++g) {
-    if (d->geom_type[g] != MPG_GEOM_CONVEX) continue;
-    const double* Vg = d->vertices + 3 * (size_t)d->geom_vertex_start[g];
-    const int nvg = d->geom_vertex_count[g];
-    // FCL 0.7.0 Convex: neighbour walk for > 32 vertices with valid faces
-    std::vector<int> enc;
-    const int nf = (int)d->geom_param[4 * g + 1];
-    bool walk = nf > 0 && fcl_convex_neighbors(nvg, d->convex_face + (int64_t)d->geom_param[4 * g], nf, enc);
-#ifdef MPG_DIAG  // ablation builds only (changes results)
-    if (std::getenv("MPG_DEBUG_NO_WALK")) walk = false;
-#endif
-    if (walk) {
-      geom_nbr[g] = (int)(hull_nbr.size() / 2);
-      if (nvg > kMaxWalkVerts) big_words = std::max(big_words, (nvg + 63) / 64);  // pooled visited set
-      for (int i = 0; i < nvg; ++i) {
-        const int st = enc[i], cnt = enc[st];
-        hull_nbr.push_back((int)(nbr_ent.size() / 4));
-        hull_nbr.push_back(cnt);
-        for (int k = 1; k <= cnt; ++k) {
-          const int vi = enc[st + k];
-          nbr_ent.insert(nbr_ent.end(), {Vg[3 * vi], Vg[3 * vi + 1], Vg[3 * vi + 2], (double)vi});
-        }
-      }
-      const size_t r0 = wcell_rec.size();
-      if (build_walk_cells(Vg, nvg, enc.data(), walk_subk, wcell_rec, wcell_ovf, wcell_aux, wcell_end, wcell_end2, wcell_pre))
-        cbase[g] = (int)(r0 / kCellRec);
-    } else {
-      std::vector<uint32_t> cstart;
-      std::vector<double> cpts;
-      if (build_hull_cells(Vg, nvg, cstart, cpts)) {
-        cbase[g] = (int)(cell_rec.size() / kCellRec);
-        pack_cell_records(cstart.data(), cpts.data(), cell_rec, cell_ovf);
-      }
-    }
-    const double* V = d->vertices + 3 * (size_t)d->geom_vertex_start[g];
-    const int nv = d->geom_vertex_count[g], ng = (nv + 3) / 4;
-    gstart[g] = (int)(hull.size() / 12);
-    ngroups[g] = ng;
-    for (int q = 0; q < ng; ++q)
-      for (int k = 0; k < 3; ++k)
-        for (int l = 0; l < 4; ++l) {
-          const int i = 4 * q + l < nv ? 4 * q + l : 0;
-          hull.push_back(V[3 * i + k]);
-        }
-  }
-  for (int g = 0; g < d->n_geoms; ++g) {  // TriangleP: its three vertices as one group (supportTriangle reads them)
-    if (d->geom_type[g] != MPG_GEOM_TRIANGLE) continue;
-    const double* V = d->vertices + 3 * (size_t)d->geom_vertex_start[g];
-    gstart[g] = (int)(hull.size() / 12);
-    ngroups[g] = 1;
-    for (int k = 0; k < 3; ++k)
-      for (int l = 0; l < 4; ++l) hull.push_back(V[3 * (l < 3 ? l : 0) + k]);
-  }
-  if (hull.empty()) hull.assign(12, 0.0);
-  if (cell_rec.empty()) cell_rec.assign(kCellRec, 0.0);
-  if (cell_ovf.empty()) cell_ovf.assign(4, 0.0);
-  if (hull_nbr.empty()) hull_nbr.assign(2, 0);
-  if (nbr_ent.empty()) nbr_ent.assign(4, 0.0);
-  if (wcell_rec.empty()) wcell_rec.assign(kCellRec, 0.0);
-  if (wcell_ovf.empty()) wcell_ovf.assign(4, 0.0);
-  if (wcell_aux.empty()) wcell_aux.assign(kWalkAux, 0.0);
-  if (wcell_end.empty()) wcell_end.assign(1, -1);
-  if (wcell_end2.empty()) wcell_end2.assign(1, -1);
-  if (wcell_pre.empty()) wcell_pre.assign(kWalkPre, 0);
-  // octrees: leaf boxes + a uniform grid per octree geometry (cells of at
-  // least the largest leaf, <= 64 per axis); a leaf is listed in every cell
-  // its box overlaps
-  // BVH meshes: per triangle its vertices (mesh frame) and AABB (TR_*), in
-  // cluster order
-  std::vector<double> mesh_tri((size_t)TR_STRIDE * std::max<int64_t>(d->n_mesh_triangles, 1), 0.0);
-  std::vector<double> mesh_node;
-  std::vector<int> mesh_link, mesh_tree(2 * (size_t)std::max(d->n_geoms, 1), 0);
-  for (int g = 0; g < d->n_geoms; ++g) {
-    if (d->geom_type[g] != MPG_GEOM_MESH) continue;
-    const double* V = d->vertices + 3 * (size_t)d->geom_vertex_start[g];
-    const int64_t t0 = (int64_t)d->geom_param[4 * g], tn = (int64_t)d->geom_param[4 * g + 1];
-    std::vector<double> rec((size_t)TR_STRIDE * std::max<int64_t>(tn, 1), 0.0);
-    for (int64_t t = 0; t < tn; ++t) {
-      double* r = rec.data() + (size_t)TR_STRIDE * t;
-      for (int v = 0; v < 3; ++v)
-        for (int k = 0; k < 3; ++k) r[TR_P + 3 * v + k] = V[3 * (size_t)d->mesh_triangle[3 * (t0 + t) + v] + k];
-      for (int k = 0; k < 3; ++k) {
-        r[TR_LO + k] = std::min(r[TR_P + k], std::min(r[TR_P + 3 + k], r[TR_P + 6 + k]));
-        r[TR_HI + k] = std::max(r[TR_P + k], std::max(r[TR_P + 3 + k], r[TR_P + 6 + k]));
-      }
-      r[TR_ID] = (double)t;  // the triangle's index in the mesh (its leaf position: tri_pos)
-    }
-    std::vector<int> order((size_t)tn);
-    for (int64_t t = 0; t < tn; ++t) order[t] = (int)t;
-    // clusters of <= max(8, T / 64) triangles: ~64 cluster boxes per mesh
-    mesh_tree[2 * g] = (int)(mesh_link.size() / 2);
-    mesh_build_clusters(rec, order, 0, (int)tn, std::max<int>(8, (int)((tn + 63) / 64)), (int)t0, mesh_node, mesh_link);
-    mesh_tree[2 * g + 1] = (int)(mesh_link.size() / 2) - mesh_tree[2 * g];
-    for (int64_t k = 0; k < tn; ++k)
-      std::copy(rec.begin() + (size_t)TR_STRIDE * order[k], rec.begin() + (size_t)TR_STRIDE * (order[k] + 1),
-                mesh_tri.begin() + (size_t)TR_STRIDE * (t0 + k));
-  }
-  if (mesh_node.empty()) mesh_node.assign(6, 0.0);
-  if (mesh_link.empty()) mesh_link.assign(2, 0);
-  // FCL's BVHModel<OBBRSS> trees (the traversal gates of mesh pairs) and the
-  // shapes' computeBV OBBs
-  FclBvh fbvh;
-  std::vector<int> fb_root(std::max(d->n_geoms, 1), -1), tri_pos(std::max<int64_t>(d->n_mesh_triangles, 1), 0);
-  std::vector<double> sobb((size_t)FB_STRIDE * std::max(d->n_geoms, 1), 0.0);
-  for (int g = 0; g < d->n_geoms; ++g) {
-    fcl_shape_obb(d, g, sobb.data() + (size_t)FB_STRIDE * g);
-    if (d->geom_type[g] != MPG_GEOM_MESH) continue;
-    const int64_t t0 = (int64_t)d->geom_param[4 * g], tn = (int64_t)d->geom_param[4 * g + 1];
-    if (tn <= 0) continue;
-    const int base = (int)(fbvh.link.size() / 3);
-    fb_root[g] = base;
-    fbvh.box.resize(fbvh.box.size() + FB_STRIDE);
-    fbvh.link.resize(fbvh.link.size() + 3);
-    std::vector<int> prim((size_t)tn);
-    for (int64_t t = 0; t < tn; ++t) prim[t] = (int)t;
-    fbvh.max_depth = 0;
-    fcl_bvh_node(fbvh, d->vertices + 3 * (size_t)d->geom_vertex_start[g], d->mesh_triangle + 3 * t0, prim, 0, 0,
-                 (int)tn, base);
-    if (fbvh.max_depth > kFclMaxDepth)
-      return set_error(MPG_E_UNSUPPORTED, "BVH mesh geometry " + std::to_string(g) + ": FCL's mean-split tree is " +
-                                              std::to_string(fbvh.max_depth) + " levels deep (the device gates descend at most " +
-                                              std::to_string(kFclMaxDepth) + ")");
-    for (int64_t k = 0; k < tn; ++k) tri_pos[t0 + prim[k]] = (int)k;
-  }
-  if (fbvh.box.empty()) {
-    fbvh.box.assign(FB_STRIDE, 0.0);
-    fbvh.link.assign(3, 0);
-  }
-  std::vector<double> oct_leaf(6 * (size_t)std::max<int64_t>(d->n_octree_leaves, 1), 0.0);
-  if (d->n_octree_leaves > 0) std::copy(d->octree_leaf, d->octree_leaf + 6 * d->n_octree_leaves, oct_leaf.begin());
-  // each leaf's path down FCL's octree: getRootBV (delta = 2^16 resolution /
-  // 2) halved by computeChildBV until the leaf box (the leaves were cut that
-  // way: host octree.cpp collect, octomap's 16 levels)
-  std::vector<uint64_t> oct_path(std::max<int64_t>(d->n_octree_leaves, 1), 0);
-  std::vector<int> oct_depth(std::max<int64_t>(d->n_octree_leaves, 1), 0);
-  for (int g = 0; g < d->n_geoms; ++g) {
-    if (d->geom_type[g] != MPG_GEOM_OCTREE) continue;
-    const int64_t l0 = (int64_t)d->geom_param[4 * g], ln = (int64_t)d->geom_param[4 * g + 1];
-    const double delta = (double)(1 << 16) * d->geom_param[4 * g + 2] / 2;
-    for (int64_t l = l0; l < l0 + ln; ++l) {
-      const double* L = d->octree_leaf + 6 * l;
-      double lo[3] = {-delta, -delta, -delta}, hi[3] = {delta, delta, delta};
-      uint64_t code = 0;
-      int depth = 0;
-      while (!(lo[0] == L[0] && lo[1] == L[1] && lo[2] == L[2] && hi[0] == L[3] && hi[1] == L[4] && hi[2] == L[5])) {
-        if (++depth > 16)
-          return set_error(MPG_E_INVALID, "octree geometry " + std::to_string(g) + ": leaf " + std::to_string(l - l0) +
-                                              " is not a box of FCL's root-BV halving (getRootBV / computeChildBV)");
-        int ci = 0;
-        for (int k = 0; k < 3; ++k) {
-          const double mid = (lo[k] + hi[k]) * 0.5;
-          if (L[k] >= mid) {
-            ci |= 1 << k;
-            lo[k] = mid;
-          } else {
-            hi[k] = mid;
-          }
-        }
-        code = (code << 3) | (uint64_t)ci;
-      }
-      oct_path[l] = code;
-      oct_depth[l] = depth;
-    }
-  }
-  std::vector<double> oct_grid((size_t)OG_STRIDE * std::max(d->n_geoms, 1), 0.0);
-  std::vector<int> oct_cells, oct_list;
-  for (int g = 0; g < d->n_geoms; ++g) {
-    if (d->geom_type[g] != MPG_GEOM_OCTREE) continue;
-    const int64_t l0 = (int64_t)d->geom_param[4 * g], ln = (int64_t)d->geom_param[4 * g + 1];
-    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, big = 0.0;
-    for (int64_t i = l0; i < l0 + ln; ++i)
-      for (int k = 0; k < 3; ++k) {
-        const double a = d->octree_leaf[6 * i + k], b = d->octree_leaf[6 * i + 3 + k];
-        lo[k] = i == l0 ? a : std::min(lo[k], a);
-        hi[k] = i == l0 ? b : std::max(hi[k], b);
-        big = std::max(big, b - a);
-      }
-    double ext = 0.0;
-    for (int k = 0; k < 3; ++k) ext = std::max(ext, hi[k] - lo[k]);
-    const double cell = std::max({big, ext / 64.0, 1e-9});
-    int dims[3];
-    for (int k = 0; k < 3; ++k) dims[k] = std::max(1, std::min(66, (int)std::ceil((hi[k] - lo[k]) / cell) + 1));
-    double* og = oct_grid.data() + (size_t)OG_STRIDE * g;
-    for (int k = 0; k < 3; ++k) og[OG_ORIGIN + k] = lo[k];
-    og[OG_INV] = 1.0 / cell;
-    for (int k = 0; k < 3; ++k) og[OG_DIMS + k] = dims[k];
-    og[OG_CELL0] = (double)oct_cells.size();
-    const size_t nc = (size_t)dims[0] * dims[1] * dims[2];
-    std::vector<std::vector<int>> lists(nc);
-    // the same cell arithmetic as the device query, so a leaf is found from
-    // every cell a query box overlapping it can touch
-    auto cidx = [&](double v, int k) {
-      const double f = std::floor((v - lo[k]) * og[OG_INV]);
-      return f < 0.0 ? 0 : (f >= dims[k] ? dims[k] - 1 : (int)f);
-    };
-    for (int64_t i = l0; i < l0 + ln; ++i) {
-      const double* L = d->octree_leaf + 6 * i;
-      for (int x = cidx(L[0], 0); x <= cidx(L[3], 0); ++x)
-        for (int y = cidx(L[1], 1); y <= cidx(L[4], 1); ++y)
-          for (int z = cidx(L[2], 2); z <= cidx(L[5], 2); ++z)
-            lists[((size_t)x * dims[1] + y) * dims[2] + z].push_back((int)i);
-    }
-    for (size_t c = 0; c < nc; ++c) {
-      oct_cells.push_back((int)oct_list.size());
-      oct_list.insert(oct_list.end(), lists[c].begin(), lists[c].end());
-    }
-  }
-  oct_cells.push_back((int)oct_list.size());
-  if (oct_list.empty()) oct_list.push_back(0);
-  // per link: joints from the root to link_parent (chain FK in phase B)
-  std::vector<int> chain_start, chain_len, chain_joints;
-  for (int l = 0; l < d->n_links; ++l) {
-    std::vector<int> c;
-    for (int j = d->link_parent[l]; j > 0; j = d->joint_parent[j - 1]) c.push_back(j);
-    std::reverse(c.begin(), c.end());
-    chain_start.push_back((int)chain_joints.size());
-    chain_len.push_back((int)c.size());
-    chain_joints.insert(chain_joints.end(), c.begin(), c.end());
-  }
-  std::vector<int> allowed(std::max(d->n_pairs, 1), 0);
-  for (int p = 0; p < d->n_pairs; ++p) allowed[p] = d->pair_allowed ? (d->pair_allowed[p] != 0) : 0;
-  std::vector<int> pair_cf(std::max(d->n_pairs, 1), 0);
-  for (int p = 0; p < d->n_pairs; ++p) {
-    pair_cf[p] = closed_form_kind(d, d->pair_a[p], d->pair_b[p]);
-    // GST_INDEP: the shape pairs without a closed form run FCL's own GJK
-    // (GJKSolver_indep keeps the same closed forms as GJKSolver_libccd)
-    if (d->gjk_solver == MPG_GJK_INDEP && pair_cf[p] == CF_NONE) pair_cf[p] = CF_GJK;
-  }
-  // latency pair records (LR_*): one round of loads per wave instead of a
-  // chain of dependent snapshot lookups (pair -> object -> link -> chain ->
-  // joints -> geometry)
-  std::vector<double> lat_rec((size_t)LR_STRIDE * std::max(d->n_pairs, 1), 0.0);
-  bool lat_rec_ok = true;
-  for (int p = 0; p < d->n_pairs; ++p) {
-    double* R = lat_rec.data() + (size_t)LR_STRIDE * p;
-    const int ids[2] = {d->pair_a[p], d->pair_b[p]};
-    R[LR_ALLOWED] = allowed[p];
-    R[LR_CF] = pair_cf[p];
-    for (int s2 = 0; s2 < 2; ++s2) {
-      const int id = ids[s2];
-      const bool mv = id < d->n_moving;
-      const int g = mv ? d->moving_geom[id] : d->static_geom[id - d->n_moving];
-      R[s2 ? LR_GB : LR_GA] = g;
-      R[s2 ? LR_BM : LR_AM] = mv ? 1.0 : 0.0;
-      R[s2 ? LR_RB : LR_RA] = geom_rec[G_STRIDE * (size_t)g + G_RADIUS];
-      double* S = R + LR_SIDE + LS_STRIDE * s2;
-      for (int k = 0; k < 3; ++k) S[LS_OBBC + k] = geom_rec[G_STRIDE * (size_t)g + G_OBB_C + k];
-      if (!mv) {
-        std::copy(d->static_transform + 12 * (size_t)(id - d->n_moving),
-                  d->static_transform + 12 * (size_t)(id - d->n_moving) + 12, S + LS_OFF);
-        continue;
-      }
-      const int l = d->moving_link[id];
-      const int cl = chain_len[l];
-      if (cl > kLatChain) {
-        lat_rec_ok = false;
-        continue;
-      }
-      S[LS_CL] = cl;
-      std::copy(d->link_placement + 12 * (size_t)l, d->link_placement + 12 * (size_t)l + 12, S + LS_LINKPL);
-      std::copy(d->moving_offset + 12 * (size_t)id, d->moving_offset + 12 * (size_t)id + 12, S + LS_OFF);
-      for (int k = 0; k < cl; ++k) {
-        const int j = chain_joints[chain_start[l] + k] - 1;
-        double* J = S + LS_J + LJ_STRIDE * k;
-        J[0] = d->joint_type[j];
-        J[1] = d->joint_q_source[j];
-        J[2] = d->joint_q_const[j];
-        for (int i = 0; i < 3; ++i) J[3 + i] = d->joint_axis[3 * (size_t)j + i];
-        for (int i = 0; i < 12; ++i) J[6 + i] = d->joint_placement[12 * (size_t)j + i];
-      }
-    }
-  }
-  // phase-A schedule: non-allowed pairs grouped by their lower moving object
-  // ---- culling margins: pairs that can reach libccd MPR (directly, on octree
-  // leaves or on mesh triangles) keep everything within its false-hit reach
-  bool may_mpr = false;
-  for (int p = 0; p < d->n_pairs; ++p) {
-    if (allowed[p]) continue;
-    const int ta = obj_geom_type(d, d->pair_a[p]), tb = obj_geom_type(d, d->pair_b[p]);
-    const bool closed = pair_cf[p] != CF_NONE && cf_class(pair_cf[p]) == CLS_CLOSED;
-    const bool mesh_mesh = ta == MPG_GEOM_MESH && tb == MPG_GEOM_MESH;
-    may_mpr |= !closed && !mesh_mesh;
-  }
-  const double reach = kCcdFalseHitReach * (1.0 + 1e-3) + 1e-5;
-  float bp_margin = may_mpr ? (float)std::max((double)kBpMargin, reach) : kBpMargin;
-  // The travel of each prismatic joint: a move-group joint's value bound from
-  // its limits (kDefaultTravel when unbounded), a fixed joint's own value.
-  // A configuration whose prismatic value exceeds its bound is evaluated with
-  // every pair (the cull's coordinate bound below would not hold for it).
-  auto sq3 = [](const double* v) { return v[0] * v[0] + v[1] * v[1] + v[2] * v[2]; };
-  // prism_bound < 0: not a move-group prismatic joint (a [0, 0] limit is a real bound of 0)
-  std::vector<double> travel(std::max(d->n_joints, 1), 0.0), prism_bound(std::max(d->n_joints, 1), -1.0);
-  int n_prism = 0;
-  for (int j = 0; j < d->n_joints; ++j) {
-    const int t = d->joint_type[j];
-    if (t < MPG_JOINT_PX || t > MPG_JOINT_PRISMATIC_UNALIGNED) continue;
-    const double an = t == MPG_JOINT_PRISMATIC_UNALIGNED ? std::sqrt(sq3(d->joint_axis + 3 * j)) : 1.0;
-    if (d->joint_q_source[j] >= 0) {
-      double qb = kDefaultTravel;
-      if (d->joint_lower && d->joint_upper && std::isfinite(d->joint_lower[j]) && std::isfinite(d->joint_upper[j]))
-        qb = std::max(std::fabs(d->joint_lower[j]), std::fabs(d->joint_upper[j]));
-      prism_bound[j] = qb;
-      ++n_prism;
-      travel[j] = qb * an;
-    } else {
-      travel[j] = std::fabs(d->joint_q_const[j]) * an;
-    }
-  }
-  // the fp32 broad phase's rounding grows with coordinate magnitude: bound
-  // every world coordinate the cull computes (the chain's reach -- sum of the
-  // placement translations and prismatic travels, revolute joints cannot
-  // lengthen it --, moving offsets, static poses, geometry radii) and keep the
-  // margin above kFp32CullRel of it (kBpMargin covers a ~2 m world near the
-  // origin)
-  double reach_x = 0.0, geo_r = 0.0, stat_x = 0.0;
-  for (int j = 0; j < d->n_joints; ++j) reach_x += std::sqrt(sq3(d->joint_placement + 12 * j + 9)) + travel[j];
-  // (the kinematic links: where a free frame starts says nothing about the chain)
-  for (int l = 0; l < d->n_links - n_free; ++l) reach_x += std::sqrt(sq3(d->link_placement + 12 * l + 9));
-  double off = 0.0;
-  for (int m = 0; m < d->n_moving; ++m) off = std::max(off, std::sqrt(sq3(d->moving_offset + 12 * m + 9)));
-  for (int g = 0; g < d->n_geoms; ++g) geo_r = std::max(geo_r, geom_rec[G_STRIDE * g + G_RADIUS] +
-                                                                   std::sqrt(sq3(&geom_rec[G_STRIDE * g + G_OBB_C])));
-  for (int s2 = 0; s2 < d->n_static; ++s2) stat_x = std::max(stat_x, std::sqrt(sq3(d->static_transform + 12 * s2 + 9)));
-  double X = std::max(reach_x + off, stat_x) + geo_r;
-  bp_margin = std::max(bp_margin, (float)(kFp32CullRel * X));
-  double small_margin = may_mpr ? std::max(kSmallMargin, reach) : kSmallMargin;
-  // Movable objects (on free frames).  Every link-borne object lies in the
-  // ball of radius link_r around the origin: each coordinate of a link origin
-  // is within reach_x (FK keeps the norm there; the link-pose input forces
-  // every pair of a row beyond it), then the offset and the geometry.  A
-  // movable object whose bounding sphere is outside far_r = link_r + margin +
-  // slack (as never_near) is dropped by the cull's exact fp64 far test; one
-  // that is not has every coordinate within far_r + 2 geo_r, which X (and so
-  // the margin, which in turn moves far_r: a few rounds settle it) covers.
-  // The margins also carry the scaling a free pose's quaternion may have
-  // (kFreeQuatTol, mpgpu.h).
-  double far_r = 0.0;
-  if (n_free) {
-    const double link_r = std::sqrt(3.0) * reach_x + off + geo_r;
-    const float quat_slack = (float)(4.0 * kFreeQuatTol * geo_r);
-    bp_margin += quat_slack;
-    small_margin += 4.0 * kFreeQuatTol * geo_r;
-    for (int it = 0; it < 8; ++it) {
-      far_r = (link_r + (double)bp_margin + 1e-6 * (1.0 + X)) * (1.0 + 1e-9);
-      X = std::max(X, far_r + 2.0 * geo_r);
-      bp_margin = std::max(bp_margin, (float)(kFp32CullRel * X) + quat_slack);
-    }
-    far_r = (link_r + (double)bp_margin + 1e-6 * (1.0 + X)) * (1.0 + 1e-9);
-    X = std::max(X, far_r + 2.0 * geo_r);
-  }
-  // link poses given directly (mpg_collide_link_poses): a pose beyond the
-  // chain's reach falls outside the coordinate bound -> every pair
-  const double pose_bound = reach_x;
-  // Reach ball of each moving object: its centre stays within radius R of
-  // the origin of the first joint of its chain (every later joint origin is
-  // a fixed distance from its parent's, plus a prismatic travel; revolute
-  // angles cannot lengthen the chain), or is fixed when the chain is empty.
-  // A static partner farther than R + the object's radius + the culling
-  // margin from that ball can never be a candidate: its schedule entry is
-  // kept only for the link-pose input, whose poses are not kinematic.
-  std::vector<std::array<double, 4>> ball(std::max(d->n_moving, 1));  // centre, radius (object radius included)
-  for (int m = 0; m < d->n_moving; ++m) {
-    const int l = d->moving_link[m];
-    const double* g = geom_rec.data() + G_STRIDE * d->moving_geom[m];
-    const double* mo = d->moving_offset + 12 * m;
-    const double* lp = d->link_placement + 12 * l;
-    double a[3], bpt[3];
-    for (int i = 0; i < 3; ++i)
-      a[i] = mo[3 * i] * g[G_OBB_C] + mo[3 * i + 1] * g[G_OBB_C + 1] + mo[3 * i + 2] * g[G_OBB_C + 2] + mo[9 + i];
-    for (int i = 0; i < 3; ++i) bpt[i] = lp[3 * i] * a[0] + lp[3 * i + 1] * a[1] + lp[3 * i + 2] * a[2] + lp[9 + i];
-    const int cs = chain_start[l], cn = chain_len[l];
-    double R = g[G_RADIUS];
-    if (cn == 0) {
-      ball[m] = {bpt[0], bpt[1], bpt[2], R};
-      continue;
-    }
-    const int j1 = chain_joints[cs] - 1;
-    const double* p1 = d->joint_placement + 12 * j1 + 9;
-    R += travel[j1] + std::sqrt(sq3(bpt));
-    for (int k = 1; k < cn; ++k) {
-      const int j = chain_joints[cs + k] - 1;
-      R += std::sqrt(sq3(d->joint_placement + 12 * j + 9)) + travel[j];
-    }
-    ball[m] = {p1[0], p1[1], p1[2], R * (1.0 + 1e-9) + 1e-9};
-  }
-  auto never_near = [&](int m, int sid) {  // exact fp64 distance, reach ball vs the static OBB
-    const double* sr = static_rec.data() + (size_t)S_STRIDE * sid;
-    const double* gs = geom_rec.data() + G_STRIDE * d->static_geom[sid];
-    double e2 = 0.0;
-    for (int k = 0; k < 3; ++k) {  // box axis k = column k of S_R
-      double t = 0.0;
-      for (int i = 0; i < 3; ++i) t += (ball[m][i] - sr[S_OBBC + i]) * sr[S_R + 3 * i + k];
-      const double ex = std::max(std::fabs(t) - gs[G_OBB_E + k], 0.0);
-      e2 += ex * ex;
-    }
-    const double slack = 1e-6 * (1.0 + X);
-    return std::sqrt(e2) - ball[m][3] > (double)bp_margin + slack;
-  };
-  // bits of every non-allowed pair (a configuration evaluated with all pairs)
-  std::vector<int> all_mask(std::max(W, 1), 0);
-  for (int p = 0; p < d->n_pairs; ++p)
-    if (!allowed[p]) all_mask[p >> 5] |= (int)(1u << (p & 31));
-  // moving-moving pairs by their lower moving object, then the moving-static
-  // pairs static-major (one static record serves all its entries), those the
-  // object's reach ball can bring near (group 0) before the rest (group 1)
-  const int ns = d->n_static;
-  std::vector<int> sched_start(d->n_moving + 1, 0), sched_pair, sched_other, st_start(2 * (ns + 1), 0), st_m;
-  std::vector<float> st_r;
-  for (int m = 0; m < d->n_moving; ++m) {
-    sched_start[m] = (int)sched_pair.size();
-    for (int p = 0; p < d->n_pairs; ++p) {
-      if (allowed[p]) continue;
-      const int a = d->pair_a[p], b = d->pair_b[p];
-      const int lo = std::min(a, b), hi = std::max(a, b);  // static ids are >= n_moving
-      if (lo != m || hi >= d->n_moving) continue;
-      sched_pair.push_back(p);
-      sched_other.push_back(hi);
-      st_m.push_back(0);
-      st_r.push_back(0.f);
-    }
-  }
-  sched_start[d->n_moving] = (int)sched_pair.size();
-  for (int g = 0; g < 2; ++g) {
-    for (int sid = 0; sid < ns; ++sid) {
-      st_start[g * (ns + 1) + sid] = (int)sched_pair.size();
-      for (int m = 0; m < d->n_moving; ++m)
-        for (int p = 0; p < d->n_pairs; ++p) {
-          if (allowed[p]) continue;
-          const int a = d->pair_a[p], b = d->pair_b[p];
-          if (std::min(a, b) != m || std::max(a, b) != d->n_moving + sid) continue;
-          if (never_near(m, sid) != (g == 1)) continue;
-          sched_pair.push_back(p);
-          sched_other.push_back(d->n_moving + sid);
-          st_m.push_back(m);
-          st_r.push_back(bpp.mobj[BM_STRIDE * m + BM_R]);
-        }
-    }
-    st_start[g * (ns + 1) + ns] = (int)sched_pair.size();
-  }
-  if (sched_pair.empty()) {
-    sched_pair.push_back(0);
-    sched_other.push_back(0);
-    st_m.push_back(0);
-    st_r.push_back(0.f);
-  }
-
-  BlobBuilder bb;
-  const size_t o_jt = bb.add(d->joint_type, d->n_joints);
-  const size_t o_jp = bb.add(d->joint_parent, d->n_joints);
-  const size_t o_jqs = bb.add(d->joint_q_source, d->n_joints);
-  const size_t o_jqc = bb.add(d->joint_q_const, d->n_joints);
-  const size_t o_ja = bb.add(d->joint_axis, 3 * (size_t)d->n_joints);
-  const size_t o_jpl = bb.add(d->joint_placement, 12 * (size_t)d->n_joints);
-  const size_t o_lp = bb.add(d->link_parent, d->n_links);
-  const size_t o_lpl = bb.add(d->link_placement, 12 * (size_t)d->n_links);
-  const size_t o_gt = bb.add(d->geom_type, d->n_geoms);
-  const size_t o_gvs = bb.add(gstart.data(), gstart.size());
-  const size_t o_gnv = bb.add(ngroups.data(), ngroups.size());
-  std::vector<int> nvert(std::max(d->n_geoms, 1), 0);
-  for (int g = 0; g < d->n_geoms; ++g) nvert[g] = d->geom_type[g] == MPG_GEOM_CONVEX ? d->geom_vertex_count[g] : 0;
-  const size_t o_gnvt = bb.add(nvert.data(), nvert.size());
-  const size_t o_grec = bb.add(geom_rec.data(), geom_rec.size());
-  const size_t o_v = bb.add(hull.data(), hull.size());
-  const size_t o_cb = bb.add(cbase.data(), cbase.size());
-  const size_t o_crec = bb.add(cell_rec.data(), cell_rec.size());
-  const size_t o_covf = bb.add(cell_ovf.data(), cell_ovf.size());
-  const size_t o_gnb = bb.add(geom_nbr.data(), geom_nbr.size());
-  const size_t o_hnb = bb.add(hull_nbr.data(), hull_nbr.size());
-  const size_t o_nent = bb.add(nbr_ent.data(), nbr_ent.size());
-  const size_t o_wrec = bb.add(wcell_rec.data(), wcell_rec.size());
-  const size_t o_wovf = bb.add(wcell_ovf.data(), wcell_ovf.size());
-  const size_t o_waux = bb.add(wcell_aux.data(), wcell_aux.size());
-  const size_t o_wend = bb.add(wcell_end.data(), wcell_end.size());
-  const size_t o_wend2 = bb.add(wcell_end2.data(), wcell_end2.size());
-  const size_t o_wpre = bb.add(wcell_pre.data(), wcell_pre.size());
-  const size_t o_ml = bb.add(d->moving_link, d->n_moving);
-  const size_t o_mg = bb.add(d->moving_geom, d->n_moving);
-  const size_t o_mo = bb.add(d->moving_offset, 12 * (size_t)d->n_moving);
-  const size_t o_sg = bb.add(d->static_geom, d->n_static);
-  const size_t o_srec = bb.add(static_rec.data(), static_rec.size());
-  const size_t o_pa = bb.add(d->pair_a, d->n_pairs);
-  const size_t o_pb = bb.add(d->pair_b, d->n_pairs);
-  const size_t o_al = bb.add(allowed.data(), allowed.size());
-  const size_t o_cf = bb.add(pair_cf.data(), pair_cf.size());
-  const size_t o_sT = bb.add(d->static_transform, 12 * (size_t)d->n_static);
-  const size_t o_cs = bb.add(chain_start.data(), chain_start.size());
-  const size_t o_cl = bb.add(chain_len.data(), chain_len.size());
-  const size_t o_cj = bb.add(chain_joints.data(), chain_joints.size());
-  const size_t o_ss = bb.add(sched_start.data(), sched_start.size());
-  const size_t o_sp = bb.add(sched_pair.data(), sched_pair.size());
-  const size_t o_so = bb.add(sched_other.data(), sched_other.size());
-  const size_t o_sts = bb.add(st_start.data(), st_start.size());
-  const size_t o_stm = bb.add(st_m.data(), st_m.size());
-  const size_t o_str = bb.add(st_r.data(), st_r.size());
-  const size_t o_pbd = bb.add(prism_bound.data(), prism_bound.size());
-  const size_t o_amk = bb.add(all_mask.data(), all_mask.size());
-  const size_t o_bjs = bb.add(bpp.jsrc.data(), bpp.jsrc.size());
-  const size_t o_bjv = bb.add(bpp.jsave.data(), bpp.jsave.size());
-  const size_t o_bja = bb.add(bpp.jaxis.data(), bpp.jaxis.size());
-  const size_t o_bjp = bb.add(bpp.jplace.data(), bpp.jplace.size());
-  const size_t o_bls = bb.add(bpp.link_start.data(), bpp.link_start.size());
-  const size_t o_blo = bb.add(bpp.link_order.data(), bpp.link_order.size());
-  const size_t o_blp = bb.add(bpp.lplace.data(), bpp.lplace.size());
-  const size_t o_bos = bb.add(bpp.obj_start.data(), bpp.obj_start.size());
-  const size_t o_boo = bb.add(bpp.obj_order.data(), bpp.obj_order.size());
-  const size_t o_bmo = bb.add(bpp.moff.data(), bpp.moff.size());
-  const size_t o_bmb = bb.add(bpp.mobj.data(), bpp.mobj.size());
-  const size_t o_bsb = bb.add(bpp.sobj.data(), bpp.sobj.size());
-  if (bpp.jobj_order.empty()) bpp.jobj_order.push_back(0);
-  const size_t o_bjk = bb.add(bpp.jkind.data(), bpp.jkind.size());
-  const size_t o_bjo = bb.add(bpp.jobj_start.data(), bpp.jobj_start.size());
-  const size_t o_bjr = bb.add(bpp.jobj_order.data(), bpp.jobj_order.size());
-  const size_t o_bop = bb.add(bpp.oplace.data(), bpp.oplace.size());
-  const size_t o_boq = bb.add(bpp.oquat.data(), bpp.oquat.size());
-  const size_t o_boc = bb.add(bpp.ocen.data(), bpp.ocen.size());
-  const size_t o_olf = bb.add(oct_leaf.data(), oct_leaf.size());
-  const size_t o_mtr = bb.add(mesh_tri.data(), mesh_tri.size());
-  const size_t o_mnd = bb.add(mesh_node.data(), mesh_node.size());
-  const size_t o_mln = bb.add(mesh_link.data(), mesh_link.size());
-  const size_t o_mtt = bb.add(mesh_tree.data(), mesh_tree.size());
-  const size_t o_lrec = bb.add(lat_rec.data(), lat_rec.size());
-  const size_t o_fbb = bb.add(fbvh.box.data(), fbvh.box.size());
-  const size_t o_fbl = bb.add(fbvh.link.data(), fbvh.link.size());
-  const size_t o_fbr = bb.add(fb_root.data(), fb_root.size());
-  const size_t o_tps = bb.add(tri_pos.data(), tri_pos.size());
-  const size_t o_sob = bb.add(sobb.data(), sobb.size());
-  const size_t o_ogr = bb.add(oct_grid.data(), oct_grid.size());
-  const size_t o_oce = bb.add(oct_cells.data(), oct_cells.size());
-  const size_t o_oli = bb.add(oct_list.data(), oct_list.size());
-  const size_t o_opa = bb.add(oct_path.data(), oct_path.size());
-  const size_t o_ode = bb.add(oct_depth.data(), oct_depth.size());
-  // free frame k (link n_links - n_free + k) -> its object; worlds without
-  // free frames add nothing to the snapshot (their hash stays what it was)
-  std::vector<int> free_obj(n_free, 0);
-  for (int m = 0; m < d->n_moving; ++m)
-    if (d->moving_link[m] >= d->n_links - n_free) free_obj[d->moving_link[m] - (d->n_links - n_free)] = m;
-  const size_t o_fob = n_free ? bb.add(free_obj.data(), free_obj.size()) : 0;
-
-  mpg_world* w = new mpg_world();
-  w->device = device;
-  w->n_geoms = d->n_geoms;
-  w->geom_type_h.assign(d->geom_type, d->geom_type + d->n_geoms);
-  w->block = block;
-  w->lds_bytes = lds;
-  w->blob_bytes = bb.bytes.size();
-  {  // FNV-1a over the snapshot: worlds built from the same descriptor agree
-    uint64_t h = 1469598103934665603ull;
-    for (const char c : bb.bytes) h = (h ^ (uint8_t)c) * 1099511628211ull;
-    w->snapshot_hash = h;
-  }
-  hipError_t e = hipMalloc(&w->blob, w->blob_bytes);
-  if (e != hipSuccess) {
-    delete w;
-    return set_error(MPG_E_HIP, std::string("hipMalloc(snapshot): ") + hipGetErrorString(e));
-  }
-  e = hipMemcpy(w->blob, bb.bytes.data(), w->blob_bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    hipFree(w->blob);
-    delete w;
-    return set_error(MPG_E_HIP, std::string("hipMemcpy(snapshot): ") + hipGetErrorString(e));
-  }
-  char* base = static_cast<char*>(w->blob);
-  DevWorld& dw = w->dw;
-  dw.nj = d->n_joints;
-  dw.dof = d->dof;
-  dw.n_links = d->n_links;
-  dw.n_geoms = d->n_geoms;
-  dw.n_moving = d->n_moving;
-  dw.n_static = d->n_static;
-  dw.n_pairs = d->n_pairs;
-  dw.W = W;
-  dw.mpr_tol = d->gjk_tolerance;
-  dw.bp_margin = bp_margin;
-  dw.small_margin = small_margin;
-  dw.n_prism = n_prism;
-  dw.prism_bound = to_cptr<double>(base + o_pbd);
-  dw.pose_bound = pose_bound;
-  dw.all_mask = to_cptr<int>(base + o_amk);
-  dw.n_free = n_free;
-  dw.far_r = far_r;
-  dw.free_obj = to_cptr<int>(base + o_fob);
-  dw.free_cur = nullptr;
-  if (n_free) {  // the current poses start at the frames' link_placement, as (p, wxyz)
-    w->free_host.resize((size_t)n_free * 7);
-    for (int k = 0; k < n_free; ++k) {
-      const double* lp = d->link_placement + 12 * (size_t)(d->n_links - n_free + k);
-      double* p7 = w->free_host.data() + 7 * (size_t)k;
-      for (int i = 0; i < 3; ++i) p7[i] = lp[9 + i];
-      mat_to_quat(lp, &p7[3], &p7[4]);
-    }
-    HIP_TRY(hipMalloc(&w->free_dev, sizeof(double) * w->free_host.size()));
-    HIP_TRY(hipMemcpy(w->free_dev, w->free_host.data(), sizeof(double) * w->free_host.size(), hipMemcpyHostToDevice));
-    dw.free_cur = w->free_dev;
-  }
-#ifdef MPG_DIAG  // ablation builds only (changes results)
-  if (const char* m = std::getenv("MPG_DEBUG_MARGIN")) {
-    dw.bp_margin = (float)std::atof(m);
-    dw.small_margin = std::atof(m);
-  }
-#endif
-  dw.debug_mode = 0;
-#ifdef MPG_DIAG  // ablation builds only (changes results)
-  if (const char* e = std::getenv("MPG_DEBUG_CULL")) dw.debug_mode = std::atoi(e);
-#endif
-  dw.big_vis = nullptr;
-  dw.big_busy = nullptr;
-  dw.big_slots = 0;
-  dw.big_words = big_words;
-  if (big_words > 0) {  // one visited set per resident wave at most (256 CUs x 32 waves)
-    dw.big_slots = 8192;
-    HIP_TRY(hipMalloc(&dw.big_vis, sizeof(unsigned long long) * (size_t)dw.big_slots * big_words));
-    HIP_TRY(hipMemset(dw.big_vis, 0, sizeof(unsigned long long) * (size_t)dw.big_slots * big_words));
-    HIP_TRY(hipMalloc(&dw.big_busy, sizeof(int) * (size_t)dw.big_slots));
-    HIP_TRY(hipMemset(dw.big_busy, 0, sizeof(int) * (size_t)dw.big_slots));
-  }
-  dw.stats = nullptr;
-  if (std::getenv("MPG_STATS") && std::atoi(std::getenv("MPG_STATS")) > 0) {
-    HIP_TRY(hipMalloc(&dw.stats, 64 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(dw.stats, 0, 64 * sizeof(unsigned long long)));
-  }
-  dw.joint_type = to_cptr<int>(base + o_jt);
-  dw.joint_parent = to_cptr<int>(base + o_jp);
-  dw.joint_q_source = to_cptr<int>(base + o_jqs);
-  dw.joint_q_const = to_cptr<double>(base + o_jqc);
-  dw.joint_axis = to_cptr<double>(base + o_ja);
-  dw.joint_place = to_cptr<double>(base + o_jpl);
-  dw.link_parent = to_cptr<int>(base + o_lp);
-  dw.link_place = to_cptr<double>(base + o_lpl);
-  dw.geom_type = to_cptr<int>(base + o_gt);
-  dw.geom_gstart = to_cptr<int>(base + o_gvs);
-  dw.geom_ng = to_cptr<int>(base + o_gnv);
-  dw.geom_nvert = to_cptr<int>(base + o_gnvt);
-  dw.geom_rec = to_cptr<double>(base + o_grec);
-  dw.hull = to_cptr<double>(base + o_v);
-  dw.hull_doubles = (int)hull.size();
-  dw.geom_cbase = to_cptr<int>(base + o_cb);
-  dw.cell_rec = to_cptr<double>(base + o_crec);
-  dw.cell_ovf = to_cptr<double>(base + o_covf);
-  dw.geom_nbr = to_cptr<int>(base + o_gnb);
-  dw.hull_nbr = to_cptr<int>(base + o_hnb);
-  dw.nbr_ent = to_cptr<double>(base + o_nent);
-  dw.wcell_rec = to_cptr<double>(base + o_wrec);
-  dw.wcell_ovf = to_cptr<double>(base + o_wovf);
-  dw.wcell_aux = to_cptr<double>(base + o_waux);
-  dw.wcell_end = to_cptr<int>(base + o_wend);
-  dw.wcell_end2 = to_cptr<int>(base + o_wend2);
-  dw.wcell_pre = to_cptr<int>(base + o_wpre);
-  dw.walk_subk = walk_subk;
-  dw.moving_link = to_cptr<int>(base + o_ml);
-  dw.moving_geom = to_cptr<int>(base + o_mg);
-  dw.moving_offset = to_cptr<double>(base + o_mo);
-  dw.static_geom = to_cptr<int>(base + o_sg);
-  dw.static_rec = to_cptr<double>(base + o_srec);
-  dw.pair_a = to_cptr<int>(base + o_pa);
-  dw.pair_b = to_cptr<int>(base + o_pb);
-  dw.pair_allowed = to_cptr<int>(base + o_al);
-  dw.pair_cf = to_cptr<int>(base + o_cf);
-  for (int p = 0; p < d->n_pairs; ++p) {
-    w->has_closed_form |= pair_cf[p] != CF_NONE && !allowed[p];
-    w->has_octree |= pair_cf[p] == CF_OCTREE && !allowed[p];
-    w->octree_first |= pair_cf[p] == CF_OCTREE && !allowed[p] && obj_geom_type(d, d->pair_a[p]) == MPG_GEOM_OCTREE;
-    w->any_closed_form |= pair_cf[p] != CF_NONE && cf_class(pair_cf[p]) == CLS_CLOSED;
-    w->any_octree |= pair_cf[p] == CF_OCTREE;
-    w->has_mesh |= pair_cf[p] == CF_MESH && !allowed[p];
-    w->any_mesh |= pair_cf[p] == CF_MESH;
-    w->any_gjk |= pair_cf[p] == CF_GJK;
-    w->has_octree2 |= !allowed[p] && obj_geom_type(d, d->pair_a[p]) == MPG_GEOM_OCTREE &&
-                      obj_geom_type(d, d->pair_b[p]) == MPG_GEOM_OCTREE;
-  }
-  dw.static_T = to_cptr<double>(base + o_sT);
-  dw.link_chain_start = to_cptr<int>(base + o_cs);
-  dw.link_chain_len = to_cptr<int>(base + o_cl);
-  dw.chain_joints = to_cptr<int>(base + o_cj);
-  auto I = [&](size_t o) { return to_cptr<int>(base + o); };
-  dw.sched_start = I(o_ss);
-  dw.sched_pair = I(o_sp);
-  dw.sched_other = I(o_so);
-  dw.st_start = I(o_sts);
-  dw.st_m = I(o_stm);
-  dw.st_r = to_cptr<float>(base + o_str);
-  auto F = [&](size_t o) { return to_cptr<float>(base + o); };
-  BpView& bp = dw.bp;
-  bp.nj = d->n_joints;
-  bp.n_links = d->n_links;
-  bp.n_moving = d->n_moving;
-  bp.n_static = d->n_static;
-  bp.n_saves = bpp.n_saves;
-  bp.joint_type = dw.joint_type;
-  bp.joint_q_source = dw.joint_q_source;
-  bp.joint_q_const = dw.joint_q_const;
-  bp.jsrc = I(o_bjs);
-  bp.jsave = I(o_bjv);
-  bp.jaxis = F(o_bja);
-  bp.jplace = F(o_bjp);
-  bp.link_start = I(o_bls);
-  bp.link_order = I(o_blo);
-  bp.lplace = F(o_blp);
-  bp.obj_start = I(o_bos);
-  bp.obj_order = I(o_boo);
-  bp.moving_link = dw.moving_link;
-  bp.moff = F(o_bmo);
-  bp.mobj = F(o_bmb);
-  bp.sobj = F(o_bsb);
-  bp.jkind = I(o_bjk);
-  bp.jobj_start = I(o_bjo);
-  bp.jobj_order = I(o_bjr);
-  bp.oplace = F(o_bop);
-  bp.oquat = F(o_boq);
-  bp.ocen = F(o_boc);
-  dw.oct_leaf = to_cptr<double>(base + o_olf);
-  dw.oct_path = to_cptr<uint64_t>(base + o_opa);
-  dw.oct_depth = to_cptr<int>(base + o_ode);
-  dw.mesh_tri = to_cptr<double>(base + o_mtr);
-  dw.mesh_node = to_cptr<double>(base + o_mnd);
-  dw.mesh_link = to_cptr<int>(base + o_mln);
-  dw.mesh_tree = to_cptr<int>(base + o_mtt);
-  dw.fb_box = to_cptr<double>(base + o_fbb);
-  dw.fb_link = to_cptr<int>(base + o_fbl);
-  dw.fb_root = to_cptr<int>(base + o_fbr);
-  dw.tri_pos = to_cptr<int>(base + o_tps);
-  dw.sobb = to_cptr<double>(base + o_sob);
-  dw.lat_rec = to_cptr<double>(base + o_lrec);
-  dw.lat_rec_ok = lat_rec_ok ? 1 : 0;
-  dw.oct_grid = to_cptr<double>(base + o_ogr);
-  dw.oct_cells = I(o_oce);
-  dw.oct_list = I(o_oli);
-  int cus = 256;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
-  // persistent narrow grid: exactly the resident workgroups
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, narrow_kernel<false>, 256, 0) != hipSuccess || per_cu <= 0)
-    per_cu = 2;
-  w->narrow_blocks = cus * per_cu;
-  // bound the candidate lists to 1 GiB: cap * n_pairs * 4 B
-  w->max_chunk = std::max<long long>(4096, std::min<long long>(1 << 20, (1ll << 28) / std::max(d->n_pairs, 1)));
-  if (const char* e = std::getenv("MPG_SMALL_BATCH_MAX")) w->small_max = std::atoll(e);
-  if (const char* e = std::getenv("MPG_SMALL_ZEROCOPY")) w->small_zero_copy = std::atoi(e) != 0;
-  if (const char* e = std::getenv("MPG_OVERLAP_MIN")) w->overlap_min = std::atoll(e);
-  if (const char* e = std::getenv("MPG_HOST_STREAMS")) w->ring_streams = std::atoi(e) > 1 ? 2 : 1;
-  if (const char* e = std::getenv("MPG_HOST_THREADS")) w->host_threads = std::max(1, std::min(64, std::atoi(e)));
-  if (const char* e = std::getenv("MPG_HOST_HEAD")) w->ring_head = std::max(0ll, std::atoll(e));
-  if (const char* e = std::getenv("MPG_HOST_TAIL")) w->ring_tail = std::max(0ll, std::atoll(e));
-  if (const char* e = std::getenv("MPG_HOST_CHUNK"))
-    w->ring_chunk = std::max(64ll, std::min((long long)w->max_chunk, (std::atoll(e) + 63) / 64 * 64));
-  if (const char* e = std::getenv("MPG_SMALL_INLINE_SC")) w->small_inline_sc = std::atoll(e);
-  if (const char* e = std::getenv("MPG_OVERLAP_PARTS")) w->overlap_parts = std::atoi(e);
-  if (const char* e = std::getenv("MPG_SMALL_HOST_SC")) w->small_host_sc = std::atoll(e);
-  if (const char* e = std::getenv("MPG_SMALL_ARGS")) w->small_args = std::atoi(e) != 0;
-  for (int j = 0; j < d->n_joints; ++j)
-    if (d->joint_q_source[j] >= 0 && joint_is_revolute(d->joint_type[j]) &&
-        std::find(w->h_rev_src.begin(), w->h_rev_src.end(), d->joint_q_source[j]) == w->h_rev_src.end())
-      w->h_rev_src.push_back(d->joint_q_source[j]);
-  if (const char* e = std::getenv("MPG_SMALL_SERVER")) w->srv_mode = std::atoi(e);
-  w->srv_stats = std::getenv("MPG_STATS") != nullptr;
-  if (const char* e = std::getenv("MPG_SMALL_SERVER_IDLE_US")) w->srv_idle_us = std::max(10ll, std::atoll(e));
-  if (const char* e = std::getenv("MPG_SMALL_SERVER_WG")) w->srv_g = std::min(kSrvMaxG, std::max(1, std::atoi(e)));
-  if (const char* e = std::getenv("MPG_SMALL_SERVER_MAX")) w->srv_max_n = std::min(kSrvN, std::max(1, std::atoi(e)));
-  w->srv_lds = srv_lds_bytes(d->n_moving, d->n_pairs, d->dof, w->dw.W, d->n_joints, d->n_static);
-  w->srv_ok = lat_rec_ok && !w->any_octree && !w->any_mesh && !w->any_gjk && d->dof > 0 && d->dof <= kLatScDof &&
-              d->n_pairs > 0 && w->dw.W <= kSrvMaxW && w->srv_lds <= 144 * 1024 &&  // + ~11 KB static LDS
-              n_free == 0;  // the resident server holds a by-value world: it would not see a pose update
-  const char* own = std::getenv("MPG_OWN_STREAM");
-  if (!own || std::atoi(own) != 0) HIP_TRY(hipStreamCreateWithFlags(&w->own_stream, hipStreamNonBlocking));
-  *out = w;
-  return MPG_OK;
-}
-
-int mpg_world_destroy(mpg_world* w) {
-  if (!w) return MPG_OK;
-  hipSetDevice(w->device);
-  if (w->dw.big_vis) hipFree(w->dw.big_vis);
-  if (w->dw.big_busy) hipFree(w->dw.big_busy);
-  if (w->dw.stats) {
-    unsigned long long st[64];
-    hipDeviceSynchronize();
-    hipMemcpy(st, w->dw.stats, sizeof(st), hipMemcpyDeviceToHost);
-    std::fprintf(stderr,
-                 "[mpg stats] small_kernel phases (sum over waves / max per wave, us): pre %.1f/%.2f, record %.1f/%.2f, "
-                 "fk %.1f/%.2f, spheres %.1f/%.2f, narrow %.1f/%.2f, store %.1f/%.2f, wave %.1f/%.2f\n",
-                 st[24] / 100.0, st[32] / 100.0, st[25] / 100.0, st[33] / 100.0, st[26] / 100.0, st[34] / 100.0,
-                 st[27] / 100.0, st[35] / 100.0, st[28] / 100.0, st[36] / 100.0, st[29] / 100.0, st[37] / 100.0,
-                 st[30] / 100.0, st[38] / 100.0);
-    if (st[42])
-      std::fprintf(stderr, "[mpg stats] latency server probe: dependent cell-record loads, shader clocks each: "
-                   "first pass %.0f, again %.0f\n", (double)st[40] / st[42], (double)st[41] / st[43]);
-    if (st[20])
-      std::fprintf(stderr, "[mpg stats] latency server MPR steps: %llu (max %llu per pair), shader clocks per step: "
-                   "support %.0f, advance %.0f\n", st[20], st[23], (double)st[21] / st[20], (double)st[22] / st[20]);
-    if (st[52])
-      std::fprintf(stderr, "[mpg stats] walk-hull support phases, shader clocks per hull support (%llu): cell lookup "
-                   "%.0f, record load + inline dots %.0f, overflow entries %.0f, tie / trap checks %.0f\n",
-                   st[52], (double)st[48] / st[52], (double)st[49] / st[52], (double)st[50] / st[52],
-                   (double)st[51] / st[52]);
-    std::fprintf(stderr, "[mpg stats] small_kernel slowest narrow test: pair %llu, %.2f us\n",
-                 (unsigned long long)(st[31] & 4095), (st[31] >> 12) / 100.0);
-    std::fprintf(stderr, "[mpg stats] walk hulls: supports %llu, trap-free fast %llu, verified %llu, full walks %llu, "
-                 "certified endpoints %llu; pending: tie %llu, uncertified %llu, resumed %llu; resolve ticks: verify %llu, walk %llu\n",
-                 st[10], st[11], st[12], st[13], st[14], st[16], st[17], st[18], st[9], st[15]);
-    std::fprintf(stderr,
-                 "[mpg stats] narrow: refill %llu, support %llu, update %llu (memtime ticks, summed over waves); "
-                 "steps %llu, mean active lanes/step %.1f; hits %llu (%.2f supports each), misses %llu (%.2f)\n",
-                 st[3], st[4], st[5], st[7], st[7] ? (double)st[6] / st[7] : 0.0, st[2],
-                 st[2] ? (double)st[0] / st[2] : 0.0, st[8], st[8] ? (double)st[1] / st[8] : 0.0);
-    hipFree(w->dw.stats);
-  }
-  if (w->srv_stats && w->srv_stat[5] > 0)
-    std::fprintf(stderr, "[mpg stats] latency server, mean us over %.0f batches: rows %.2f, fk %.2f, spheres %.2f, "
-                 "narrow %.2f, publish %.2f; host post->done %.2f\n", w->srv_stat[5], w->srv_stat[0] / w->srv_stat[5],
-                 w->srv_stat[1] / w->srv_stat[5], w->srv_stat[2] / w->srv_stat[5], w->srv_stat[3] / w->srv_stat[5],
-                 w->srv_stat[4] / w->srv_stat[5], w->srv_stat[6] / w->srv_stat[5]);
-  if (w->srv_stats && w->hp_stat[0] > 0)
-    std::fprintf(stderr, "[mpg stats] host pipeline, mean us over %.0f calls: input copies %.1f, issue %.1f, "
-                 "result wait %.1f, unpack %.1f; whole call %.1f\n", w->hp_stat[0], w->hp_stat[1] / w->hp_stat[0],
-                 w->hp_stat[2] / w->hp_stat[0], w->hp_stat[3] / w->hp_stat[0], w->hp_stat[4] / w->hp_stat[0],
-                 w->hp_stat[5] / w->hp_stat[0]);
-  if (w->srv_h) {  // the server leaves at its next poll
-    __atomic_store_n(&w->srv_h->quit, 1ull, __ATOMIC_RELEASE);
-    hipStreamSynchronize(w->srv_stream);
-    hipStreamDestroy(w->srv_stream);
-    hipHostFree(w->srv_h);
-  }
-  hipFree(w->blob);
-  if (w->h_q) hipHostFree(w->h_q);
-  if (w->h_hits) hipHostFree(w->h_hits);
-  hipFree(w->d_qs);
-  if (w->d_ssc) hipFree(w->d_ssc);
-  if (w->h_ssc) hipHostFree(w->h_ssc);
-  if (w->own_stream) hipStreamDestroy(w->own_stream);
-  for (auto& kv : w->sides) {
-    hipStreamDestroy(kv.second.side);
-    hipEventDestroy(kv.second.fork);
-    hipEventDestroy(kv.second.join);
-  }
-  hipFree(w->d_q);
-  hipFree(w->d_flags);
-  hipFree(w->d_masks);
-  hipFree(w->d_out);
-  free_ring(w);
-  w->pool.reset();
-  if (w->ring.h2d) {
-    hipStreamDestroy(w->ring.h2d);
-    hipStreamDestroy(w->ring.side);
-    for (int j = 0; j < mpg_world::kRing; ++j) {
-      hipEventDestroy(w->ring.e_in[j]);
-      hipEventDestroy(w->ring.e_done[j]);
-    }
-  }
-  for (auto& mk : w->marks) {
-    hipEventDestroy(mk.a);
-    hipEventDestroy(mk.b);
-  }
-  for (hipEvent_t e : w->ev_pool) hipEventDestroy(e);
-  hipFree(w->dist.poses);
-  hipFree(w->dist.save64);
-  hipFree(w->dist.q);
-  hipFree(w->dist.out);
-  hipFree(w->dist.pts);
-  hipFree(w->dist.links);
-  if (w->dist.last) hipEventDestroy(w->dist.last);
-  hipFree(w->dist.big);
-  hipFree(w->dist.list);
-  if (w->gather_ev) hipEventDestroy(w->gather_ev);
-  if (w->motion.last) hipEventDestroy(w->motion.last);
-  hipFree(w->contact.in);
-  hipFree(w->contact.out);
-  hipFree(w->contact.fl);
-  hipFree(w->contact.mk);
-  hipFree(w->motion.edges);
-  hipFree(w->motion.segs);
-  hipFree(w->motion.offs);
-  hipFree(w->motion.out);
-  hipFree(w->motion.states);
-  hipFree(w->motion.flags);
-  hipFree(w->prof_units);
-  for (auto& kv : w->ws)
-  {
-    for (uint32_t* p : {kv.second.surv, kv.second.cnt, kv.second.seg_len, kv.second.seg_start, kv.second.prefix,
-                        kv.second.cand})
-      hipFree(p);
-    hipFree(kv.second.rq);
-    hipFree(kv.second.sc);
-    hipFree(kv.second.links);
-  }
-  hipFree(w->free_dev);
-  hipFree(w->free_stage.q);
-  hipFree(w->free_stage.fp);
-  hipFree(w->free_stage.links);
-  hipFree(w->free_stage.fl);
-  hipFree(w->free_stage.mk);
-  delete w;
-  return MPG_OK;
-}
-
-int mpg_world_get_info(const mpg_world* w, mpg_world_info* info) {
-  if (!w || !info) return set_error(MPG_E_INVALID, "NULL argument");
-  info->n_pairs = w->dw.n_pairs;
-  info->mask_words = w->dw.W;
-  info->dof = w->dw.dof;
-  info->n_links = w->dw.n_links;
-  info->device = w->device;
-  info->block_size = w->block;
-  info->snapshot_bytes = (int64_t)w->blob_bytes;
-  return MPG_OK;
-}
+#include "mpg_abi_world.h"
 
 }  // extern "C"
 
 namespace {
-// pinned input rows (ncfg * row doubles: q rows or link poses), hit bytes
-// (n_pairs * ncfg) and joint sincos: the input capacity is tracked in doubles,
-// since the same buffers serve q rows (dof) and link-pose rows (n_links * 7)
-int ensure_small(mpg_world* w, size_t ncfg, size_t row) {
-  const size_t want_q = ncfg * std::max<size_t>(row, 1);
-  if (ncfg <= w->small_cap && want_q <= w->small_qcap) return MPG_OK;
-  ncfg = std::max(ncfg, w->small_cap);
-  const size_t qcap = std::max(want_q, w->small_qcap);
-  if (w->h_q) hipHostFree(w->h_q);
-  if (w->h_hits) hipHostFree(w->h_hits);
-  if (w->d_qs) hipFree(w->d_qs);
-  if (w->d_ssc) hipFree(w->d_ssc);
-  if (w->h_ssc) hipHostFree(w->h_ssc);
-  w->d_ssc = nullptr;
-  w->h_ssc = nullptr;
-  w->h_q = nullptr;
-  w->h_hits = nullptr;
-  w->d_qs = nullptr;
-  w->small_cap = 0;
-  w->small_qcap = 0;
-  const size_t P = (size_t)std::max(w->dw.n_pairs, 1);
-  HIP_TRY(hipHostMalloc((void**)&w->h_q, sizeof(double) * qcap, hipHostMallocMapped | hipHostMallocCoherent));
-  HIP_TRY(hipHostGetDevicePointer((void**)&w->d_qmap, w->h_q, 0));
-  HIP_TRY(hipHostMalloc((void**)&w->h_hits, P * ncfg, hipHostMallocMapped | hipHostMallocCoherent));
-  HIP_TRY(hipHostGetDevicePointer((void**)&w->d_hits, w->h_hits, 0));
-  HIP_TRY(hipMalloc(&w->d_qs, sizeof(double) * qcap));
-  HIP_TRY(hipMalloc(&w->d_ssc, sizeof(double) * 2 * ncfg * std::max<int>(w->dw.dof, 1)));
-  HIP_TRY(hipHostMalloc((void**)&w->h_ssc, sizeof(double) * 2 * ncfg * std::max<int>(w->dw.dof, 1),
-                        hipHostMallocMapped | hipHostMallocCoherent));
-  HIP_TRY(hipHostGetDevicePointer((void**)&w->d_sscmap, w->h_ssc, 0));
-  w->small_cap = ncfg;
-  w->small_qcap = qcap;
-  return MPG_OK;
-}
 
-// (re)start the latency server; it takes `done` as the last batch served
-int srv_start(mpg_world* w) {
-  if (!w->srv_h) {
-    HIP_TRY(hipHostMalloc((void**)&w->srv_h, sizeof(SrvCtl), hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(w->srv_h, 0, sizeof(SrvCtl));
-    HIP_TRY(hipHostGetDevicePointer((void**)&w->srv_d, w->srv_h, 0));
-    HIP_TRY(hipStreamCreateWithFlags(&w->srv_stream, hipStreamNonBlocking));
-    HIP_TRY(hipFuncSetAttribute((const void*)lat_server_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)w->srv_lds));
-  }
-  for (int k = 0; k < kSrvMaxG; ++k) __atomic_store_n(&w->srv_h->gone[k], 0ull, __ATOMIC_RELAXED);
-  __atomic_store_n(&w->srv_h->quit, 0ull, __ATOMIC_RELEASE);
-  ++w->srv_starts;
-  hipLaunchKernelGGL(lat_server_kernel, dim3(w->srv_g), dim3(kSrvThreads), w->srv_lds, w->srv_stream, w->dw, w->srv_d,
-                     (unsigned long long)w->srv_idle_us * 100ull, w->srv_stats ? 1 : 0);
-  HIP_TRY(hipGetLastError());
-  w->srv_running = true;
-  return MPG_OK;
-}
+#include "mpg_collide_host.h"
 
-// one batch through the resident server: rows (q, host sin/cos) into the
-// control block, seq bumped, the host spins on `done`.  The server may have
-// left (idle) before it saw the request: every 50 us the host looks for
-// workgroups that have left (`gone`) without answering -- all of them (stream
-// complete): start it again; some of them: stop the rest and start all again.
-// Workgroups that are only slow (another stream sharing the GPU) are waited
-// for.  No answer within 2 s: the server is stopped, MPG_E_HIP (the caller
-// launches instead for a while, then tries the server again).
-int collide_served(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint32_t* pair_mask) {
-  if (w->srv_running && w->srv_quitting) {  // told to quit after a missed answer
-    if (hipStreamQuery(w->srv_stream) != hipSuccess) return set_error(MPG_E_HIP, "latency server has not left yet");
-    w->srv_running = false;
-    w->srv_quitting = false;
-  }
-  if (!w->srv_running) {
-    const int rc = srv_start(w);
-    if (rc) return rc;
-  }
-  SrvCtl* C = w->srv_h;
-  const int dof = w->dw.dof, W = w->dw.W;
-  for (int64_t c = 0; c < n; ++c) {
-    double* r = C->rows + c * 3 * dof;
-    std::memcpy(r, q + c * dof, sizeof(double) * (size_t)dof);
-    for (const int src : w->h_rev_src) mpg_sincos(q[c * dof + src], &r[dof + 2 * src], &r[dof + 2 * src + 1]);
-  }
-  const unsigned long long seq = (++w->srv_seq << 8) | (unsigned long long)n;
-  __atomic_store_n(&C->seq, seq, __ATOMIC_RELEASE);
-  const auto t0 = std::chrono::steady_clock::now();
-  long long next_us = 50;
-  bool forced = false;
-  auto all_done = [&] {
-    for (int k = 0; k < w->srv_g; ++k)
-      if (__atomic_load_n(&C->done[k], __ATOMIC_ACQUIRE) != seq) return false;
-    return true;
-  };
-  while (!all_done()) {
-    __builtin_ia32_pause();
-    const long long us =
-        std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-    if (us < next_us) continue;
-    next_us = us + 50;
-    hipError_t e = hipStreamQuery(w->srv_stream);
-    bool partial = false;  // a workgroup left before this request, others are still resident
-    for (int k = 0; k < w->srv_g && e == hipErrorNotReady; ++k)
-      partial |= __atomic_load_n(&C->gone[k], __ATOMIC_ACQUIRE) != 0ull &&
-                 __atomic_load_n(&C->done[k], __ATOMIC_ACQUIRE) != seq;
-    if (partial && !forced) {
-      // stop the ones still polling and start all again (once per request);
-      // they see quit within one poll, so this wait is short
-      __atomic_store_n(&C->quit, 1ull, __ATOMIC_RELEASE);
-      e = hipStreamSynchronize(w->srv_stream);
-      forced = true;
-    }
-    if (e == hipSuccess) {  // it left before this request: start it again
-      w->srv_running = false;
-      const int rc = srv_start(w);
-      if (rc) return rc;
-    } else if (e != hipErrorNotReady || us > 2000000) {
-      __atomic_store_n(&C->quit, 1ull, __ATOMIC_RELEASE);
-      w->srv_quitting = true;  // not waited for here: the next try checks that it has left
-      return set_error(MPG_E_HIP, "latency server did not answer");
-    }
-  }
-  ++w->srv_served;
-  if (w->prof) {  // a served batch counts as one narrow-stage "launch" of its post -> done time
-    std::lock_guard<std::mutex> lk(w->prof_mu);
-    w->prof_ms[MPG_STAGE_NARROW] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    w->prof_n[MPG_STAGE_NARROW] += 1;
-    w->prof_cfg += n;
-  }
-  if (w->srv_stats) {  // MPG_STATS: phase sums (rows, fk, spheres, narrow, publish), us
-    w->srv_stat[5] += 1.0;
-    for (int k = 0; k < 5; ++k) w->srv_stat[k] += (double)(C->phase[k + 1] - C->phase[k]) / 100.0;
-    w->srv_stat[6] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-  }
-  for (int64_t c = 0; c < n; ++c) {
-    uint32_t any = 0;
-    for (int k = 0; k < W; ++k) {
-      uint32_t v = 0;
-      for (int gg = 0; gg < w->srv_g; ++gg) v |= __atomic_load_n(&C->out[gg][c * W + k], __ATOMIC_RELAXED);
-      any |= v;
-      if (pair_mask) pair_mask[c * W + k] = v;
-    }
-    flags[c] = any ? 1 : 0;
-  }
-  return MPG_OK;
-}
-
-// one round trip: input to the device, one small_kernel launch writing hit
-// bytes straight into host memory, one synchronisation; the host folds the
-// hits into flags / pair masks
-// dev_in: the rows are already on the device (link poses assembled there for
-// a world with free frames); q is then not read
-template <bool FROM_POSES>
-int collide_small(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint32_t* pair_mask, hipStream_t s,
-                  const double* dev_in = nullptr) {
-  if (!FROM_POSES && w->srv_mode && w->srv_ok && n <= w->srv_max_n && !w->dw.dbg(3) && !w->dw.dbg(7) &&
-      (!w->srv_broken || std::chrono::steady_clock::now() >= w->srv_retry_at)) {
-    if (collide_served(w, q, n, flags, pair_mask) == MPG_OK) {
-      w->srv_broken = false;
-      return MPG_OK;
-    }
-    // the server could not be started or did not answer: launches for the
-    // next second, then the server is tried again
-    std::fprintf(stderr, "mplib_amd: latency server unavailable (%s); one launch per batch for 1 s\n",
-                 g_last_error.c_str());
-    w->srv_broken = true;
-    ++w->srv_fallbacks;
-    w->srv_retry_at = std::chrono::steady_clock::now() + std::chrono::seconds(1);
-    (void)hipGetLastError();
-  }
-  const size_t row = FROM_POSES ? (size_t)w->dw.n_links * 7 : (size_t)w->dw.dof;
-  const size_t cap = std::max<size_t>((size_t)n, std::min<size_t>((size_t)w->small_max, 256));
-  int rc = ensure_small(w, cap, row);
-  if (rc) return rc;
-  const int P = w->dw.n_pairs, W = w->dw.W;
-  std::memset(flags, 0, (size_t)n);
-  if (pair_mask) std::memset(pair_mask, 0, sizeof(uint32_t) * (size_t)n * W);
-  if (P == 0) return MPG_OK;
-  const double* qin = dev_in ? dev_in : w->small_zero_copy ? w->d_qmap : w->d_qs;
-  if (row && !dev_in) {  // zero-copy: the kernel reads the pinned rows directly, no copy launch
-    std::memcpy(w->h_q, q, sizeof(double) * (size_t)n * row);
-    if (!w->small_zero_copy)
-      HIP_TRY(hipMemcpyAsync(w->d_qs, w->h_q, sizeof(double) * (size_t)n * row, hipMemcpyHostToDevice, s));
-  }
-  const int n_tiles = (int)((n + 63) / 64);
-  const long long waves = (long long)P * n_tiles;
-  StageTimer t_small(w, s, MPG_STAGE_NARROW);
-  if (w->prof) w->prof_cfg += n;
-  // the smallest batches: joint sin/cos on the host (mpg_sincos, the device's
-  // own restatement of glibc's, bit for bit) into pinned mapped memory, one
-  // launch without the sin/cos work; up to small_inline_sc states: one launch
-  // with sin/cos inline; larger: a sin/cos launch first
-  const bool host_sc = !FROM_POSES && w->dw.dof > 0 && n <= w->small_host_sc;
-  const bool inline_sc = !host_sc && (FROM_POSES || (n <= w->small_inline_sc && w->dw.dof <= kLatScDof));
-  double* sc_src = w->d_ssc;
-  if (host_sc) {
-    const int dof = w->dw.dof;
-    for (int64_t c = 0; c < n; ++c)
-      for (const int src : w->h_rev_src) {
-        double sv, cv;
-        mpg_sincos(q[c * dof + src], &sv, &cv);
-        w->h_ssc[(c * dof + src) * 2] = sv;
-        w->h_ssc[(c * dof + src) * 2 + 1] = cv;
-      }
-    sc_src = w->d_sscmap;
-  }
-  if (!inline_sc && !host_sc && w->dw.dof > 0) {
-    const long long nt = n * w->dw.dof;
-    hipLaunchKernelGGL(small_sincos_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, w->dw, qin,
-                       (long long)n, w->d_ssc);
-    HIP_TRY(hipGetLastError());
-  }
-  const dim3 grid((unsigned)((waves + 3) / 4));
-  const bool host_staged = host_sc && w->dw.dof <= kLatScDof && w->dw.lat_rec_ok;
-  // the fewest states: their rows travel in the kernel arguments
-  const bool by_args = host_staged && n * 3 * (int64_t)w->dw.dof <= kLatIn && w->small_args;
-  LatIn args{};
-  if (by_args) {
-    const int dof = w->dw.dof;
-    for (int64_t c = 0; c < n; ++c) {
-      double* r = args.d + c * 3 * dof;
-      std::memcpy(r, q + c * dof, sizeof(double) * (size_t)dof);
-      std::memcpy(r + dof, w->h_ssc + c * 2 * dof, sizeof(double) * 2 * (size_t)dof);
-    }
-  }
-  auto launch = [&](auto kern) {  // every class instance reads the same sin/cos source
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, w->dw, qin, (long long)n, n_tiles, w->d_hits, sc_src, args);
-    return hipGetLastError();
-  };
-  auto pick = [&](auto k0, auto k1, auto k2, auto k3) {
-    return inline_sc ? launch(k1) : by_args ? launch(k3) : host_staged ? launch(k2) : launch(k0);
-  };
-  HIP_TRY(pick(small_kernel<FROM_POSES, CLS_CLOSED, 0>, small_kernel<FROM_POSES, CLS_CLOSED, 1>,
-               small_kernel<FROM_POSES, CLS_CLOSED, 2>, small_kernel<FROM_POSES, CLS_CLOSED, 3>));
-  if (w->any_octree)
-    HIP_TRY(pick(small_kernel<FROM_POSES, CLS_OCTREE, 0>, small_kernel<FROM_POSES, CLS_OCTREE, 1>,
-                 small_kernel<FROM_POSES, CLS_OCTREE, 2>, small_kernel<FROM_POSES, CLS_OCTREE, 3>));
-  if (w->any_mesh)
-    HIP_TRY(pick(small_kernel<FROM_POSES, CLS_MESH, 0>, small_kernel<FROM_POSES, CLS_MESH, 1>,
-                 small_kernel<FROM_POSES, CLS_MESH, 2>, small_kernel<FROM_POSES, CLS_MESH, 3>));
-  if (w->any_gjk)
-    HIP_TRY(pick(small_kernel<FROM_POSES, CLS_GJK, 0>, small_kernel<FROM_POSES, CLS_GJK, 1>,
-                 small_kernel<FROM_POSES, CLS_GJK, 2>, small_kernel<FROM_POSES, CLS_GJK, 3>));
-  t_small.stop();
-  HIP_TRY(hipStreamSynchronize(s));
-  const uint8_t* h = w->h_hits;
-  for (int p = 0; p < P; ++p) {
-    const uint8_t* hp = h + (size_t)p * n;
-    const uint32_t bit = 1u << (p & 31);
-    for (int64_t c = 0; c < n; ++c)
-      if (hp[c]) {
-        flags[c] = 1;
-        if (pair_mask) pair_mask[(size_t)c * W + (p >> 5)] |= bit;
-      }
-  }
-  return MPG_OK;
-}
-
-// stream-ordered for the caller: the side stream waits for everything queued
-// on `s` before the call, and `s` waits for the side stream's half
-template <bool FROM_POSES>
-int launch_collide_overlapped(mpg_world* w, const double* in, long long n, uint8_t* flags, uint32_t* masks,
-                              hipStream_t s) {
-  StreamPin pin(w, s);
-  // one chunk or less runs on the caller's stream alone: its two halves'
-  // cull and narrow kernels each fill the chip and are latency-bound, so on a
-  // second stream they only time-share the CUs (cfg3, 2^20: single stream
-  // +0.7-1.3 %; cfg4, 4 chunks: overlapped +16 %, profiles/r05a/overlap_ab.txt)
-  if (w->overlap_min <= 0 || n < w->overlap_min || n <= w->max_chunk)
-    return launch_collide<FROM_POSES>(w, in, n, flags, masks, s);
-  // one side stream and fork/join event pair per caller stream: callers on
-  // different streams (one host thread each, include/mpgpu.h) never record
-  // into or wait on each other's events, and each side stream has its own
-  // workspace (get_workspace keys by stream)
-  mpg_world::Side sd;
-  {
-    std::lock_guard<std::mutex> lk(w->ws_mu);
-    auto it = w->sides.find(s);
-    if (it == w->sides.end()) {
-      if (w->ws.find(s) == w->ws.end()) evict_streams_locked(w);
-      mpg_world::Side n{};
-      HIP_TRY(hipStreamCreateWithFlags(&n.side, hipStreamNonBlocking));
-      HIP_TRY(hipEventCreateWithFlags(&n.fork, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&n.join, hipEventDisableTiming));
-      it = w->sides.emplace(s, n).first;
-    }
-    it->second.last = ++w->ws_tick;
-    sd = it->second;
-  }
-  const size_t row = FROM_POSES ? (size_t)w->dw.n_links * 7 : (size_t)w->dw.dof;
-  // parts alternate between the caller's stream and the side stream
-  const int parts = std::max(2, w->overlap_parts);
-  const long long step = ((n + parts - 1) / parts + 63) / 64 * 64;
-  HIP_TRY(hipEventRecord(sd.fork, s));
-  HIP_TRY(hipStreamWaitEvent(sd.side, sd.fork, 0));
-  int k = 0;
-  for (long long off = 0; off < n; off += step, ++k) {
-    const long long m = std::min(step, n - off);
-    const int rc = launch_collide<FROM_POSES>(w, in + (size_t)off * row, m, flags + off,
-                                              masks ? masks + (size_t)off * w->dw.W : nullptr, (k & 1) ? sd.side : s);
-    if (rc) return rc;
-  }
-  HIP_TRY(hipEventRecord(sd.join, sd.side));
-  HIP_TRY(hipStreamWaitEvent(s, sd.join, 0));
-  return MPG_OK;
-}
-
-// Host buffers above the latency path's sizes (mpg_hostpipe.h): per chunk,
-// the rows are copied from the caller's (pageable) buffer on the ring's copy
-// stream by the feeder thread; the compute stream waits for them, runs the
-// collide pipeline into the slot's device outputs, packs the colliding
-// configurations' mask rows straight into pinned host memory and copies the
-// flags back; the issuing thread unpacks a finished chunk into the caller's
-// buffers while the next chunks are in flight.  PCIe carries the rows in
-// (8 * row B per configuration) and 1 + 4W B per colliding configuration
-// back instead of 1 + 4W B per configuration.  Caller holds host_mu.
-template <bool FROM_POSES>
-struct HostPipeOps {
-  mpg_world* w;
-  const double* q;
-  uint8_t* flags;
-  uint32_t* pair_mask;
-  hipStream_t s;
-  size_t row;
-  // the first error text of the feeder / issuer threads (g_last_error is per
-  // thread); finish() runs on the caller's thread and sets g_last_error itself
-  std::mutex err_mu;
-  std::string thread_err;
-  bool fin_failed = false;
-
-  int thread_fail(int rc, const std::string& msg) {
-    std::lock_guard<std::mutex> lk(err_mu);
-    if (thread_err.empty()) thread_err = msg;
-    return rc;
-  }
-  int bind_thread() {
-    if (hipSetDevice(w->device) != hipSuccess) return thread_fail(MPG_E_HIP, "hipSetDevice failed in a pipeline thread");
-    return MPG_OK;
-  }
-  double t_in = 0, t_issue = 0, t_wait = 0, t_unpack = 0;
-  static double us_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-  }
-  int h2d(int64_t, int j, int64_t start, int64_t m) {
-    auto& R = w->ring;
-    const auto t0 = std::chrono::steady_clock::now();
-    hipError_t e = hipSuccess;
-    if (row) e = hipMemcpyAsync(R.d_in[j], q + (size_t)start * row, sizeof(double) * (size_t)m * row,
-                                hipMemcpyHostToDevice, R.h2d);
-    if (e == hipSuccess) e = hipEventRecord(R.e_in[j], R.h2d);
-    t_in += us_since(t0);
-    if (e != hipSuccess) return thread_fail(MPG_E_HIP, std::string("host pipeline input copy failed: ") + hipGetErrorString(e));
-    return MPG_OK;
-  }
-  int issue(int64_t k, int j, int64_t start, int64_t m) {
-    const int rc = issue_chunk(k, j, start, m);
-    return rc ? thread_fail(rc, g_last_error) : MPG_OK;  // g_last_error of this (issuer) thread
-  }
-  int issue_chunk(int64_t k, int j, int64_t, int64_t m) {
-    auto& R = w->ring;
-    const auto t0 = std::chrono::steady_clock::now();
-    const hipStream_t cs = (w->ring_streams > 1 && (k & 1)) ? R.side : s;
-    HIP_TRY(hipStreamWaitEvent(cs, R.e_in[j], 0));
-    const int rc = launch_collide<FROM_POSES>(w, R.d_in[j], m, R.d_fl[j], R.d_mk[j], cs);
-    if (rc) return rc;
-    // results straight into pinned host memory: the flags, and with masks the
-    // block counts and the packed rows (no copy launches)
-    const int Wp = pair_mask ? w->dw.W : 0;
-    const unsigned nb = (unsigned)((m + kPackCfg - 1) / kPackCfg);
-    if (Wp > 0) {
-      hipLaunchKernelGGL(flag_count_kernel, dim3(nb), dim3(256), 0, cs, R.d_fl[j], (long long)m, R.d_bcnt[j],
-                         R.h_bcnt_d[j]);
-      HIP_TRY(hipGetLastError());
-    }
-    const size_t lds = sizeof(uint32_t) * 256 * (size_t)Wp;
-    if (lds <= 64 * 1024)
-      hipLaunchKernelGGL(mask_pack_kernel<true>, dim3(nb), dim3(256), lds, cs, R.d_fl[j], R.d_mk[j], (long long)m, Wp,
-                         R.d_bcnt[j], R.h_mk_d[j], R.h_fl_d[j]);
-    else
-      hipLaunchKernelGGL(mask_pack_kernel<false>, dim3(nb), dim3(256), 0, cs, R.d_fl[j], R.d_mk[j], (long long)m, Wp,
-                         R.d_bcnt[j], R.h_mk_d[j], R.h_fl_d[j]);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(R.e_done[j], cs));
-    t_issue += us_since(t0);
-    return MPG_OK;
-  }
-  int finish(int64_t, int j, int64_t start, int64_t m) {
-    auto& R = w->ring;
-    const auto t0 = std::chrono::steady_clock::now();
-    const hipError_t e = hipEventSynchronize(R.e_done[j]);
-    if (e != hipSuccess) {
-      fin_failed = true;
-      return set_error(MPG_E_HIP, std::string("host pipeline: ") + hipGetErrorString(e));
-    }
-    const auto t1 = std::chrono::steady_clock::now();
-    t_wait += std::chrono::duration<double, std::micro>(t1 - t0).count();
-    mpg_hostpipe::unpack_chunk(w->pool.get(), R.h_fl[j], R.h_mk[j], R.h_bcnt[j], kPackCfg, m, w->dw.W, flags + start,
-                               pair_mask && w->dw.W > 0 ? pair_mask + (size_t)start * w->dw.W : nullptr);
-    t_unpack += us_since(t1);
-    return MPG_OK;
-  }
-  void drain() {
-    hipStreamSynchronize(w->ring.h2d);
-    hipStreamSynchronize(w->ring.side);
-    hipStreamSynchronize(s);
-  }
-};
-
-template <bool FROM_POSES>
-int collide_host_pipelined(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint32_t* pair_mask,
-                           hipStream_t s) {
-  const mpg_hostpipe::Plan p =
-      mpg_hostpipe::plan(n, w->ring_chunk, 1 << 15, mpg_world::kRing, w->ring_head, w->ring_tail);
-  const size_t row = FROM_POSES ? (size_t)w->dw.n_links * 7 : (size_t)w->dw.dof;
-  int rc = ensure_ring(w, (size_t)p.chunk, row);
-  if (rc) return rc;
-  if (!w->pool && w->host_threads > 1 && p.chunk >= 2 * kPackCfg)
-    w->pool.reset(new mpg_hostpipe::Pool(w->host_threads - 1));
-  HostPipeOps<FROM_POSES> ops{w, q, flags, pair_mask, s, row};
-  const auto t0 = std::chrono::steady_clock::now();
-  rc = mpg_hostpipe::run(p, n, ops);
-  if (w->srv_stats) {
-    const double v[6] = {1.0, ops.t_in, ops.t_issue, ops.t_wait, ops.t_unpack, HostPipeOps<FROM_POSES>::us_since(t0)};
-    for (int k = 0; k < 6; ++k) w->hp_stat[k] += v[k];
-  }
-  if (rc && !ops.fin_failed) return set_error(rc, ops.thread_err);
-  return rc;
-}
-
-int collide_free(mpg_world* w, const double* q, const double* free_pose, int64_t free_rows, int64_t n, uint8_t* flags,
-                 uint32_t* pair_mask, int mem, void* stream);
-int check_free_poses(const double* p7, size_t count);
-
-template <bool FROM_POSES>
-int collide_common(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint32_t* pair_mask, int mem,
-                   void* stream) {
-  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
-  // joint-value rows of a world with free frames: at its current poses
-  if (!FROM_POSES && w->dw.n_free) return collide_free(w, q, nullptr, 0, n, flags, pair_mask, mem, stream);
-  if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
-  const size_t row = FROM_POSES ? (size_t)w->dw.n_links * 7 : (size_t)w->dw.dof;
-  // a world without inputs (dof 0) may pass q = NULL
-  if (n > 0 && ((!q && row > 0) || !flags)) return set_error(MPG_E_INVALID, "input/flags is NULL");
-  // host-memory link-pose rows: the free frames' columns are checked as every host-memory free pose is
-  if (FROM_POSES && mem == MPG_MEM_HOST && w->dw.n_free)
-    for (int64_t i = 0; i < n; ++i) {
-      const int rc = check_free_poses(q + ((size_t)i * w->dw.n_links + (w->dw.n_links - w->dw.n_free)) * 7,
-                                      (size_t)w->dw.n_free);
-      if (rc) return rc;
-    }
-  HIP_TRY(hipSetDevice(w->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (mem == MPG_MEM_DEVICE) return launch_collide_overlapped<FROM_POSES>(w, q, n, flags, pair_mask, s);
-  if (mem != MPG_MEM_HOST) return set_error(MPG_E_INVALID, "bad mem kind");
-  std::lock_guard<std::mutex> lk(w->host_mu);
-  if (!s && w->own_stream) s = w->own_stream;
-  if (n == 0) return MPG_OK;
-  if (n <= w->small_max) return collide_small<FROM_POSES>(w, q, n, flags, pair_mask, s);
-  return collide_host_pipelined<FROM_POSES>(w, q, n, flags, pair_mask, s);
-}
-
-// ---------------------------------------------------------------------------
-// Worlds with free frames.  Every pair evaluation of such a world runs on
-// link-pose rows: fk_free_kernel writes the kinematic links' poses from q and
-// copies the free frames' poses next to them (per row, shared, or the world's
-// current ones), then the link-pose instances of the cull / narrow / small
-// kernels evaluate the rows.  Device calls keep the rows in the caller
-// stream's workspace and read the caller's pose array directly: no state in
-// the world, no synchronisation.  Worlds without free frames never come here.
-// ---------------------------------------------------------------------------
-constexpr long long kFreeChunk = 1 << 18;  // rows per pass: n_links * 56 B each
-
-// device buffers; free_pose NULL = current poses; free_stride in doubles
-int launch_collide_free(mpg_world* w, const double* q, const double* free_pose, long long free_stride, long long n,
-                        uint8_t* flags, uint32_t* masks, hipStream_t s, const ContactOut* co = nullptr) {
-  if (n == 0) return MPG_OK;
-  StreamPin pin(w, s);
-  const long long chunk = std::min<long long>(n, std::min<long long>(kFreeChunk, w->max_chunk));
-  mpg_world::Workspace* ws = nullptr;
-  int rc = get_workspace(w, s, chunk, &ws);
-  if (rc) return rc;
-  const size_t lrow = (size_t)w->dw.n_links * 7;
-  if (ws->links_cap < chunk) {  // this stream's queued work may still read the old rows
-    if (ws->links) {
-      HIP_TRY(hipStreamSynchronize(s));
-      HIP_TRY(hipFree(ws->links));
-    }
-    ws->links = nullptr;
-    ws->links_cap = 0;
-    HIP_TRY(hipMalloc(&ws->links, sizeof(double) * lrow * (size_t)chunk));
-    ws->links_cap = chunk;
-  }
-  const size_t P = (size_t)w->dw.n_pairs;
-  for (long long off = 0; off < n; off += chunk) {
-    const long long m = std::min(chunk, n - off);
-    hipLaunchKernelGGL(fk_free_kernel, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, w->dw,
-                       q ? q + (size_t)off * w->dw.dof : nullptr, m, ws->links,
-                       free_pose ? free_pose + (size_t)off * free_stride : nullptr, free_stride);
-    HIP_TRY(hipGetLastError());
-    ContactOut sub{};
-    if (co) sub = ContactOut{co->depth + off * P, co->normal + off * P * 3, co->pos + off * P * 3};
-    rc = launch_collide<true>(w, ws->links, m, flags + off, masks ? masks + (size_t)off * w->dw.W : nullptr, s,
-                              co ? &sub : nullptr);
-    if (rc) return rc;
-  }
-  return MPG_OK;
-}
-
-// joint-value rows on the device, evaluated at the world's current free poses
-int launch_collide_q(mpg_world* w, const double* q, long long n, uint8_t* flags, uint32_t* masks, hipStream_t s,
-                     const ContactOut* co = nullptr) {
-  if (w->dw.n_free) return launch_collide_free(w, q, nullptr, 0, n, flags, masks, s, co);
-  return launch_collide<false>(w, q, n, flags, masks, s, co);
-}
-
-// finite values and unit quaternions (kFreeQuatTol) of host-memory free poses
-int check_free_poses(const double* p7, size_t count) {
-  for (size_t k = 0; k < count; ++k) {
-    const double* p = p7 + 7 * k;
-    if (!finite_all(p, 7)) return set_error(MPG_E_INVALID, "non-finite free pose");
-    const double nq = std::sqrt(p[3] * p[3] + p[4] * p[4] + p[5] * p[5] + p[6] * p[6]);
-    if (!(std::fabs(nq - 1.0) <= kFreeQuatTol))
-      return set_error(MPG_E_INVALID, "free pose quaternion is not of unit norm (within 1e-6)");
-  }
-  return MPG_OK;
-}
-
-// host buffers: rows staged to the device in passes of kFreeChunk; batches up
-// to the latency path's size take its one-launch kernel on the assembled rows
-int collide_free_host(mpg_world* w, const double* q, const double* free_pose, long long free_rows, int64_t n,
-                      uint8_t* flags, uint32_t* pair_mask, hipStream_t s) {
-  auto& F = w->free_stage;
-  auto grow = [&](void** p, size_t& cap, size_t want) -> int {
-    if (cap >= want) return MPG_OK;
-    if (*p) HIP_TRY(hipFree(*p));
-    *p = nullptr;
-    cap = 0;
-    HIP_TRY(hipMalloc(p, want));
-    cap = want;
-    return MPG_OK;
-  };
-  const size_t dof = (size_t)w->dw.dof, frow = (size_t)w->dw.n_free * 7, lrow = (size_t)w->dw.n_links * 7;
-  const size_t W = (size_t)w->dw.W;
-  const long long chunk = std::min<long long>(n, kFreeChunk);
-  int rc;
-  if ((rc = grow((void**)&F.q, F.q_cap, sizeof(double) * std::max<size_t>(1, dof * chunk)))) return rc;
-  if ((rc = grow((void**)&F.fp, F.fp_cap, sizeof(double) * frow * (free_rows > 1 ? chunk : 1)))) return rc;
-  if ((rc = grow((void**)&F.links, F.links_cap, sizeof(double) * lrow * chunk))) return rc;
-  // the latency kernel reads all n rows at once: only a batch that one pass
-  // assembles (small_batch_max may be set above kFreeChunk)
-  const bool small = n <= w->small_max && n <= chunk;
-  if (!small) {
-    if ((rc = grow((void**)&F.fl, F.fl_cap, (size_t)chunk))) return rc;
-    if ((rc = grow((void**)&F.mk, F.mk_cap, sizeof(uint32_t) * W * chunk))) return rc;
-  }
-  if (free_pose && free_rows == 1)
-    HIP_TRY(hipMemcpyAsync(F.fp, free_pose, sizeof(double) * frow, hipMemcpyHostToDevice, s));
-  for (long long off = 0; off < n; off += chunk) {
-    const long long m = std::min<long long>(chunk, n - off);
-    if (dof) HIP_TRY(hipMemcpyAsync(F.q, q + (size_t)off * dof, sizeof(double) * dof * m, hipMemcpyHostToDevice, s));
-    if (free_pose && free_rows > 1)
-      HIP_TRY(hipMemcpyAsync(F.fp, free_pose + (size_t)off * frow, sizeof(double) * frow * m, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(fk_free_kernel, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, w->dw, F.q, m, F.links,
-                       free_pose ? F.fp : nullptr, free_rows > 1 ? (long long)frow : 0ll);
-    HIP_TRY(hipGetLastError());
-    if (small) return collide_small<true>(w, nullptr, n, flags, pair_mask, s, F.links);
-    rc = launch_collide<true>(w, F.links, m, F.fl, pair_mask ? F.mk : nullptr, s);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(flags + off, F.fl, (size_t)m, hipMemcpyDeviceToHost, s));
-    if (pair_mask)
-      HIP_TRY(hipMemcpyAsync(pair_mask + (size_t)off * W, F.mk, sizeof(uint32_t) * W * m, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  }
-  return MPG_OK;
-}
-
-int collide_free(mpg_world* w, const double* q, const double* free_pose, int64_t free_rows, int64_t n, uint8_t* flags,
-                 uint32_t* pair_mask, int mem, void* stream) {
-  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
-  if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
-  if (n > 0 && ((!q && w->dw.dof > 0) || !flags)) return set_error(MPG_E_INVALID, "input/flags is NULL");
-  if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
-  if (free_pose && free_rows != 1 && free_rows != n)
-    return set_error(MPG_E_INVALID, "free_rows must be 1 (shared by the batch) or n (one pose set per configuration)");
-  if (free_pose && w->dw.n_free == 0) return set_error(MPG_E_INVALID, "the world has no free frames");
-  if (w->dw.n_free == 0) return collide_common<false>(w, q, n, flags, pair_mask, mem, stream);
-  HIP_TRY(hipSetDevice(w->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const long long fstride = free_rows > 1 ? (long long)w->dw.n_free * 7 : 0ll;
-  if (mem == MPG_MEM_DEVICE) return launch_collide_free(w, q, free_pose, fstride, n, flags, pair_mask, s);
-  if (free_pose) {
-    const int rc = check_free_poses(free_pose, (size_t)free_rows * w->dw.n_free);
-    if (rc) return rc;
-  }
-  std::lock_guard<std::mutex> lk(w->host_mu);
-  if (!s && w->own_stream) s = w->own_stream;
-  if (n == 0) return MPG_OK;
-  return collide_free_host(w, q, free_pose, free_rows, n, flags, pair_mask, s);
-}
 }  // namespace
 
 extern "C" {
 
-int mpg_release_stream(mpg_world* w, void* stream) {
-  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
-  HIP_TRY(hipSetDevice(w->device));
-  std::lock_guard<std::mutex> lk(w->ws_mu);
-  const auto b = w->busy.find(static_cast<hipStream_t>(stream));
-  if (b != w->busy.end() && b->second > 0) return set_error(MPG_E_INVALID, "stream has a call in progress");
-  release_stream_locked(w, static_cast<hipStream_t>(stream));
-  return MPG_OK;
-}
-
-int mpg_set_small_batch_max(mpg_world* w, int64_t n) {
-  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
-  if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
-  std::lock_guard<std::mutex> lk(w->host_mu);
-  w->small_max = n;
-  return MPG_OK;
-}
-
-int mpg_collide_batch(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint32_t* pair_mask, int mem,
-                      void* stream) {
-  return collide_common<false>(w, q, n, flags, pair_mask, mem, stream);
-}
-
-int mpg_collide_batch_multi(mpg_world* const* worlds, int32_t n_worlds, const double* q, int64_t n, uint8_t* flags,
-                            uint32_t* pair_mask) {
-  if (n_worlds <= 0 || !worlds) return set_error(MPG_E_INVALID, "no worlds");
-  if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
-  if (n > 0 && (!q || !flags)) return set_error(MPG_E_INVALID, "q / flags is NULL");
-  mpg_world_info i0{};
-  for (int k = 0; k < n_worlds; ++k) {
-    mpg_world_info ik{};
-    if (!worlds[k]) return set_error(MPG_E_INVALID, "world " + std::to_string(k) + " is NULL");
-    mpg_world_get_info(worlds[k], &ik);
-    if (k == 0) {
-      i0 = ik;
-    } else if (ik.dof != i0.dof || ik.n_pairs != i0.n_pairs || ik.mask_words != i0.mask_words ||
-               ik.n_links != i0.n_links || ik.snapshot_bytes != i0.snapshot_bytes ||
-               worlds[k]->snapshot_hash != worlds[0]->snapshot_hash) {
-      return set_error(MPG_E_INVALID, "world " + std::to_string(k) + " was not built from world 0's descriptor");
-    }
-    for (int j = 0; j < k; ++j)
-      if (worlds[j] == worlds[k]) return set_error(MPG_E_INVALID, "a world is listed twice");
-  }
-  std::vector<int> rc(n_worlds, MPG_OK);
-  std::vector<std::string> err(n_worlds);
-  auto run = [&](int k) {
-    int64_t start = 0, count = 0;
-    mpg_shard_range(n, k, n_worlds, &start, &count);
-    if (count == 0) return;
-    rc[k] = mpg_collide_batch(worlds[k], q + (size_t)start * i0.dof, count, flags + start,
-                              pair_mask ? pair_mask + (size_t)start * i0.mask_words : nullptr, MPG_MEM_HOST, nullptr);
-    if (rc[k]) err[k] = g_last_error;  // the worker thread's error text
-  };
-  std::vector<std::thread> th;
-  for (int k = 1; k < n_worlds; ++k) th.emplace_back(run, k);
-  run(0);
-  for (auto& t : th) t.join();
-  for (int k = 0; k < n_worlds; ++k)
-    if (rc[k]) return set_error(rc[k], "world " + std::to_string(k) + ": " + err[k]);
-  return MPG_OK;
-}
-
-int mpg_shard_range(int64_t n, int32_t k, int32_t n_parts, int64_t* start, int64_t* count) {
-  if (n < 0 || n_parts <= 0 || k < 0 || k >= n_parts || !start || !count)
-    return set_error(MPG_E_INVALID, "mpg_shard_range: bad arguments");
-  // contiguous shards, the first n % n_parts one row longer (mplib_amd.dist.shard_range)
-  const int64_t base = n / n_parts, rem = n % n_parts;
-  *start = k * base + std::min<int64_t>(k, rem);
-  *count = base + (k < rem ? 1 : 0);
-  return MPG_OK;
-}
-
-int mpg_collide_batch_multi_device(mpg_world* const* worlds, int32_t n_worlds, const double* const* q,
-                                   const int64_t* counts, uint8_t* const* flags, uint32_t* const* pair_mask,
-                                   void* const* streams, uint8_t* gather_flags, uint32_t* gather_masks) {
-  if (n_worlds <= 0 || !worlds) return set_error(MPG_E_INVALID, "no worlds");
-  if (!counts || !q || !flags) return set_error(MPG_E_INVALID, "counts / q / flags array is NULL");
-  if (gather_masks && !pair_mask) return set_error(MPG_E_INVALID, "gather_masks needs pair_mask");
-  for (int k = 0; k < n_worlds; ++k) {
-    if (!worlds[k]) return set_error(MPG_E_INVALID, "world " + std::to_string(k) + " is NULL");
-    if (counts[k] < 0) return set_error(MPG_E_INVALID, "counts[" + std::to_string(k) + "] < 0");
-    for (int j = 0; j < k; ++j)
-      if (worlds[j] == worlds[k]) return set_error(MPG_E_INVALID, "a world is listed twice");
-  }
-  const mpg_world* w0 = worlds[0];
-  for (int k = 0; k < n_worlds; ++k) {
-    const mpg_world* wk = worlds[k];
-    if (wk->dw.dof != w0->dw.dof || wk->dw.n_pairs != w0->dw.n_pairs || wk->dw.W != w0->dw.W ||
-        wk->blob_bytes != w0->blob_bytes || wk->snapshot_hash != w0->snapshot_hash)
-      return set_error(MPG_E_INVALID, "world " + std::to_string(k) + " was not built from world 0's descriptor");
-    if (counts[k] > 0 && ((!q[k] && wk->dw.dof > 0) || !flags[k]))
-      return set_error(MPG_E_INVALID, "shard " + std::to_string(k) + ": q / flags is NULL");
-    if (counts[k] > 0 && gather_masks && !pair_mask[k])
-      return set_error(MPG_E_INVALID, "shard " + std::to_string(k) + ": gather_masks needs its pair_mask");
-  }
-  const int W = w0->dw.W;
-  std::vector<int64_t> off(n_worlds + 1, 0);
-  for (int k = 0; k < n_worlds; ++k) off[k + 1] = off[k] + counts[k];
-  const bool gather = gather_flags || gather_masks;
-  if (gather) {  // direct peer copies over xGMI from every other device into device 0
-    HIP_TRY(hipSetDevice(w0->device));
-    for (int k = 1; k < n_worlds; ++k) {
-      if (worlds[k]->device == w0->device) continue;
-      int can = 0;
-      HIP_TRY(hipDeviceCanAccessPeer(&can, w0->device, worlds[k]->device));
-      if (!can) continue;  // hipMemcpyPeerAsync still works, staged by the runtime
-      const hipError_t e = hipDeviceEnablePeerAccess(worlds[k]->device, 0);
-      if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled)
-        return set_error(MPG_E_HIP, std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e));
-      (void)hipGetLastError();
-    }
-  }
-  std::vector<int> rc(n_worlds, MPG_OK);
-  std::vector<std::string> err(n_worlds);
-  auto run = [&](int k) {
-    mpg_world* w = worlds[k];
-    hipStream_t s = streams ? static_cast<hipStream_t>(streams[k]) : nullptr;
-    uint32_t* mk = pair_mask ? pair_mask[k] : nullptr;
-    auto fail = [&](int code, const std::string& m) {
-      rc[k] = code;
-      err[k] = m;
-    };
-    if (hipSetDevice(w->device) != hipSuccess) return fail(MPG_E_HIP, "hipSetDevice failed");
-    if (counts[k] > 0) {
-      const int r = mpg_collide_batch(w, q[k], counts[k], flags[k], mk, MPG_MEM_DEVICE, s);
-      if (r) return fail(r, g_last_error);
-    }
-    if (!gather) return;
-    hipError_t e = hipSuccess;
-    if (counts[k] > 0 && gather_flags)
-      e = hipMemcpyPeerAsync(gather_flags + off[k], w0->device, flags[k], w->device, (size_t)counts[k], s);
-    if (e == hipSuccess && counts[k] > 0 && gather_masks)
-      e = hipMemcpyPeerAsync(gather_masks + off[k] * W, w0->device, mk, w->device,
-                             sizeof(uint32_t) * (size_t)counts[k] * W, s);
-    if (e == hipSuccess && k > 0) {
-      if (!w->gather_ev) e = hipEventCreateWithFlags(&w->gather_ev, hipEventDisableTiming);
-      if (e == hipSuccess) e = hipEventRecord(w->gather_ev, s);
-    }
-    if (e != hipSuccess) return fail(MPG_E_HIP, std::string("gather: ") + hipGetErrorString(e));
-  };
-  std::vector<std::thread> th;
-  for (int k = 1; k < n_worlds; ++k) th.emplace_back(run, k);
-  run(0);
-  for (auto& t : th) t.join();
-  for (int k = 0; k < n_worlds; ++k)
-    if (rc[k]) return set_error(rc[k], "world " + std::to_string(k) + ": " + err[k]);
-  if (gather) {  // streams[0] orders after every shard's copies
-    HIP_TRY(hipSetDevice(w0->device));
-    hipStream_t s0 = streams ? static_cast<hipStream_t>(streams[0]) : nullptr;
-    for (int k = 1; k < n_worlds; ++k) HIP_TRY(hipStreamWaitEvent(s0, worlds[k]->gather_ev, 0));
-  }
-  return MPG_OK;
-}
-
-int mpg_collide_link_poses(mpg_world* w, const double* link_pose, int64_t n, uint8_t* flags, uint32_t* pair_mask,
-                           int mem, void* stream) {
-  return collide_common<true>(w, link_pose, n, flags, pair_mask, mem, stream);
-}
-
-int mpg_collide_batch_free(mpg_world* w, const double* q, const double* free_pose, int64_t free_rows, int64_t n,
-                           uint8_t* flags, uint32_t* pair_mask, int mem, void* stream) {
-  return collide_free(w, q, free_pose, free_rows, n, flags, pair_mask, mem, stream);
-}
-
-int mpg_world_set_free_poses(mpg_world* w, const double* pose7) {
-  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
-  if (w->dw.n_free == 0) return set_error(MPG_E_INVALID, "the world has no free frames");
-  if (!pose7) return set_error(MPG_E_INVALID, "pose7 is NULL");
-  const int rc = check_free_poses(pose7, (size_t)w->dw.n_free);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(w->device));
-  // calls in flight read the buffer: wait for them, then overwrite it in place
-  std::lock_guard<std::mutex> lk(w->host_mu);
-  HIP_TRY(hipDeviceSynchronize());
-  std::copy(pose7, pose7 + w->free_host.size(), w->free_host.begin());
-  HIP_TRY(hipMemcpy(w->free_dev, w->free_host.data(), sizeof(double) * w->free_host.size(), hipMemcpyHostToDevice));
-  return MPG_OK;
-}
-
-int mpg_world_get_free_info(const mpg_world* w, int32_t* n_free, double* far_radius, double* pose7) {
-  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
-  if (n_free) *n_free = w->dw.n_free;
-  if (far_radius) *far_radius = w->dw.far_r;
-  if (pose7) std::copy(w->free_host.begin(), w->free_host.end(), pose7);
-  return MPG_OK;
-}
-
-int mpg_check_motion_batch(mpg_world* w, const double* q_from, const double* q_to, int64_t n, uint32_t so2_mask,
-                           double longest_valid_segment, uint8_t* valid, int32_t* first_invalid, int32_t* segments,
-                           int mem, void* stream) {
-  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
-  if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
-  if (n > 0 && (!q_from || !q_to || !valid)) return set_error(MPG_E_INVALID, "from/to/valid is NULL");
-  if (!(longest_valid_segment > 0.0)) return set_error(MPG_E_INVALID, "longest_valid_segment must be > 0");
-  if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
-  if (w->dw.dof > 32) return set_error(MPG_E_UNSUPPORTED, "motion validation supports dof <= 32");
-  if (n == 0) return MPG_OK;
-  HIP_TRY(hipSetDevice(w->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  std::lock_guard<std::mutex> lk(w->motion_mu);
-  const int dof = w->dw.dof;
-  const size_t eb = sizeof(double) * (size_t)n * dof;
-  auto& M = w->motion;
-  auto grow = [&](void** p, size_t& cap, size_t want) { return scratch_grow(M.last, p, cap, want); };
-  int rc = scratch_begin(M.last, s);
-  if (rc) return rc;
-  if ((rc = grow((void**)&M.edges, M.edges_cap, 2 * eb))) return rc;
-  if ((rc = grow((void**)&M.segs, M.segs_cap, sizeof(int32_t) * n))) return rc;
-  if ((rc = grow((void**)&M.offs, M.offs_cap, sizeof(long long) * n))) return rc;
-  if ((rc = grow((void**)&M.out, M.out_cap, (sizeof(int32_t) + 1) * n))) return rc;
-  const double* from = q_from;
-  const double* to = q_to;
-  if (mem == MPG_MEM_HOST) {
-    HIP_TRY(hipMemcpyAsync(M.edges, q_from, eb, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(M.edges + (size_t)n * dof, q_to, eb, hipMemcpyHostToDevice, s));
-    from = M.edges;
-    to = M.edges + (size_t)n * dof;
-  }
-  const unsigned grid = (unsigned)((n + 255) / 256);
-  hipLaunchKernelGGL(motion_count_kernel, dim3(grid), dim3(256), 0, s, from, to, (long long)n, dof, so2_mask,
-                     longest_valid_segment, M.segs);
-  HIP_TRY(hipGetLastError());
-  // the state count decides the allocation: one synchronisation per call
-  std::vector<int32_t> segs((size_t)n);
-  HIP_TRY(hipMemcpyAsync(segs.data(), M.segs, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  std::vector<long long> offs((size_t)n);
-  long long total = 0;
-  for (int64_t e = 0; e < n; ++e) {
-    offs[e] = total;
-    total += segs[e];
-  }
-  HIP_TRY(hipMemcpyAsync(M.offs, offs.data(), sizeof(long long) * n, hipMemcpyHostToDevice, s));
-  if ((rc = grow((void**)&M.states, M.states_cap, sizeof(double) * (size_t)total * dof))) return rc;
-  if ((rc = grow((void**)&M.flags, M.flags_cap, (size_t)total))) return rc;
-  hipLaunchKernelGGL(motion_states_kernel, dim3(grid), dim3(256), 0, s, from, to, (long long)n, dof, so2_mask, M.segs,
-                     M.offs, M.states);
-  HIP_TRY(hipGetLastError());
-  rc = launch_collide_q(w, M.states, total, M.flags, nullptr, s);
-  if (rc) return rc;
-  uint8_t* d_valid = mem == MPG_MEM_DEVICE ? valid : reinterpret_cast<uint8_t*>(M.out + n);
-  int32_t* d_first = first_invalid ? (mem == MPG_MEM_DEVICE ? first_invalid : M.out) : nullptr;
-  hipLaunchKernelGGL(motion_reduce_kernel, dim3(grid), dim3(256), 0, s, M.flags, (long long)n, M.segs, M.offs, d_valid,
-                     d_first);
-  HIP_TRY(hipGetLastError());
-  if (mem == MPG_MEM_HOST) {
-    HIP_TRY(hipMemcpyAsync(valid, d_valid, n, hipMemcpyDeviceToHost, s));
-    if (first_invalid) HIP_TRY(hipMemcpyAsync(first_invalid, d_first, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (segments) std::memcpy(segments, segs.data(), sizeof(int32_t) * n);
-  } else if (segments) {
-    HIP_TRY(hipMemcpyAsync(segments, M.segs, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, s));
-  }
-  HIP_TRY(hipEventRecord(M.last, s));
-  return MPG_OK;
-}
-
-int mpg_distance_batch(mpg_world* w, const double* q, int64_t n, int32_t n_self_pairs, double* d_self,
-                       int32_t* p_self, double* d_others, int32_t* p_others, int mem, void* stream) {
-  return mpg_distance_batch_ex(w, q, n, n_self_pairs, 0, d_self, p_self, nullptr, d_others, p_others, nullptr, mem,
-                               stream);
-}
-
-int mpg_distance_batch_ex(mpg_world* w, const double* q, int64_t n, int32_t n_self_pairs, int32_t flags,
-                          double* d_self, int32_t* p_self, double* pts_self, double* d_others, int32_t* p_others,
-                          double* pts_others, int mem, void* stream) {
-  mpg_distance_request req;
-  req.flags = flags;
-  req.distance_tolerance = 1e-6;
-  return mpg_distance_batch_req(w, q, n, n_self_pairs, &req, d_self, p_self, pts_self, d_others, p_others, pts_others,
-                                mem, stream);
-}
-
-int mpg_distance_batch_req(mpg_world* w, const double* q, int64_t n, int32_t n_self_pairs,
-                           const mpg_distance_request* req, double* d_self, int32_t* p_self, double* pts_self,
-                           double* d_others, int32_t* p_others, double* pts_others, int mem, void* stream) {
-  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
-  if (!req) return set_error(MPG_E_INVALID, "request is NULL");
-  if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
-  if (n_self_pairs < 0 || n_self_pairs > w->dw.n_pairs) return set_error(MPG_E_INVALID, "bad n_self_pairs");
-  if (n > 0 && ((!q && w->dw.dof > 0) || !d_self || !p_self || !d_others || !p_others))
-    return set_error(MPG_E_INVALID, "NULL buffer");
-  if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
-  const int32_t flags = req->flags;
-  if (flags & ~(MPG_DISTANCE_SIGNED | MPG_DISTANCE_NEAREST_POINTS | MPG_DISTANCE_GJK_INDEP))
-    return set_error(MPG_E_INVALID, "bad flags");
-  if (!(req->distance_tolerance >= 0.0)) return set_error(MPG_E_INVALID, "bad distance_tolerance");
-  if (w->has_octree2)
-    return set_error(MPG_E_UNSUPPORTED, "distance for a pair of two OcTrees (OcTreeDistanceRecurse) is not implemented");
-  const bool indep = (flags & MPG_DISTANCE_GJK_INDEP) != 0;
-  if (indep && (flags & MPG_DISTANCE_SIGNED))
-    return set_error(MPG_E_UNSUPPORTED, "signed distance with GST_INDEP (FCL's EPA) is not implemented");
-  if (indep && (w->has_mesh || w->has_octree))
-    return set_error(MPG_E_UNSUPPORTED, "distance with GST_INDEP for an OcTree or BVH mesh pair is not implemented");
-  const ccd_real tol = (ccd_real)req->distance_tolerance;  // GJKSolver_libccd::distance_tolerance -> ccd.dist_tolerance
-  const double dtol = req->distance_tolerance;              // GJKSolver_indep::gjk_tolerance (distance-inl.h)
-  const bool want_pts = pts_self || pts_others;
-  const int mode = (want_pts || (flags & (MPG_DISTANCE_SIGNED | MPG_DISTANCE_NEAREST_POINTS)) ? MPG_DIST_POINTS : 0) |
-                   (flags & MPG_DISTANCE_SIGNED ? MPG_DIST_SIGNED : 0) |
-                   (flags & MPG_DISTANCE_NEAREST_POINTS ? MPG_DIST_NP : 0) | (indep ? MPG_DIST_INDEP : 0);
-  if (n == 0) return MPG_OK;
-  HIP_TRY(hipSetDevice(w->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  std::lock_guard<std::mutex> lk(w->dist_mu);
-  auto& D = w->dist;
-  auto grow = [&](void** p, size_t& cap, size_t want) { return scratch_grow(D.last, p, cap, want); };
-  int rc = scratch_begin(D.last, s);
-  if (rc) return rc;
-  const size_t nm = std::max(w->dw.n_moving, 1), ns = std::max(w->dw.bp.n_saves, 1);
-  if ((rc = grow((void**)&D.poses, D.poses_cap, sizeof(double) * kPoseStride * nm * n))) return rc;
-  if ((rc = grow((void**)&D.save64, D.save_cap, sizeof(double) * 12 * ns * n))) return rc;
-  const double* qin = q;
-  double *ds = d_self, *dd = d_others, *qs = pts_self, *qo = pts_others;
-  int32_t *ps = p_self, *po = p_others;
-  const size_t out_bytes = (2 * sizeof(double) + 2 * sizeof(int32_t) + (mode ? 12 * sizeof(double) : 0)) * n;
-  if (mem == MPG_MEM_HOST) {
-    if ((rc = grow((void**)&D.q, D.q_cap, sizeof(double) * std::max(w->dw.dof, 1) * n))) return rc;
-    if ((rc = grow((void**)&D.out, D.out_cap, out_bytes))) return rc;
-    if (w->dw.dof) HIP_TRY(hipMemcpyAsync(D.q, q, sizeof(double) * w->dw.dof * n, hipMemcpyHostToDevice, s));
-    qin = D.q;
-    ds = reinterpret_cast<double*>(D.out);
-    dd = ds + n;
-    qs = dd + n;
-    qo = qs + (mode ? 6 * n : 0);
-    ps = reinterpret_cast<int32_t*>(qo + (mode ? 6 * n : 0));
-    po = ps + n;
-  } else if (mode && (!qs || !qo)) {  // device buffers: scratch for the points nobody asked for
-    if ((rc = grow((void**)&D.pts, D.pts_cap, 12 * sizeof(double) * n))) return rc;
-    if (!qs) qs = D.pts;
-    if (!qo) qo = D.pts + 6 * n;
-  }
-  const unsigned grid = (unsigned)((n + 127) / 128);
-  if (w->dw.n_free) {  // link-pose rows with the current free poses, then the objects' transforms from them
-    if ((rc = grow((void**)&D.links, D.links_cap, sizeof(double) * 7 * w->dw.n_links * n))) return rc;
-    hipLaunchKernelGGL(fk_free_kernel, dim3(grid), dim3(128), 0, s, w->dw, qin, (long long)n, D.links,
-                       (const double*)nullptr, 0ll);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL((pose_kernel<true>), dim3(grid), dim3(128), 0, s, w->dw, D.links, (long long)n, D.poses,
-                       D.save64);
-  } else {
-    hipLaunchKernelGGL((pose_kernel<false>), dim3(grid), dim3(128), 0, s, w->dw, qin, (long long)n, D.poses, D.save64);
-  }
-  HIP_TRY(hipGetLastError());
-  auto launch = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(128), 0, s, w->dw, D.poses, (long long)n, n_self_pairs, tol, dtol, ds,
-                       ps, dd, po, qs, qo);
-    return hipGetLastError();
-  };
-  constexpr int P = MPG_DIST_POINTS, SG = MPG_DIST_SIGNED, NPF = MPG_DIST_NP, IN = MPG_DIST_INDEP;
-  switch (mode) {
-    case 0: HIP_TRY(launch(distance_kernel<0>)); break;
-    case P: HIP_TRY(launch(distance_kernel<P>)); break;
-    case P | NPF: HIP_TRY(launch(distance_kernel<P | NPF>)); break;
-    case P | SG: HIP_TRY(launch(distance_kernel<P | SG>)); break;
-    case P | SG | NPF: HIP_TRY(launch(distance_kernel<P | SG | NPF>)); break;
-    case IN: HIP_TRY(launch(distance_kernel<IN>)); break;
-    case P | IN: HIP_TRY(launch(distance_kernel<P | IN>)); break;
-    default: HIP_TRY(launch(distance_kernel<P | NPF | IN>)); break;
-  }
-  if (mode & SG) {  // EPAs past the private polytope: again with a big one from the pool
-    if ((rc = grow((void**)&D.big, D.big_cap, sizeof(ccdx::BigPolytope) * kBigPool))) return rc;
-    if ((rc = grow((void**)&D.list, D.list_cap, sizeof(unsigned) * (n + 1)))) return rc;
-    HIP_TRY(hipMemsetAsync(D.list, 0, sizeof(unsigned), s));
-    hipLaunchKernelGGL(overflow_list_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ps, (long long)n,
-                       D.list);
-    HIP_TRY(hipGetLastError());
-    auto redo = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(1), dim3(kBigPool), 0, s, w->dw, D.poses, (long long)n, n_self_pairs, tol, dtol,
-                         ds, ps, dd, po, qs, qo, D.big, D.list);
-      return hipGetLastError();
-    };
-    if (mode & NPF) HIP_TRY(redo(distance_redo_kernel<P | SG | NPF>));
-    else HIP_TRY(redo(distance_redo_kernel<P | SG>));
-  }
-  HIP_TRY(hipEventRecord(D.last, s));
-  if (mem == MPG_MEM_HOST) {
-    HIP_TRY(hipMemcpyAsync(d_self, ds, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(d_others, dd, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(p_self, ps, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(p_others, po, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-    if (mode && pts_self) HIP_TRY(hipMemcpyAsync(pts_self, qs, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, s));
-    if (mode && pts_others) HIP_TRY(hipMemcpyAsync(pts_others, qo, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int64_t i = 0; i < n; ++i) {
-      if (p_self[i] == MPG_DISTANCE_FCL_THROWS)
-        return set_error(MPG_E_FAILED, "configuration " + std::to_string(i) +
-                                           ": FCL's libccd EPA throws here (FCL_THROW_FAILED_AT_THIS_CONFIGURATION)");
-      if (p_self[i] == MPG_DISTANCE_EPA_CAPACITY)
-        return set_error(MPG_E_UNSUPPORTED, "configuration " + std::to_string(i) +
-                                                ": EPA polytope beyond the device capacity (" +
-                                                std::to_string(ccdx::kBigPtV) + " vertices)");
-    }
-  }
-  return MPG_OK;
-}
-
-int mpg_collide_contacts(mpg_world* w, const double* input, int64_t n, int input_kind, uint8_t* flags,
-                         uint32_t* pair_mask, double* depth, double* normal, double* pos, int mem, void* stream) {
-  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
-  if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
-  if (input_kind != MPG_INPUT_Q && input_kind != MPG_INPUT_LINK_POSES) return set_error(MPG_E_INVALID, "bad input_kind");
-  const bool poses = input_kind == MPG_INPUT_LINK_POSES;
-  const size_t row = poses ? (size_t)w->dw.n_links * 7 : (size_t)w->dw.dof;
-  if (n > 0 && ((!input && row > 0) || !flags || !pair_mask || !depth || !normal || !pos))
-    return set_error(MPG_E_INVALID, "NULL buffer");
-  if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
-  if (w->any_gjk)
-    return set_error(MPG_E_UNSUPPORTED, "contacts with gjk_solver MPG_GJK_INDEP (FCL's EPA) are not implemented");
-  if (w->has_octree2)
-    return set_error(MPG_E_UNSUPPORTED, "contacts for a pair of two OcTrees are not implemented");
-  if (w->octree_first)  // contact_kernel reports the (shape, octree) order PlanningWorld uses
-    return set_error(MPG_E_UNSUPPORTED, "contacts for a pair whose first object is an OcTree are not implemented");
-  if (n == 0) return MPG_OK;
-  // host-memory link-pose rows: the free frames' columns are checked as every host-memory free pose is
-  if (poses && mem == MPG_MEM_HOST && w->dw.n_free)
-    for (int64_t i = 0; i < n; ++i) {
-      const int rc = check_free_poses(input + ((size_t)i * w->dw.n_links + (w->dw.n_links - w->dw.n_free)) * 7,
-                                      (size_t)w->dw.n_free);
-      if (rc) return rc;
-    }
-  HIP_TRY(hipSetDevice(w->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t P = (size_t)w->dw.n_pairs, W = (size_t)w->dw.W;
-  if (mem == MPG_MEM_DEVICE) {
-    ContactOut co{depth, normal, pos};
-    return poses ? launch_collide<true>(w, input, n, flags, pair_mask, s, &co)
-                 : launch_collide_q(w, input, n, flags, pair_mask, s, &co);
-  }
-  // host buffers: grow-only device staging kept by the world (one host call
-  // at a time: host_mu), no allocation per call
-  std::lock_guard<std::mutex> lk(w->host_mu);
-  if (!s && w->own_stream) s = w->own_stream;
-  auto grow = [&](void** p, size_t& cap, size_t want) -> bool {
-    if (cap >= want) return true;
-    if (*p) hipFree(*p);
-    *p = nullptr;
-    cap = 0;
-    if (hipMalloc(p, want) != hipSuccess) return false;
-    cap = want;
-    return true;
-  };
-  auto& C = w->contact;
-  int rc = MPG_OK;
-  do {
-    if (!grow((void**)&C.in, C.in_cap, sizeof(double) * std::max<size_t>(1, row * n)) ||
-        !grow((void**)&C.out, C.out_cap, sizeof(double) * 7 * P * n) || !grow((void**)&C.fl, C.fl_cap, n) ||
-        !grow((void**)&C.mk, C.mk_cap, sizeof(uint32_t) * W * n)) {
-      rc = set_error(MPG_E_NOMEM, "contact staging buffers");
-      break;
-    }
-    double *d_in = C.in, *d_out = C.out;
-    uint8_t* d_fl = C.fl;
-    uint32_t* d_mk = C.mk;
-    if (row && hipMemcpyAsync(d_in, input, sizeof(double) * row * n, hipMemcpyHostToDevice, s) != hipSuccess) {
-      rc = set_error(MPG_E_HIP, "copy input");
-      break;
-    }
-    ContactOut co{d_out, d_out + P * n, d_out + 4 * P * n};
-    rc = poses ? launch_collide<true>(w, d_in, n, d_fl, d_mk, s, &co) : launch_collide_q(w, d_in, n, d_fl, d_mk, s, &co);
-    if (rc) break;
-    if (hipMemcpyAsync(flags, d_fl, n, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(pair_mask, d_mk, sizeof(uint32_t) * W * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(depth, co.depth, sizeof(double) * P * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(normal, co.normal, sizeof(double) * 3 * P * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(pos, co.pos, sizeof(double) * 3 * P * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-      rc = set_error(MPG_E_HIP, "copy contact results");
-  } while (false);
-  return rc;
-}
-
-int mpg_fk_batch(mpg_world* w, const double* q, int64_t n, double* link_pose, int mem, void* stream) {
-  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
-  if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
-  if (n > 0 && (!q || !link_pose)) return set_error(MPG_E_INVALID, "q/link_pose is NULL");
-  HIP_TRY(hipSetDevice(w->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t nout = (size_t)n * w->dw.n_links * 7;
-  const unsigned grid = (unsigned)((n + 127) / 128);
-  if (mem == MPG_MEM_DEVICE) {
-    if (n && w->dw.n_free)
-      hipLaunchKernelGGL(fk_free_kernel, dim3(grid), dim3(128), 0, s, w->dw, q, (long long)n, link_pose,
-                         (const double*)nullptr, 0ll);
-    else if (n)
-      hipLaunchKernelGGL(fk_kernel, dim3(grid), dim3(128), 0, s, w->dw, q, (long long)n, link_pose);
-    HIP_TRY(hipGetLastError());
-    return MPG_OK;
-  }
-  if (mem != MPG_MEM_HOST) return set_error(MPG_E_INVALID, "bad mem kind");
-  std::lock_guard<std::mutex> lk(w->host_mu);
-  int rc = ensure_staging(w, (size_t)n, std::max<size_t>(nout, 1));
-  if (rc) return rc;
-  if (n == 0) return MPG_OK;
-  HIP_TRY(hipMemcpyAsync(w->d_q, q, sizeof(double) * n * w->dw.dof, hipMemcpyHostToDevice, s));
-  if (w->dw.n_free)
-    hipLaunchKernelGGL(fk_free_kernel, dim3(grid), dim3(128), 0, s, w->dw, w->d_q, (long long)n, w->d_out,
-                       (const double*)nullptr, 0ll);
-  else
-    hipLaunchKernelGGL(fk_kernel, dim3(grid), dim3(128), 0, s, w->dw, w->d_q, (long long)n, w->d_out);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(link_pose, w->d_out, sizeof(double) * nout, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return MPG_OK;
-}
-
-int mpg_debug_collide_pairs(mpg_world* w, int32_t geom_a, int32_t geom_b, int64_t n, const double* Ta,
-                            const double* Tb, uint8_t* hit) {
-  if (!w || n < 0 || (n > 0 && (!Ta || !Tb || !hit))) return set_error(MPG_E_INVALID, "bad arguments");
-  if (geom_a < 0 || geom_b < 0 || geom_a >= w->n_geoms || geom_b >= w->n_geoms)
-    return set_error(MPG_E_INVALID, "geometry index out of range");
-  if (n == 0) return MPG_OK;
-  const int ta = w->geom_type_h[geom_a], tb = w->geom_type_h[geom_b];
-  int cf = CF_NONE;
-  if (ta == MPG_GEOM_MESH || tb == MPG_GEOM_MESH) cf = CF_MESH;
-  else if (ta == MPG_GEOM_OCTREE || tb == MPG_GEOM_OCTREE) cf = CF_OCTREE;
-  else if (ta == MPG_GEOM_BOX && tb == MPG_GEOM_BOX) cf = CF_BOX_BOX;
-  else if (ta == MPG_GEOM_SPHERE && tb == MPG_GEOM_SPHERE) cf = CF_SPHERE_SPHERE;
-  else if (ta == MPG_GEOM_SPHERE && tb == MPG_GEOM_BOX) cf = CF_SPHERE_BOX;
-  else if (ta == MPG_GEOM_BOX && tb == MPG_GEOM_SPHERE) cf = CF_BOX_SPHERE;
-  else if (ta == MPG_GEOM_SPHERE && tb == MPG_GEOM_CAPSULE) cf = CF_SPHERE_CAPSULE;
-  else if (ta == MPG_GEOM_CAPSULE && tb == MPG_GEOM_SPHERE) cf = CF_CAPSULE_SPHERE;
-  else if (ta == MPG_GEOM_SPHERE && tb == MPG_GEOM_CYLINDER) cf = CF_SPHERE_CYLINDER;
-  else if (ta == MPG_GEOM_CYLINDER && tb == MPG_GEOM_SPHERE) cf = CF_CYLINDER_SPHERE;
-  if ((cf == CF_OCTREE && ta == tb) || (cf == CF_MESH && (ta == MPG_GEOM_OCTREE || tb == MPG_GEOM_OCTREE)))
-    return set_error(MPG_E_UNSUPPORTED, "geometry pair not supported");
-  HIP_TRY(hipSetDevice(w->device));
-  struct Guard {  // every exit path frees the buffers and the private stream
-    double *dA = nullptr, *dB = nullptr;
-    uint8_t* dh = nullptr;
-    hipStream_t s = nullptr;
-    ~Guard() {
-      if (s) hipStreamSynchronize(s);
-      hipFree(dA);
-      hipFree(dB);
-      hipFree(dh);
-      if (s) hipStreamDestroy(s);
-    }
-  } g;
-  HIP_TRY(hipStreamCreateWithFlags(&g.s, hipStreamNonBlocking));
-  HIP_TRY(hipMalloc(&g.dA, sizeof(double) * 12 * n));
-  HIP_TRY(hipMalloc(&g.dB, sizeof(double) * 12 * n));
-  HIP_TRY(hipMalloc(&g.dh, (size_t)n));
-  HIP_TRY(hipMemcpyAsync(g.dA, Ta, sizeof(double) * 12 * n, hipMemcpyHostToDevice, g.s));
-  HIP_TRY(hipMemcpyAsync(g.dB, Tb, sizeof(double) * 12 * n, hipMemcpyHostToDevice, g.s));
-  // (walk_wave_eval finds the octree / mesh argument itself)
-  hipLaunchKernelGGL(debug_pairs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.s, w->dw, geom_a, geom_b, cf,
-                     (long long)n, g.dA, g.dB, g.dh);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(hit, g.dh, (size_t)n, hipMemcpyDeviceToHost, g.s));
-  HIP_TRY(hipStreamSynchronize(g.s));
-  return MPG_OK;
-}
-
-int mpg_sample_uniform(const double* lower, const double* upper, int32_t dof, int64_t n, uint64_t seed,
-                       int64_t row_offset, double* q, int device) {
-  if (dof < 0 || dof > kSampleMaxDof) return set_error(MPG_E_INVALID, "dof out of range [0, 64]");
-  if (n < 0 || row_offset < 0 || (n > 0 && dof > 0 && (!lower || !upper || !q)))
-    return set_error(MPG_E_INVALID, "bad arguments");
-  if (n == 0 || dof == 0) return MPG_OK;
-  SampleRange r{};
-  for (int k = 0; k < dof; ++k) {
-    if (!(std::isfinite(lower[k]) && std::isfinite(upper[k]) && lower[k] <= upper[k]))
-      return set_error(MPG_E_INVALID, "sampling range must be finite with lower <= upper");
-    r.lo[k] = lower[k];
-    r.hi[k] = upper[k];
-  }
-  HIP_TRY(hipSetDevice(device));
-  double* d = nullptr;
-  HIP_TRY(hipMalloc(&d, sizeof(double) * (size_t)n * dof));
-  const long long tot = (long long)n * dof;
-  hipLaunchKernelGGL(sample_uniform_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, 0, r, (int)dof,
-                     (long long)n, seed, (long long)row_offset, d);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpy(q, d, sizeof(double) * (size_t)tot, hipMemcpyDeviceToHost);
-  hipFree(d);
-  if (e != hipSuccess) return set_error(MPG_E_HIP, std::string("mpg_sample_uniform: ") + hipGetErrorString(e));
-  return MPG_OK;
-}
-
-int mpg_collide_count(mpg_world* w, const double* lower, const double* upper, int64_t n, uint64_t seed,
-                      int64_t* counts, void* stream) {
-  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
-  const int dof = w->dw.dof, P = w->dw.n_pairs, W = w->dw.W;
-  if (dof > kSampleMaxDof) return set_error(MPG_E_UNSUPPORTED, "mpg_collide_count supports dof <= 64");
-  if (n < 0 || (P > 0 && !counts) || (dof > 0 && (!lower || !upper))) return set_error(MPG_E_INVALID, "bad arguments");
-  if ((size_t)P * sizeof(uint32_t) > 64 * 1024) return set_error(MPG_E_UNSUPPORTED, "mpg_collide_count supports <= 16384 pairs");
-  for (int p = 0; p < P; ++p) counts[p] = 0;
-  if (n == 0 || P == 0) return MPG_OK;
-  SampleRange r{};
-  for (int k = 0; k < dof; ++k) {
-    if (!(std::isfinite(lower[k]) && std::isfinite(upper[k]) && lower[k] <= upper[k]))
-      return set_error(MPG_E_INVALID, "sampling range must be finite with lower <= upper");
-    r.lo[k] = lower[k];
-    r.hi[k] = upper[k];
-  }
-  HIP_TRY(hipSetDevice(w->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const long long chunk = std::min<long long>(n, w->max_chunk);
-  struct Bufs {  // freed on every exit path, after the stream drained
-    double* q = nullptr;
-    uint8_t* fl = nullptr;
-    uint32_t* mk = nullptr;
-    unsigned long long* cnt = nullptr;
-    hipStream_t s = nullptr;
-    ~Bufs() {
-      hipStreamSynchronize(s);
-      hipFree(q);
-      hipFree(fl);
-      hipFree(mk);
-      hipFree(cnt);
-    }
-  } b;
-  b.s = s;
-  HIP_TRY(hipMalloc(&b.q, sizeof(double) * (size_t)chunk * std::max(dof, 1)));
-  HIP_TRY(hipMalloc(&b.fl, (size_t)chunk));
-  HIP_TRY(hipMalloc(&b.mk, sizeof(uint32_t) * (size_t)chunk * W));
-  HIP_TRY(hipMalloc(&b.cnt, sizeof(unsigned long long) * P));
-  HIP_TRY(hipMemsetAsync(b.cnt, 0, sizeof(unsigned long long) * P, s));
-  for (long long off = 0; off < n; off += chunk) {
-    const long long m = std::min(chunk, n - off);
-    if (dof > 0) {
-      const long long tot = m * dof;
-      hipLaunchKernelGGL(sample_uniform_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, r, dof, m, seed,
-                         off, b.q);
-      HIP_TRY(hipGetLastError());
-    }
-    const int rc = w->dw.n_free ? launch_collide_q(w, b.q, m, b.fl, b.mk, s)
-                                : launch_collide_overlapped<false>(w, b.q, m, b.fl, b.mk, s);
-    if (rc) return rc;
-    const unsigned grid = (unsigned)std::min<long long>(1024, (m + 255) / 256);
-    hipLaunchKernelGGL(pair_count_kernel, dim3(grid), dim3(256), sizeof(uint32_t) * P, s, b.mk, m, W, P, b.cnt);
-    HIP_TRY(hipGetLastError());
-  }
-  std::vector<unsigned long long> h(P);
-  HIP_TRY(hipMemcpyAsync(h.data(), b.cnt, sizeof(unsigned long long) * P, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  for (int p = 0; p < P; ++p) counts[p] = (int64_t)h[p];
-  return MPG_OK;
-}
-
-int mpg_debug_sincos(const double* x, int64_t n, double* s, double* c, int device) {
-  if (n < 0 || (n > 0 && (!x || !s || !c))) return set_error(MPG_E_INVALID, "bad arguments");
-  if (n == 0) return MPG_OK;
-  HIP_TRY(hipSetDevice(device));
-  double *dx = nullptr, *ds = nullptr, *dc = nullptr;
-  HIP_TRY(hipMalloc(&dx, sizeof(double) * n));
-  HIP_TRY(hipMalloc(&ds, sizeof(double) * n));
-  HIP_TRY(hipMalloc(&dc, sizeof(double) * n));
-  HIP_TRY(hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(sincos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dx, (long long)n, ds, dc);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(s, ds, sizeof(double) * n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(c, dc, sizeof(double) * n, hipMemcpyDeviceToHost));
-  hipFree(dx);
-  hipFree(ds);
-  hipFree(dc);
-  return MPG_OK;
-}
+#include "mpg_abi_batch.h"
 
 }  // extern "C"

@@ -2068,7 +2068,7 @@ static void bsphere(const real *const *P, int n, real *c, real *r) {
  * recursing.  Only the OBB half of OBBRSS decides collisions
  * (OBBRSS::overlap = obb.overlap), so the RSS half is not built.
  * The device's snapshot builds the same tree independently
- * (mplib_amd/csrc/mpg_kernels.hip build_fcl_bvh). */
+ * (mplib_amd/csrc/mpg_snapshot_host.h FclBvh, fcl_bvh_node). */
 typedef struct {
     double axis[9]; /* row-major; column k = the k-th box axis */
     double To[3], ext[3];

@@ -50,7 +50,7 @@
  *     the unit search direction there.  The second exit ("no progress": the
  *     new support point is as far from the origin as the simplex) reports
  *     that support pair (last.v1, last.v2), as libccd's ccdGJKDist2 does.
- * The device twin is mplib_amd/csrc/mpg_kernels.hip (ccd_gjk / ccd_epa); both
+ * The device twin is mplib_amd/csrc/mpg_ccd_dist.h (gjk_distance / epa); both
  * are compiled without FP contraction and must agree bit for bit.
  */
 

@@ -1,7 +1,7 @@
 """CollisionRequest(gjk_solver_type=GST_INDEP): FCL 0.7.0's own GJK
 (GJKSolver_indep::shapeIntersect -> details::GJK::evaluate on a MinkowskiDiff,
 double precision), restated in oracle/fcl_gjk_indep.h and on the device
-(mpg_kernels.hip gjk_indep_intersect, the CF_GJK pair class).  VERDICT r5
+(mpg_gjk_indep.h gjk_indep_intersect, the CF_GJK pair class).  VERDICT r5
 missing #1: the C++ default of FCLModel::collideFull
 (/root/reference/src/fcl_model.h:74-77) and selectable from Python
 (python/pybind_fcl.hpp:264, 276).
