@@ -59,7 +59,7 @@ extern "C" {
 #endif
 
 #define MPG_VERSION_MAJOR 0
-#define MPG_VERSION_MINOR 2
+#define MPG_VERSION_MINOR 3
 
 /* status codes */
 #define MPG_OK 0
@@ -371,10 +371,19 @@ int mpg_collide_link_poses(mpg_world *world, const double *link_pose, int64_t n,
  * far_radius, margins included), so an object parked far away costs nothing
  * in the narrow phase and never widens the fp32 coordinate bound.
  *
- * Per-row poses for contacts, distance and motion validation, several
- * objects on one free frame, mpg_collide_batch_multi* with per-call poses
- * (set the poses on each world) and a movable base of an articulation are
- * not provided.
+ * mpg_distance_batch_free, mpg_check_motion_batch_free and
+ * mpg_collide_contacts_free (declared next to the calls they extend) take
+ * free_pose / free_rows after their input rows in the same way, with the same
+ * rules: NULL = the current poses (then identical to the call without
+ * _free, which forwards here), free_rows == 1 or n else MPG_E_INVALID, a
+ * non-NULL free_pose on a world without free frames MPG_E_INVALID.
+ * MPG_MEM_DEVICE arrays are read by the kernels where the caller keeps them;
+ * MPG_MEM_HOST arrays are checked as below and staged in the grow-only
+ * scratch of the call's family (no allocation per call once warm).
+ *
+ * Several objects on one free frame, mpg_collide_batch_multi* with per-call
+ * poses (set the poses on each world), a movable base of an articulation and
+ * poses that change along an edge are not provided.
  */
 int mpg_world_set_free_poses(mpg_world *world, const double *pose7);
 int mpg_collide_batch_free(mpg_world *world, const double *q, const double *free_pose, int64_t free_rows,
@@ -400,6 +409,16 @@ int mpg_world_get_free_info(const mpg_world *world, int32_t *n_free, double *far
 int mpg_check_motion_batch(mpg_world *world, const double *q_from, const double *q_to, int64_t n,
                            uint32_t so2_mask, double longest_valid_segment, uint8_t *valid,
                            int32_t *first_invalid, int32_t *segments, int mem, void *stream);
+/* With the free poses given per call (see mpg_collide_batch_free): free_rows
+ * == 1, one pose set shared by every edge, or n, one pose set per EDGE --
+ * every state along edge e is checked with pose set e (the poses do not
+ * change along an edge).  The device keeps one int32 per interpolated state
+ * (its edge), never a pose set per state.  At most 2^31 - 1 edges with
+ * per-edge poses (MPG_E_UNSUPPORTED beyond). */
+int mpg_check_motion_batch_free(mpg_world *world, const double *q_from, const double *q_to,
+                                const double *free_pose, int64_t free_rows, int64_t n, uint32_t so2_mask,
+                                double longest_valid_segment, uint8_t *valid, int32_t *first_invalid,
+                                int32_t *segments, int mem, void *stream);
 
 /*
  * Batched distance: per configuration, PlanningWorldTpl::distanceSelf and
@@ -485,6 +504,13 @@ typedef struct mpg_distance_request {
 int mpg_distance_batch_req(mpg_world *world, const double *q, int64_t n, int32_t n_self_pairs,
                            const mpg_distance_request *request, double *d_self, int32_t *p_self, double *pts_self,
                            double *d_others, int32_t *p_others, double *pts_others, int mem, void *stream);
+/* mpg_distance_batch_req with the free poses given per call (see
+ * mpg_collide_batch_free): free_rows == n, configuration i measured against
+ * the movable objects at pose set i, or 1. */
+int mpg_distance_batch_free(mpg_world *world, const double *q, const double *free_pose, int64_t free_rows,
+                            int64_t n, int32_t n_self_pairs, const mpg_distance_request *request, double *d_self,
+                            int32_t *p_self, double *pts_self, double *d_others, int32_t *p_others,
+                            double *pts_others, int mem, void *stream);
 /* mpg_distance_batch_req with distance_tolerance = 1e-6 */
 int mpg_distance_batch_ex(mpg_world *world, const double *q, int64_t n, int32_t n_self_pairs, int32_t flags,
                           double *d_self, int32_t *p_self, double *pts_self, double *d_others, int32_t *p_others,
@@ -522,6 +548,12 @@ int mpg_distance_batch_ex(mpg_world *world, const double *q, int64_t n, int32_t 
 #define MPG_INPUT_LINK_POSES 1
 int mpg_collide_contacts(mpg_world *world, const double *input, int64_t n, int input_kind, uint8_t *flags,
                          uint32_t *pair_mask, double *depth, double *normal, double *pos, int mem, void *stream);
+/* With the free poses given per call (see mpg_collide_batch_free), for
+ * MPG_INPUT_Q rows.  MPG_INPUT_LINK_POSES rows already carry the free frames'
+ * columns: a non-NULL free_pose with them is MPG_E_INVALID. */
+int mpg_collide_contacts_free(mpg_world *world, const double *input, const double *free_pose, int64_t free_rows,
+                              int64_t n, int input_kind, uint8_t *flags, uint32_t *pair_mask, double *depth,
+                              double *normal, double *pos, int mem, void *stream);
 
 /* link_pose: [n*n_links*7] = getLinkPose(l) -> (px, py, pz, qw, qx, qy, qz);
  * free frames: their current poses. */

@@ -732,7 +732,7 @@ class PlanningWorld {
   bool remove_normal_object(const std::string& n);
   // Movable scene objects: their poses are inputs of the device snapshot
   // (free frames, include/mpgpu.h), so set_pose on one needs no rebuild and
-  // collide_batch can take poses per call.  Marking is a structure change; it
+  // collide_batch, distance_batch and check_motion_batch can take poses per call.  Marking is a structure change; it
   // leaves the pair table as it is.  An attached object is an attached body
   // whether marked or not.
   void set_normal_object_movable(const std::string& n, bool movable = true);
@@ -775,11 +775,13 @@ class PlanningWorld {
   WorldDistanceResult distance_with_others(const DistanceRequest& r = DistanceRequest());
   WorldDistanceResult distance_full(const DistanceRequest& r = DistanceRequest());
   // per configuration: (self group, others group) minimum and pair index
+  // (poses / pose_rows as collide_batch_free takes them; NULL: current poses)
   void distance_batch(const double* q, int64_t n, double* d_self, int32_t* p_self, double* d_others,
-                      int32_t* p_others);
+                      int32_t* p_others, const double* poses = nullptr, int64_t pose_rows = 0);
   // with DistanceRequest's flags and the nearest points [n*6] (may be NULL)
   void distance_batch_ex(const double* q, int64_t n, const DistanceRequest& r, double* d_self, int32_t* p_self,
-                         double* pts_self, double* d_others, int32_t* p_others, double* pts_others);
+                         double* pts_self, double* d_others, int32_t* p_others, double* pts_others,
+                         const double* poses = nullptr, int64_t pose_rows = 0);
   int n_self_pairs();
 
   // batch API (one launch for N configurations)
@@ -796,7 +798,8 @@ class PlanningWorld {
   std::vector<double> movable_poses() const;  // current (p, wxyz) per movable object
   // distance_batch_ex on device buffers (MPG_MEM_DEVICE, enqueued on stream)
   void distance_batch_device(const void* q, int64_t n, const DistanceRequest& r, void* d_self, void* p_self,
-                             void* pts_self, void* d_others, void* p_others, void* pts_others, void* stream);
+                             void* pts_self, void* d_others, void* p_others, void* pts_others, void* stream,
+                             const void* poses = nullptr, int64_t pose_rows = 0);
   int mask_words();
   mpg_world* device_world();  // rebuilds the snapshot if the world changed
   // batched OMPL motion validation over the planner's state space
@@ -806,8 +809,10 @@ class PlanningWorld {
     double max_extent = 0.0;
   };
   MotionSpace motion_space();
+  // poses [pose_rows, M, 7]: pose_rows = 1, or n -- one pose set per edge, held along the edge
   void check_motion_batch(const double* from, const double* to, int64_t n, double longest_valid_segment,
-                          uint8_t* valid, int32_t* first_invalid, int32_t* segments);
+                          uint8_t* valid, int32_t* first_invalid, int32_t* segments, const double* poses = nullptr,
+                          int64_t pose_rows = 0);
   // Planner.generate_collision_pair (mplib/planner.py:118-163), batched: per
   // pair of pair_table(), how many of n random FULL configurations of the
   // planned articulations (every joint, as set_qpos(q, full=True) sets it)

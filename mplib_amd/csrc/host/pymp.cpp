@@ -102,6 +102,44 @@ void translate_exceptions() {
   });
 }
 
+// object_poses of the batched queries: {name: (7,) or (n, 7) float64} for
+// movable scene objects, assembled as the device takes them -- [pose_rows, M,
+// 7] in get_movable_object_names() order, pose_rows = n if some entry is per
+// row, else 1; names left out keep their current pose.  Returns pose_rows
+// (0: no dict, or no movable objects -- the world's current poses).
+int64_t parse_object_poses(PlanningWorld& w, const std::optional<py::dict>& object_poses, int64_t n,
+                           std::vector<double>& poses) {
+  if (!object_poses) return 0;
+  const std::vector<std::string> names = w.get_movable_object_names();
+  const size_t M = names.size();
+  using Arr = py::array_t<double, py::array::c_style | py::array::forcecast>;
+  std::vector<std::optional<Arr>> given(M);
+  int64_t pose_rows = 1;
+  for (auto item : *object_poses) {
+    const std::string name = py::cast<std::string>(item.first);
+    const auto it = std::find(names.begin(), names.end(), name);
+    if (it == names.end()) throw std::invalid_argument("object_poses: '" + name + "' is not a movable scene object");
+    Arr a = Arr::ensure(item.second);
+    if (!a) throw std::invalid_argument("object_poses['" + name + "'] must be a float64 array");
+    const bool shared = a.ndim() == 1 && a.shape(0) == 7;
+    const bool per_row = a.ndim() == 2 && a.shape(0) == n && a.shape(1) == 7;
+    if (!shared && !per_row)
+      throw std::invalid_argument("object_poses['" + name + "'] must be (7,) or (" + std::to_string(n) + ", 7)");
+    if (per_row) pose_rows = n;
+    given[it - names.begin()] = a;
+  }
+  const std::vector<double> cur = w.movable_poses();
+  if (M == 0) pose_rows = 0;
+  poses.resize((size_t)pose_rows * M * 7);
+  for (int64_t r = 0; r < pose_rows; ++r)
+    for (size_t k = 0; k < M; ++k) {
+      const double* src = cur.data() + 7 * k;
+      if (given[k]) src = given[k]->data() + (given[k]->ndim() == 2 ? 7 * r : 0);
+      std::copy(src, src + 7, poses.data() + ((size_t)r * M + k) * 7);
+    }
+  return pose_rows;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(pymp, m_all) {
@@ -1008,7 +1046,7 @@ PYBIND11_MODULE(pymp, m_all) {
       .def("distance_full", &PW::distance_full, py::arg("request") = DistanceRequest())
       .def("distance_batch",
            [](PW& w, py::array_t<double, py::array::c_style | py::array::forcecast> states, py::object request,
-              bool nearest_points) -> py::tuple {
+              bool nearest_points, std::optional<py::dict> object_poses) -> py::tuple {
              const int dim = w.state_dim();
              if (states.ndim() != 2 || states.shape(1) != dim)
                throw std::invalid_argument("states must be [N, " + std::to_string(dim) + "] float64");
@@ -1017,6 +1055,9 @@ PYBIND11_MODULE(pymp, m_all) {
              r.check_supported();
              const int32_t flags = r.flags();
              const int64_t n = states.shape(0);
+             std::vector<double> poses;
+             const int64_t pose_rows = parse_object_poses(w, object_poses, n, poses);
+             const double* pp = pose_rows > 0 ? poses.data() : nullptr;
              py::array_t<double> ds(n), dot(n);
              py::array_t<int32_t> ps(n), po(n);
              const double* q = states.data();
@@ -1025,7 +1066,7 @@ PYBIND11_MODULE(pymp, m_all) {
              if (!nearest_points && flags == 0 && r.distance_tolerance == 1e-6) {
                {
                  py::gil_scoped_release rel;
-                 w.distance_batch(q, n, a, c, b, d);
+                 w.distance_batch(q, n, a, c, b, d, pp, pose_rows);
                }
                return py::tuple(py::make_tuple(ds, ps, dot, po));
              }
@@ -1033,16 +1074,18 @@ PYBIND11_MODULE(pymp, m_all) {
              double *e = qs.mutable_data(), *f = qo.mutable_data();
              {
                py::gil_scoped_release rel;
-               w.distance_batch_ex(q, n, r, a, c, e, b, d, f);
+               w.distance_batch_ex(q, n, r, a, c, e, b, d, f, pp, pose_rows);
              }
              return py::tuple(py::make_tuple(ds, ps, dot, po, qs, qo));
            },
            py::arg("states"), py::arg("request") = py::none(), py::arg("nearest_points") = false,
+           py::arg("object_poses") = py::none(),
            "Batched self_distance / distance_with_others: (d_self[N], pair_self[N], d_others[N], pair_others[N]); "
            "-1 = a penetrating pair, pair indices into get_collision_pair_info().  With a DistanceRequest "
            "(enable_signed_distance: -penetration depth instead of -1; distance_tolerance) or nearest_points=True, "
            "also DistanceResult.nearest_points of each group's minimum pair: (..., pts_self[N, 6], pts_others[N, 6]) "
-           "(include/mpgpu.h mpg_distance_batch_req: which point is which).")
+           "(include/mpgpu.h mpg_distance_batch_req: which point is which).  object_poses: as collide_batch takes "
+           "it -- row i is measured with the movable objects at their row-i poses.")
       // ---- batched validity (new; one device launch for N states) ----
       .def("sample_pair_counts",
            [](PW& w, int64_t n, uint64_t seed) {
@@ -1078,41 +1121,8 @@ PYBIND11_MODULE(pymp, m_all) {
                throw std::invalid_argument("states must be [N, " + std::to_string(dim) + "] float64");
              const int64_t n = states.shape(0);
              const int W = w.mask_words();
-             // object_poses: the movable objects' columns, per row ([N, 7]) or
-             // shared ((7,)); names left out keep their current pose
              std::vector<double> poses;
-             int64_t pose_rows = 0;
-             if (object_poses) {
-               const std::vector<std::string> names = w.get_movable_object_names();
-               const size_t M = names.size();
-               using Arr = py::array_t<double, py::array::c_style | py::array::forcecast>;
-               std::vector<std::optional<Arr>> given(M);
-               pose_rows = 1;
-               for (auto item : *object_poses) {
-                 const std::string name = py::cast<std::string>(item.first);
-                 const auto it = std::find(names.begin(), names.end(), name);
-                 if (it == names.end())
-                   throw std::invalid_argument("object_poses: '" + name + "' is not a movable scene object");
-                 Arr a = Arr::ensure(item.second);
-                 if (!a) throw std::invalid_argument("object_poses['" + name + "'] must be a float64 array");
-                 const bool shared = a.ndim() == 1 && a.shape(0) == 7;
-                 const bool per_row = a.ndim() == 2 && a.shape(0) == n && a.shape(1) == 7;
-                 if (!shared && !per_row)
-                   throw std::invalid_argument("object_poses['" + name + "'] must be (7,) or (" + std::to_string(n) +
-                                               ", 7)");
-                 if (per_row) pose_rows = n;
-                 given[it - names.begin()] = a;
-               }
-               const std::vector<double> cur = w.movable_poses();
-               if (M == 0) pose_rows = 0;
-               poses.resize((size_t)pose_rows * M * 7);
-               for (int64_t r = 0; r < pose_rows; ++r)
-                 for (size_t k = 0; k < M; ++k) {
-                   const double* src = cur.data() + 7 * k;
-                   if (given[k]) src = given[k]->data() + (given[k]->ndim() == 2 ? 7 * r : 0);
-                   std::copy(src, src + 7, poses.data() + ((size_t)r * M + k) * 7);
-                 }
-             }
+             const int64_t pose_rows = parse_object_poses(w, object_poses, n, poses);
              py::array_t<uint8_t> flags(n);
              py::array_t<uint32_t> masks({(ssize_t)n, (ssize_t)W});
              const double* q = states.data();
@@ -1149,30 +1159,37 @@ PYBIND11_MODULE(pymp, m_all) {
       .def("distance_batch_device",
            [](PW& w, uintptr_t q, int64_t n, uintptr_t d_self, uintptr_t p_self, uintptr_t d_others,
               uintptr_t p_others, uintptr_t pts_self, uintptr_t pts_others, uintptr_t stream,
-              std::optional<DistanceRequest> request) {
+              std::optional<DistanceRequest> request, uintptr_t object_poses, int64_t object_pose_rows) {
              const DistanceRequest r = request ? *request : DistanceRequest();
              w.distance_batch_device(reinterpret_cast<const void*>(q), n, r, reinterpret_cast<void*>(d_self),
                                      reinterpret_cast<void*>(p_self), reinterpret_cast<void*>(pts_self),
                                      reinterpret_cast<void*>(d_others), reinterpret_cast<void*>(p_others),
-                                     reinterpret_cast<void*>(pts_others), reinterpret_cast<void*>(stream));
+                                     reinterpret_cast<void*>(pts_others), reinterpret_cast<void*>(stream),
+                                     reinterpret_cast<const void*>(object_poses), object_pose_rows);
            },
            py::arg("states_ptr"), py::arg("n"), py::arg("d_self_ptr"), py::arg("p_self_ptr"),
            py::arg("d_others_ptr"), py::arg("p_others_ptr"), py::arg("pts_self_ptr") = 0,
            py::arg("pts_others_ptr") = 0, py::arg("stream") = 0, py::arg("request") = py::none(),
+           py::arg("object_poses_ptr") = 0, py::arg("object_pose_rows") = 0,
            "Enqueue distance_batch on device buffers (float64 [n, dim] -> float64 [n], int32 [n] per group, "
            "optional float64 [n, 6] nearest points).  No error is raised for a configuration where FCL throws: "
            "it gets NaN distances and pair index -2 (MPG_DISTANCE_FCL_THROWS) in both groups, or -3 "
            "(MPG_DISTANCE_EPA_CAPACITY) when the EPA polytope outgrew the device; check p < -1 before indexing "
-           "the pair table (mplib_amd.dist.distance_sharded_device does).")
+           "the pair table (mplib_amd.dist.distance_sharded_device does).  object_poses_ptr / object_pose_rows: as "
+           "collide_batch_device takes them.")
       .def("check_motion_batch",
            [](PW& w, py::array_t<double, py::array::c_style | py::array::forcecast> q_from,
-              py::array_t<double, py::array::c_style | py::array::forcecast> q_to, double fraction, double lvs) {
+              py::array_t<double, py::array::c_style | py::array::forcecast> q_to, double fraction, double lvs,
+              std::optional<py::dict> object_poses) {
              const int dim = w.state_dim();
              if (q_from.ndim() != 2 || q_from.shape(1) != dim || q_to.ndim() != 2 || q_to.shape(1) != dim ||
                  q_to.shape(0) != q_from.shape(0))
                throw std::invalid_argument("q_from / q_to must both be [N, " + std::to_string(dim) + "] float64");
              if (lvs <= 0.0) lvs = fraction * w.motion_space().max_extent;
              const int64_t n = q_from.shape(0);
+             std::vector<double> poses;
+             const int64_t pose_rows = parse_object_poses(w, object_poses, n, poses);
+             const double* pp = pose_rows > 0 ? poses.data() : nullptr;
              py::array_t<bool> valid(n);
              py::array_t<int32_t> first(n), segs(n);
              const double* a = q_from.data();
@@ -1182,15 +1199,17 @@ PYBIND11_MODULE(pymp, m_all) {
              int32_t* sg = segs.mutable_data();
              {
                py::gil_scoped_release rel;
-               w.check_motion_batch(a, b, n, lvs, v, f, sg);
+               w.check_motion_batch(a, b, n, lvs, v, f, sg, pp, pose_rows);
              }
              return py::make_tuple(valid, first, segs);
            },
            py::arg("q_from"), py::arg("q_to"), py::arg("longest_valid_segment_fraction") = 0.01,
-           py::arg("longest_valid_segment") = 0.0,
+           py::arg("longest_valid_segment") = 0.0, py::arg("object_poses") = py::none(),
            "Batched OMPL DiscreteMotionValidator::checkMotion over the planner's state space: returns (valid[N], "
            "first_invalid[N] (1-based state index along the edge, -1 if valid), segments[N]). The longest valid "
-           "segment defaults to fraction * the space's maximum extent, as OMPL's SpaceInformation does.")
+           "segment defaults to fraction * the space's maximum extent, as OMPL's SpaceInformation does.  "
+           "object_poses: {name: (7,) or (N, 7)} for movable scene objects -- every state along edge i is checked "
+           "with the objects at their row-i poses (held along the edge); names left out keep their current pose.")
       .def("get_motion_space",
            [](PW& w) {
              auto ms = w.motion_space();
@@ -1266,36 +1285,48 @@ PYBIND11_MODULE(pymp, m_all) {
            "setQposAll(state); distance(): the distance to the nearest invalid state, -1 in collision "
            "(ompl_planner.h:69-72, planning_world.h:271-273)")
       .def("is_valid_batch",
-           [states_arg](ValidityChecker& v, py::array_t<double, py::array::c_style | py::array::forcecast> states) {
+           [states_arg](ValidityChecker& v, py::array_t<double, py::array::c_style | py::array::forcecast> states,
+                        std::optional<py::dict> object_poses) {
              const int64_t n = states_arg(*v.world, states);
+             std::vector<double> poses;
+             const int64_t pose_rows = parse_object_poses(*v.world, object_poses, n, poses);
              std::vector<uint8_t> fl((size_t)n);
              std::vector<uint32_t> mk((size_t)n * (size_t)std::max(v.world->mask_words(), 1));
              {
                py::gil_scoped_release rel;
-               v.world->collide_batch(states.data(), n, fl.data(), mk.data());
+               if (pose_rows > 0)
+                 v.world->collide_batch_free(states.data(), poses.data(), pose_rows, n, fl.data(), mk.data());
+               else
+                 v.world->collide_batch(states.data(), n, fl.data(), mk.data());
              }
              py::array_t<bool> out(n);
              for (int64_t i = 0; i < n; ++i) out.mutable_data()[i] = fl[(size_t)i] == 0;
              return out;
            },
-           py::arg("states"))
+           py::arg("states"), py::arg("object_poses") = py::none(),
+           "!collide() of N states in one device launch, world state untouched; object_poses as "
+           "PlanningWorld.collide_batch takes it (state i against the movable objects at their row-i poses)")
       .def("clearance_batch",
-           [states_arg](ValidityChecker& v, py::array_t<double, py::array::c_style | py::array::forcecast> states) {
+           [states_arg](ValidityChecker& v, py::array_t<double, py::array::c_style | py::array::forcecast> states,
+                        std::optional<py::dict> object_poses) {
              const int64_t n = states_arg(*v.world, states);
+             std::vector<double> poses;
+             const int64_t pose_rows = parse_object_poses(*v.world, object_poses, n, poses);
              std::vector<double> ds((size_t)n), dot((size_t)n);
              std::vector<int32_t> ps((size_t)n), po((size_t)n);
              {
                py::gil_scoped_release rel;
-               v.world->distance_batch(states.data(), n, ds.data(), ps.data(), dot.data(), po.data());
+               v.world->distance_batch(states.data(), n, ds.data(), ps.data(), dot.data(), po.data(),
+                                       pose_rows > 0 ? poses.data() : nullptr, pose_rows);
              }
              py::array_t<double> out(n);
              for (int64_t i = 0; i < n; ++i)  // distanceFull: the smaller group minimum (planning_world.cpp:718-719)
                out.mutable_data()[i] = ds[(size_t)i] < dot[(size_t)i] ? ds[(size_t)i] : dot[(size_t)i];
              return out;
            },
-           py::arg("states"),
+           py::arg("states"), py::arg("object_poses") = py::none(),
            "clearance() of N states in one device launch (MaximizeMinClearanceObjective's query, "
-           "ompl_planner.cpp:180-186), world state untouched");
+           "ompl_planner.cpp:180-186), world state untouched; object_poses as PlanningWorld.distance_batch takes it");
   py::class_<OMPLPlanner, std::shared_ptr<OMPLPlanner>>(mo, "OMPLPlanner")
       .def(py::init([](const std::shared_ptr<PW>& world, py::object checker) {
              auto p = std::make_shared<OMPLPlanner>(world);

@@ -791,11 +791,12 @@ PlanningWorld::MotionSpace PlanningWorld::motion_space() {
 }
 
 void PlanningWorld::check_motion_batch(const double* from, const double* to, int64_t n, double lvs, uint8_t* valid,
-                                       int32_t* first_invalid, int32_t* segments) {
+                                       int32_t* first_invalid, int32_t* segments, const double* poses,
+                                       int64_t pose_rows) {
   ensure_snapshot(CollisionRequest());
   const MotionSpace ms = motion_space();
-  check_status(mpg_check_motion_batch(world_->get(), from, to, n, ms.so2_mask, lvs, valid, first_invalid, segments,
-                                      MPG_MEM_HOST, nullptr),
+  check_status(mpg_check_motion_batch_free(world_->get(), from, to, poses, pose_rows, n, ms.so2_mask, lvs, valid,
+                                           first_invalid, segments, MPG_MEM_HOST, nullptr),
                "mpg_check_motion_batch");
 }
 
@@ -830,7 +831,9 @@ int PlanningWorld::n_self_pairs() {
 }
 
 void PlanningWorld::distance_batch(const double* q, int64_t n, double* d_self, int32_t* p_self, double* d_others,
-                                   int32_t* p_others) {
+                                   int32_t* p_others, const double* poses, int64_t pose_rows) {
+  if (poses) return distance_batch_ex(q, n, DistanceRequest(), d_self, p_self, nullptr, d_others, p_others, nullptr,
+                                      poses, pose_rows);
   const int ns = n_self_pairs();
   ensure_snapshot(CollisionRequest());
   check_status(mpg_distance_batch(world_->get(), q, n, ns, d_self, p_self, d_others, p_others, MPG_MEM_HOST, nullptr),
@@ -839,27 +842,29 @@ void PlanningWorld::distance_batch(const double* q, int64_t n, double* d_self, i
 
 void PlanningWorld::distance_batch_ex(const double* q, int64_t n, const DistanceRequest& r, double* d_self,
                                       int32_t* p_self, double* pts_self, double* d_others, int32_t* p_others,
-                                      double* pts_others) {
+                                      double* pts_others, const double* poses, int64_t pose_rows) {
   const int ns = n_self_pairs();
   ensure_snapshot(CollisionRequest());
   const mpg_distance_request req = r.to_c();
-  check_status(mpg_distance_batch_req(world_->get(), q, n, ns, &req, d_self, p_self, pts_self, d_others, p_others,
-                                      pts_others, MPG_MEM_HOST, nullptr),
+  check_status(mpg_distance_batch_free(world_->get(), q, poses, pose_rows, n, ns, &req, d_self, p_self, pts_self,
+                                       d_others, p_others, pts_others, MPG_MEM_HOST, nullptr),
                "mpg_distance_batch_req");
 }
 
 void PlanningWorld::distance_batch_device(const void* q, int64_t n, const DistanceRequest& r, void* d_self,
                                           void* p_self, void* pts_self, void* d_others, void* p_others,
-                                          void* pts_others, void* stream) {
+                                          void* pts_others, void* stream, const void* poses,
+                                          int64_t pose_rows) {
   r.check_supported();
   const int ns = n_self_pairs();
   ensure_snapshot(CollisionRequest());
   const mpg_distance_request req = r.to_c();
-  check_status(mpg_distance_batch_req(world_->get(), static_cast<const double*>(q), n, ns, &req,
-                                      static_cast<double*>(d_self), static_cast<int32_t*>(p_self),
-                                      static_cast<double*>(pts_self), static_cast<double*>(d_others),
-                                      static_cast<int32_t*>(p_others), static_cast<double*>(pts_others),
-                                      MPG_MEM_DEVICE, stream),
+  check_status(mpg_distance_batch_free(world_->get(), static_cast<const double*>(q),
+                                       static_cast<const double*>(poses), pose_rows, n, ns, &req,
+                                       static_cast<double*>(d_self), static_cast<int32_t*>(p_self),
+                                       static_cast<double*>(pts_self), static_cast<double*>(d_others),
+                                       static_cast<int32_t*>(p_others), static_cast<double*>(pts_others),
+                                       MPG_MEM_DEVICE, stream),
                "mpg_distance_batch_req");
 }
 

@@ -193,13 +193,26 @@ int mpg_world_get_free_info(const mpg_world* w, int32_t* n_free, double* far_rad
 int mpg_check_motion_batch(mpg_world* w, const double* q_from, const double* q_to, int64_t n, uint32_t so2_mask,
                            double longest_valid_segment, uint8_t* valid, int32_t* first_invalid, int32_t* segments,
                            int mem, void* stream) {
+  return mpg_check_motion_batch_free(w, q_from, q_to, nullptr, 0, n, so2_mask, longest_valid_segment, valid,
+                                     first_invalid, segments, mem, stream);
+}
+
+int mpg_check_motion_batch_free(mpg_world* w, const double* q_from, const double* q_to, const double* free_pose,
+                                int64_t free_rows, int64_t n, uint32_t so2_mask, double longest_valid_segment,
+                                uint8_t* valid, int32_t* first_invalid, int32_t* segments, int mem, void* stream) {
   if (!w) return set_error(MPG_E_INVALID, "world is NULL");
   if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
   if (n > 0 && (!q_from || !q_to || !valid)) return set_error(MPG_E_INVALID, "from/to/valid is NULL");
   if (!(longest_valid_segment > 0.0)) return set_error(MPG_E_INVALID, "longest_valid_segment must be > 0");
   if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
+  if (const int frc = check_free_args(w, free_pose, free_rows, n)) return frc;
   if (w->dw.dof > 32) return set_error(MPG_E_UNSUPPORTED, "motion validation supports dof <= 32");
   if (n == 0) return MPG_OK;
+  const bool per_edge = free_pose && free_rows > 1;  // free_rows == n: the row map holds int32 edge indices
+  if (per_edge && n > (int64_t)INT32_MAX)
+    return set_error(MPG_E_UNSUPPORTED, "per-edge free poses support at most 2^31 - 1 edges");
+  if (free_pose && mem == MPG_MEM_HOST)
+    if (const int frc = check_free_poses(free_pose, (size_t)free_rows * w->dw.n_free)) return frc;
   HIP_TRY(hipSetDevice(w->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   std::lock_guard<std::mutex> lk(w->motion_mu);
@@ -215,11 +228,19 @@ int mpg_check_motion_batch(mpg_world* w, const double* q_from, const double* q_t
   if ((rc = grow((void**)&M.out, M.out_cap, (sizeof(int32_t) + 1) * n))) return rc;
   const double* from = q_from;
   const double* to = q_to;
+  const double* fp = free_pose;  // device memory: read where the caller keeps it
+  const size_t frow = (size_t)w->dw.n_free * 7;
   if (mem == MPG_MEM_HOST) {
     HIP_TRY(hipMemcpyAsync(M.edges, q_from, eb, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(M.edges + (size_t)n * dof, q_to, eb, hipMemcpyHostToDevice, s));
     from = M.edges;
     to = M.edges + (size_t)n * dof;
+    if (free_pose) {
+      const size_t fb = sizeof(double) * frow * (size_t)free_rows;
+      if ((rc = grow((void**)&M.fp, M.fp_cap, fb))) return rc;
+      HIP_TRY(hipMemcpyAsync(M.fp, free_pose, fb, hipMemcpyHostToDevice, s));
+      fp = M.fp;
+    }
   }
   const unsigned grid = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(motion_count_kernel, dim3(grid), dim3(256), 0, s, from, to, (long long)n, dof, so2_mask,
@@ -241,7 +262,17 @@ int mpg_check_motion_batch(mpg_world* w, const double* q_from, const double* q_t
   hipLaunchKernelGGL(motion_states_kernel, dim3(grid), dim3(256), 0, s, from, to, (long long)n, dof, so2_mask, M.segs,
                      M.offs, M.states);
   HIP_TRY(hipGetLastError());
-  rc = launch_collide_q(w, M.states, total, M.flags, nullptr, s);
+  if (per_edge) {  // every sub-state of edge e with edge e's pose set: a map, not total * n_free poses
+    if ((rc = grow((void**)&M.row_of, M.row_of_cap, sizeof(int32_t) * (size_t)total))) return rc;
+    hipLaunchKernelGGL(motion_rowmap_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, M.offs,
+                       (long long)n, total, M.row_of);
+    HIP_TRY(hipGetLastError());
+    rc = launch_collide_free(w, M.states, fp, (long long)frow, total, M.flags, nullptr, s, nullptr, M.row_of);
+  } else if (fp) {
+    rc = launch_collide_free(w, M.states, fp, 0ll, total, M.flags, nullptr, s);
+  } else {
+    rc = launch_collide_q(w, M.states, total, M.flags, nullptr, s);
+  }
   if (rc) return rc;
   uint8_t* d_valid = mem == MPG_MEM_DEVICE ? valid : reinterpret_cast<uint8_t*>(M.out + n);
   int32_t* d_first = first_invalid ? (mem == MPG_MEM_DEVICE ? first_invalid : M.out) : nullptr;
@@ -279,6 +310,14 @@ int mpg_distance_batch_ex(mpg_world* w, const double* q, int64_t n, int32_t n_se
 int mpg_distance_batch_req(mpg_world* w, const double* q, int64_t n, int32_t n_self_pairs,
                            const mpg_distance_request* req, double* d_self, int32_t* p_self, double* pts_self,
                            double* d_others, int32_t* p_others, double* pts_others, int mem, void* stream) {
+  return mpg_distance_batch_free(w, q, nullptr, 0, n, n_self_pairs, req, d_self, p_self, pts_self, d_others, p_others,
+                                 pts_others, mem, stream);
+}
+
+int mpg_distance_batch_free(mpg_world* w, const double* q, const double* free_pose, int64_t free_rows, int64_t n,
+                            int32_t n_self_pairs, const mpg_distance_request* req, double* d_self, int32_t* p_self,
+                            double* pts_self, double* d_others, int32_t* p_others, double* pts_others, int mem,
+                            void* stream) {
   if (!w) return set_error(MPG_E_INVALID, "world is NULL");
   if (!req) return set_error(MPG_E_INVALID, "request is NULL");
   if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
@@ -286,6 +325,7 @@ int mpg_distance_batch_req(mpg_world* w, const double* q, int64_t n, int32_t n_s
   if (n > 0 && ((!q && w->dw.dof > 0) || !d_self || !p_self || !d_others || !p_others))
     return set_error(MPG_E_INVALID, "NULL buffer");
   if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
+  if (const int frc = check_free_args(w, free_pose, free_rows, n)) return frc;
   const int32_t flags = req->flags;
   if (flags & ~(MPG_DISTANCE_SIGNED | MPG_DISTANCE_NEAREST_POINTS | MPG_DISTANCE_GJK_INDEP))
     return set_error(MPG_E_INVALID, "bad flags");
@@ -304,6 +344,8 @@ int mpg_distance_batch_req(mpg_world* w, const double* q, int64_t n, int32_t n_s
                    (flags & MPG_DISTANCE_SIGNED ? MPG_DIST_SIGNED : 0) |
                    (flags & MPG_DISTANCE_NEAREST_POINTS ? MPG_DIST_NP : 0) | (indep ? MPG_DIST_INDEP : 0);
   if (n == 0) return MPG_OK;
+  if (free_pose && mem == MPG_MEM_HOST)
+    if (const int frc = check_free_poses(free_pose, (size_t)free_rows * w->dw.n_free)) return frc;
   HIP_TRY(hipSetDevice(w->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   std::lock_guard<std::mutex> lk(w->dist_mu);
@@ -335,10 +377,18 @@ int mpg_distance_batch_req(mpg_world* w, const double* q, int64_t n, int32_t n_s
     if (!qo) qo = D.pts + 6 * n;
   }
   const unsigned grid = (unsigned)((n + 127) / 128);
-  if (w->dw.n_free) {  // link-pose rows with the current free poses, then the objects' transforms from them
+  if (w->dw.n_free) {  // link-pose rows with the call's or the current free poses, then the objects' transforms
     if ((rc = grow((void**)&D.links, D.links_cap, sizeof(double) * 7 * w->dw.n_links * n))) return rc;
-    hipLaunchKernelGGL(fk_free_kernel, dim3(grid), dim3(128), 0, s, w->dw, qin, (long long)n, D.links,
-                       (const double*)nullptr, 0ll);
+    const size_t frow = (size_t)w->dw.n_free * 7;
+    const double* fp = free_pose;  // device memory: read where the caller keeps it
+    if (free_pose && mem == MPG_MEM_HOST) {
+      const size_t fb = sizeof(double) * frow * (size_t)free_rows;
+      if ((rc = grow((void**)&D.fp, D.fp_cap, fb))) return rc;
+      HIP_TRY(hipMemcpyAsync(D.fp, free_pose, fb, hipMemcpyHostToDevice, s));
+      fp = D.fp;
+    }
+    hipLaunchKernelGGL(fk_free_kernel<false>, dim3(grid), dim3(128), 0, s, w->dw, qin, (long long)n, D.links, fp,
+                       free_rows > 1 ? (long long)frow : 0ll, (const int32_t*)nullptr);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL((pose_kernel<true>), dim3(grid), dim3(128), 0, s, w->dw, D.links, (long long)n, D.poses,
                        D.save64);
@@ -401,10 +451,20 @@ int mpg_distance_batch_req(mpg_world* w, const double* q, int64_t n, int32_t n_s
 
 int mpg_collide_contacts(mpg_world* w, const double* input, int64_t n, int input_kind, uint8_t* flags,
                          uint32_t* pair_mask, double* depth, double* normal, double* pos, int mem, void* stream) {
+  return mpg_collide_contacts_free(w, input, nullptr, 0, n, input_kind, flags, pair_mask, depth, normal, pos, mem,
+                                   stream);
+}
+
+int mpg_collide_contacts_free(mpg_world* w, const double* input, const double* free_pose, int64_t free_rows, int64_t n,
+                              int input_kind, uint8_t* flags, uint32_t* pair_mask, double* depth, double* normal,
+                              double* pos, int mem, void* stream) {
   if (!w) return set_error(MPG_E_INVALID, "world is NULL");
   if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
   if (input_kind != MPG_INPUT_Q && input_kind != MPG_INPUT_LINK_POSES) return set_error(MPG_E_INVALID, "bad input_kind");
   const bool poses = input_kind == MPG_INPUT_LINK_POSES;
+  if (poses && free_pose)
+    return set_error(MPG_E_INVALID, "link-pose rows carry the free frames' poses: free_pose must be NULL");
+  if (const int frc = check_free_args(w, free_pose, free_rows, n)) return frc;
   const size_t row = poses ? (size_t)w->dw.n_links * 7 : (size_t)w->dw.dof;
   if (n > 0 && ((!input && row > 0) || !flags || !pair_mask || !depth || !normal || !pos))
     return set_error(MPG_E_INVALID, "NULL buffer");
@@ -423,11 +483,16 @@ int mpg_collide_contacts(mpg_world* w, const double* input, int64_t n, int input
                                       (size_t)w->dw.n_free);
       if (rc) return rc;
     }
+  if (free_pose && mem == MPG_MEM_HOST)
+    if (const int frc = check_free_poses(free_pose, (size_t)free_rows * w->dw.n_free)) return frc;
   HIP_TRY(hipSetDevice(w->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t P = (size_t)w->dw.n_pairs, W = (size_t)w->dw.W;
+  const size_t frow = (size_t)w->dw.n_free * 7;
+  const long long fstride = free_rows > 1 ? (long long)frow : 0ll;
   if (mem == MPG_MEM_DEVICE) {
     ContactOut co{depth, normal, pos};
+    if (free_pose) return launch_collide_free(w, input, free_pose, fstride, n, flags, pair_mask, s, &co);
     return poses ? launch_collide<true>(w, input, n, flags, pair_mask, s, &co)
                  : launch_collide_q(w, input, n, flags, pair_mask, s, &co);
   }
@@ -449,8 +514,14 @@ int mpg_collide_contacts(mpg_world* w, const double* input, int64_t n, int input
   do {
     if (!grow((void**)&C.in, C.in_cap, sizeof(double) * std::max<size_t>(1, row * n)) ||
         !grow((void**)&C.out, C.out_cap, sizeof(double) * 7 * P * n) || !grow((void**)&C.fl, C.fl_cap, n) ||
-        !grow((void**)&C.mk, C.mk_cap, sizeof(uint32_t) * W * n)) {
+        !grow((void**)&C.mk, C.mk_cap, sizeof(uint32_t) * W * n) ||
+        (free_pose && !grow((void**)&C.fp, C.fp_cap, sizeof(double) * frow * (size_t)free_rows))) {
       rc = set_error(MPG_E_NOMEM, "contact staging buffers");
+      break;
+    }
+    if (free_pose && hipMemcpyAsync(C.fp, free_pose, sizeof(double) * frow * (size_t)free_rows,
+                                    hipMemcpyHostToDevice, s) != hipSuccess) {
+      rc = set_error(MPG_E_HIP, "copy free poses");
       break;
     }
     double *d_in = C.in, *d_out = C.out;
@@ -461,7 +532,8 @@ int mpg_collide_contacts(mpg_world* w, const double* input, int64_t n, int input
       break;
     }
     ContactOut co{d_out, d_out + P * n, d_out + 4 * P * n};
-    rc = poses ? launch_collide<true>(w, d_in, n, d_fl, d_mk, s, &co) : launch_collide_q(w, d_in, n, d_fl, d_mk, s, &co);
+    if (free_pose) rc = launch_collide_free(w, d_in, C.fp, fstride, n, d_fl, d_mk, s, &co);
+    else rc = poses ? launch_collide<true>(w, d_in, n, d_fl, d_mk, s, &co) : launch_collide_q(w, d_in, n, d_fl, d_mk, s, &co);
     if (rc) break;
     if (hipMemcpyAsync(flags, d_fl, n, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemcpyAsync(pair_mask, d_mk, sizeof(uint32_t) * W * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -484,8 +556,8 @@ int mpg_fk_batch(mpg_world* w, const double* q, int64_t n, double* link_pose, in
   const unsigned grid = (unsigned)((n + 127) / 128);
   if (mem == MPG_MEM_DEVICE) {
     if (n && w->dw.n_free)
-      hipLaunchKernelGGL(fk_free_kernel, dim3(grid), dim3(128), 0, s, w->dw, q, (long long)n, link_pose,
-                         (const double*)nullptr, 0ll);
+      hipLaunchKernelGGL(fk_free_kernel<false>, dim3(grid), dim3(128), 0, s, w->dw, q, (long long)n, link_pose,
+                         (const double*)nullptr, 0ll, (const int32_t*)nullptr);
     else if (n)
       hipLaunchKernelGGL(fk_kernel, dim3(grid), dim3(128), 0, s, w->dw, q, (long long)n, link_pose);
     HIP_TRY(hipGetLastError());
@@ -498,8 +570,8 @@ int mpg_fk_batch(mpg_world* w, const double* q, int64_t n, double* link_pose, in
   if (n == 0) return MPG_OK;
   HIP_TRY(hipMemcpyAsync(w->d_q, q, sizeof(double) * n * w->dw.dof, hipMemcpyHostToDevice, s));
   if (w->dw.n_free)
-    hipLaunchKernelGGL(fk_free_kernel, dim3(grid), dim3(128), 0, s, w->dw, w->d_q, (long long)n, w->d_out,
-                       (const double*)nullptr, 0ll);
+    hipLaunchKernelGGL(fk_free_kernel<false>, dim3(grid), dim3(128), 0, s, w->dw, w->d_q, (long long)n, w->d_out,
+                       (const double*)nullptr, 0ll, (const int32_t*)nullptr);
   else
     hipLaunchKernelGGL(fk_kernel, dim3(grid), dim3(128), 0, s, w->dw, w->d_q, (long long)n, w->d_out);
   HIP_TRY(hipGetLastError());

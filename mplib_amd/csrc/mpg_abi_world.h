@@ -33,7 +33,7 @@ int mpg_last_error_copy(char* buf, size_t size) {
   return (int)std::min<size_t>(len, 0x7fffffff);
 }
 
-const char* mpg_version(void) { return "mpgpu 0.2 (gfx950, fp64, libccd-MPR)"; }
+const char* mpg_version(void) { return "mpgpu 0.3 (gfx950, fp64, libccd-MPR)"; }
 
 int mpg_device_count(int* count) {
   if (!count) return set_error(MPG_E_INVALID, "count is NULL");
@@ -1005,6 +1005,7 @@ int mpg_world_destroy(mpg_world* w) {
   hipFree(w->dist.out);
   hipFree(w->dist.pts);
   hipFree(w->dist.links);
+  hipFree(w->dist.fp);
   if (w->dist.last) hipEventDestroy(w->dist.last);
   hipFree(w->dist.big);
   hipFree(w->dist.list);
@@ -1014,12 +1015,15 @@ int mpg_world_destroy(mpg_world* w) {
   hipFree(w->contact.out);
   hipFree(w->contact.fl);
   hipFree(w->contact.mk);
+  hipFree(w->contact.fp);
   hipFree(w->motion.edges);
   hipFree(w->motion.segs);
   hipFree(w->motion.offs);
   hipFree(w->motion.out);
   hipFree(w->motion.states);
   hipFree(w->motion.flags);
+  hipFree(w->motion.fp);
+  hipFree(w->motion.row_of);
   hipFree(w->prof_units);
   for (auto& kv : w->ws)
   {

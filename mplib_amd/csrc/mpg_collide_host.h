@@ -471,9 +471,13 @@ int collide_common(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uin
 // ---------------------------------------------------------------------------
 constexpr long long kFreeChunk = 1 << 18;  // rows per pass: n_links * 56 B each
 
-// device buffers; free_pose NULL = current poses; free_stride in doubles
+// device buffers; free_pose NULL = current poses; free_stride in doubles.
+// row_of (with free_pose and a stride): row i takes pose set row_of[i], not i;
+// each pass reads the map from its own first row on, and the pose array from
+// its start (the map holds indices into the whole array).
 int launch_collide_free(mpg_world* w, const double* q, const double* free_pose, long long free_stride, long long n,
-                        uint8_t* flags, uint32_t* masks, hipStream_t s, const ContactOut* co = nullptr) {
+                        uint8_t* flags, uint32_t* masks, hipStream_t s, const ContactOut* co = nullptr,
+                        const int32_t* row_of = nullptr) {
   if (n == 0) return MPG_OK;
   StreamPin pin(w, s);
   const long long chunk = std::min<long long>(n, std::min<long long>(kFreeChunk, w->max_chunk));
@@ -494,9 +498,14 @@ int launch_collide_free(mpg_world* w, const double* q, const double* free_pose, 
   const size_t P = (size_t)w->dw.n_pairs;
   for (long long off = 0; off < n; off += chunk) {
     const long long m = std::min(chunk, n - off);
-    hipLaunchKernelGGL(fk_free_kernel, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, w->dw,
-                       q ? q + (size_t)off * w->dw.dof : nullptr, m, ws->links,
-                       free_pose ? free_pose + (size_t)off * free_stride : nullptr, free_stride);
+    const double* qoff = q ? q + (size_t)off * w->dw.dof : nullptr;
+    if (row_of && free_pose)
+      hipLaunchKernelGGL(fk_free_kernel<true>, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, w->dw, qoff, m,
+                         ws->links, free_pose, free_stride, row_of + off);
+    else
+      hipLaunchKernelGGL(fk_free_kernel<false>, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, w->dw, qoff, m,
+                         ws->links, free_pose ? free_pose + (size_t)off * free_stride : nullptr, free_stride,
+                         (const int32_t*)nullptr);
     HIP_TRY(hipGetLastError());
     ContactOut sub{};
     if (co) sub = ContactOut{co->depth + off * P, co->normal + off * P * 3, co->pos + off * P * 3};
@@ -523,6 +532,15 @@ int check_free_poses(const double* p7, size_t count) {
     if (!(std::fabs(nq - 1.0) <= kFreeQuatTol))
       return set_error(MPG_E_INVALID, "free pose quaternion is not of unit norm (within 1e-6)");
   }
+  return MPG_OK;
+}
+
+// free_pose / free_rows of an entry point that takes the free poses per call
+// (n: its rows -- configurations, or edges)
+int check_free_args(const mpg_world* w, const double* free_pose, int64_t free_rows, int64_t n) {
+  if (free_pose && free_rows != 1 && free_rows != n)
+    return set_error(MPG_E_INVALID, "free_rows must be 1 (shared by the batch) or n (one pose set per row)");
+  if (free_pose && w->dw.n_free == 0) return set_error(MPG_E_INVALID, "the world has no free frames");
   return MPG_OK;
 }
 
@@ -561,8 +579,9 @@ int collide_free_host(mpg_world* w, const double* q, const double* free_pose, lo
     if (dof) HIP_TRY(hipMemcpyAsync(F.q, q + (size_t)off * dof, sizeof(double) * dof * m, hipMemcpyHostToDevice, s));
     if (free_pose && free_rows > 1)
       HIP_TRY(hipMemcpyAsync(F.fp, free_pose + (size_t)off * frow, sizeof(double) * frow * m, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(fk_free_kernel, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, w->dw, F.q, m, F.links,
-                       free_pose ? F.fp : nullptr, free_rows > 1 ? (long long)frow : 0ll);
+    hipLaunchKernelGGL(fk_free_kernel<false>, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, w->dw, F.q, m,
+                       F.links, free_pose ? F.fp : nullptr, free_rows > 1 ? (long long)frow : 0ll,
+                       (const int32_t*)nullptr);
     HIP_TRY(hipGetLastError());
     if (small) return collide_small<true>(w, nullptr, n, flags, pair_mask, s, F.links);
     rc = launch_collide<true>(w, F.links, m, F.fl, pair_mask ? F.mk : nullptr, s);

@@ -6458,18 +6458,39 @@ __global__ void fk_kernel(DevWorld w, const double* __restrict__ q, long long n,
 // from free_pose (row cfg * free_stride doubles in; stride 0: one pose set
 // shared by the batch) or, when free_pose is NULL, from the world's current
 // poses.  A movable object's transform is then the frame's isometry whatever
-// the source of the pose.
+// the source of the pose.  MAPPED: row cfg takes pose set row_of[cfg] instead
+// of cfg (motion validation: the sub-states of an edge share the edge's set;
+// row_of is already offset to this pass's first row, free_pose is not).
+// One set for every row is read through uniform addresses by each lane; one
+// set per row is copied by the block with its lanes along a set's doubles, so
+// that loads and stores cover whole 56 * n_free byte runs (a lane per row
+// would touch 64 lines per load).
+template <bool MAPPED>
 __global__ void fk_free_kernel(DevWorld w, const double* __restrict__ q, long long n, double* __restrict__ out,
-                               const double* __restrict__ free_pose, long long free_stride) {
-  const long long cfg = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (cfg >= n) return;
-  FkState st;
-  forward_kinematics(w, q + cfg * w.dof, st);
+                               const double* __restrict__ free_pose, long long free_stride,
+                               const int32_t* __restrict__ row_of) {
+  const long long base = (long long)blockIdx.x * blockDim.x;
+  const long long cfg = base + threadIdx.x;
   const int nk = w.n_links - w.n_free;
-  for (int l = 0; l < nk; ++l) link_transform(w, st, l, out + (cfg * w.n_links + l) * 7);
-  const double* src = free_pose ? free_pose + cfg * free_stride : w.free_cur;
-  double* dst = out + (cfg * w.n_links + nk) * 7;
-  for (int k = 0; k < w.n_free * 7; ++k) dst[k] = src[k];
+  const int fr = w.n_free * 7;
+  if (cfg < n) {
+    FkState st;
+    forward_kinematics(w, q + cfg * w.dof, st);
+    for (int l = 0; l < nk; ++l) link_transform(w, st, l, out + (cfg * w.n_links + l) * 7);
+    if (!free_pose || free_stride == 0) {
+      const double* src = free_pose ? free_pose : w.free_cur;
+      double* dst = out + (cfg * w.n_links + nk) * 7;
+      for (int k = 0; k < fr; ++k) dst[k] = src[k];
+    }
+  }
+  if (!free_pose || free_stride == 0) return;
+  const long long left = n - base;  // > 0: the grid covers n rows
+  const int tot = (int)(left < (long long)blockDim.x ? left : (long long)blockDim.x) * fr;
+  for (int i = threadIdx.x; i < tot; i += blockDim.x) {
+    const int r = i / fr, k = i - r * fr;
+    const long long row = MAPPED ? (long long)row_of[base + r] : base + r;
+    out[((base + r) * w.n_links + nk) * 7 + k] = free_pose[row * free_stride + k];
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -6537,6 +6558,24 @@ __global__ void motion_states_kernel(const double* __restrict__ from, const doub
       }
     }
   }
+}
+
+// Per-edge free poses: row_of[i] = the edge that owns sub-state i, the last e
+// with offs[e] <= i (offs is the exclusive prefix of segs >= 1, so strictly
+// increasing with offs[0] = 0).  One thread per sub-state: neighbouring lanes
+// search neighbouring keys (the same few offs lines) and store neighbouring
+// words.
+__global__ void motion_rowmap_kernel(const long long* __restrict__ offs, long long n_edges, long long total,
+                                     int32_t* __restrict__ row_of) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  long long lo = 0, hi = n_edges - 1;  // invariant: offs[lo] <= i, and hi == n_edges - 1 or offs[hi + 1] > i
+  while (lo < hi) {
+    const long long mid = lo + (hi - lo + 1) / 2;
+    if (offs[mid] <= i) lo = mid;
+    else hi = mid - 1;
+  }
+  row_of[i] = (int32_t)lo;
 }
 
 __global__ void motion_reduce_kernel(const uint8_t* __restrict__ flags, long long n, const int32_t* __restrict__ segs,

@@ -68,6 +68,10 @@ struct mpg_world {
     size_t states_cap = 0;
     uint8_t* flags = nullptr;
     size_t flags_cap = 0;
+    double* fp = nullptr;  // host-memory free poses of the call: [free_rows * n_free * 7]
+    size_t fp_cap = 0;
+    int32_t* row_of = nullptr;  // per-edge free poses: the edge of each sub-state (motion_rowmap_kernel)
+    size_t row_of_cap = 0;
     hipEvent_t last = nullptr;  // the previous call's work (scratch order across streams)
   } motion;
   std::mutex motion_mu;
@@ -94,6 +98,8 @@ struct mpg_world {
     size_t pts_cap = 0;
     double* links = nullptr;  // worlds with free frames: link-pose rows
     size_t links_cap = 0;
+    double* fp = nullptr;  // host-memory free poses of the call: [free_rows * n_free * 7]
+    size_t fp_cap = 0;
     hipEvent_t last = nullptr;  // the previous call's work (scratch order across streams)
     ccdx::BigPolytope* big = nullptr;  // kBigPool EPA polytopes (distance_redo_kernel)
     size_t big_cap = 0;
@@ -105,7 +111,8 @@ struct mpg_world {
     double *in = nullptr, *out = nullptr;
     uint8_t* fl = nullptr;
     uint32_t* mk = nullptr;
-    size_t in_cap = 0, out_cap = 0, fl_cap = 0, mk_cap = 0;
+    double* fp = nullptr;  // host-memory free poses of the call
+    size_t in_cap = 0, out_cap = 0, fl_cap = 0, mk_cap = 0, fp_cap = 0;
   } contact;
   std::mutex dist_mu;
   std::mutex prof_mu;
