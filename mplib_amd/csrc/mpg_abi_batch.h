@@ -138,8 +138,8 @@ int mpg_collide_batch_multi_device(mpg_world* const* worlds, int32_t n_worlds, c
       e = hipMemcpyPeerAsync(gather_masks + off[k] * W, w0->device, mk, w->device,
                              sizeof(uint32_t) * (size_t)counts[k] * W, s);
     if (e == hipSuccess && k > 0) {
-      if (!w->gather_ev) e = hipEventCreateWithFlags(&w->gather_ev, hipEventDisableTiming);
-      if (e == hipSuccess) e = hipEventRecord(w->gather_ev, s);
+      if (!w->gather_ev) e = w->gather_ev.create(hipEventDisableTiming);
+      if (e == hipSuccess) e = hipEventRecord(w->gather_ev.get(), s);
     }
     if (e != hipSuccess) return fail(MPG_E_HIP, std::string("gather: ") + hipGetErrorString(e));
   };
@@ -152,7 +152,7 @@ int mpg_collide_batch_multi_device(mpg_world* const* worlds, int32_t n_worlds, c
   if (gather) {  // streams[0] orders after every shard's copies
     HIP_TRY(hipSetDevice(w0->device));
     hipStream_t s0 = streams ? static_cast<hipStream_t>(streams[0]) : nullptr;
-    for (int k = 1; k < n_worlds; ++k) HIP_TRY(hipStreamWaitEvent(s0, worlds[k]->gather_ev, 0));
+    for (int k = 1; k < n_worlds; ++k) HIP_TRY(hipStreamWaitEvent(s0, worlds[k]->gather_ev.get(), 0));
   }
   return MPG_OK;
 }
@@ -178,7 +178,7 @@ int mpg_world_set_free_poses(mpg_world* w, const double* pose7) {
   std::lock_guard<std::mutex> lk(w->host_mu);
   HIP_TRY(hipDeviceSynchronize());
   std::copy(pose7, pose7 + w->free_host.size(), w->free_host.begin());
-  HIP_TRY(hipMemcpy(w->free_dev, w->free_host.data(), sizeof(double) * w->free_host.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(w->free_dev.get(), w->free_host.data(), sizeof(double) * w->free_host.size(), hipMemcpyHostToDevice));
   return MPG_OK;
 }
 
@@ -219,36 +219,39 @@ int mpg_check_motion_batch_free(mpg_world* w, const double* q_from, const double
   const int dof = w->dw.dof;
   const size_t eb = sizeof(double) * (size_t)n * dof;
   auto& M = w->motion;
-  auto grow = [&](void** p, size_t& cap, size_t want) { return scratch_grow(M.last, p, cap, want); };
+  // scratch_grow waits for M.last (the previous call's work) before it replaces a buffer
+  auto grow = [&](auto& buf, size_t count) { return scratch_grow(M.last, buf, count); };
   int rc = scratch_begin(M.last, s);
   if (rc) return rc;
-  if ((rc = grow((void**)&M.edges, M.edges_cap, 2 * eb))) return rc;
-  if ((rc = grow((void**)&M.segs, M.segs_cap, sizeof(int32_t) * n))) return rc;
-  if ((rc = grow((void**)&M.offs, M.offs_cap, sizeof(long long) * n))) return rc;
-  if ((rc = grow((void**)&M.out, M.out_cap, (sizeof(int32_t) + 1) * n))) return rc;
+  if ((rc = grow(M.edges, 2 * (size_t)n * dof))) return rc;
+  if ((rc = grow(M.segs, n))) return rc;
+  if ((rc = grow(M.offs, n))) return rc;
+  if ((rc = grow(M.out, (sizeof(int32_t) + 1) * n))) return rc;
+  double* const d_edges = M.edges.get();
+  int32_t* const d_segs = M.segs.get();
+  long long* const d_offs = M.offs.get();
   const double* from = q_from;
   const double* to = q_to;
   const double* fp = free_pose;  // device memory: read where the caller keeps it
   const size_t frow = (size_t)w->dw.n_free * 7;
   if (mem == MPG_MEM_HOST) {
-    HIP_TRY(hipMemcpyAsync(M.edges, q_from, eb, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(M.edges + (size_t)n * dof, q_to, eb, hipMemcpyHostToDevice, s));
-    from = M.edges;
-    to = M.edges + (size_t)n * dof;
+    HIP_TRY(hipMemcpyAsync(d_edges, q_from, eb, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_edges + (size_t)n * dof, q_to, eb, hipMemcpyHostToDevice, s));
+    from = d_edges;
+    to = d_edges + (size_t)n * dof;
     if (free_pose) {
-      const size_t fb = sizeof(double) * frow * (size_t)free_rows;
-      if ((rc = grow((void**)&M.fp, M.fp_cap, fb))) return rc;
-      HIP_TRY(hipMemcpyAsync(M.fp, free_pose, fb, hipMemcpyHostToDevice, s));
-      fp = M.fp;
+      if ((rc = grow(M.fp, frow * (size_t)free_rows))) return rc;
+      HIP_TRY(hipMemcpyAsync(M.fp.get(), free_pose, sizeof(double) * frow * (size_t)free_rows, hipMemcpyHostToDevice, s));
+      fp = M.fp.get();
     }
   }
   const unsigned grid = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(motion_count_kernel, dim3(grid), dim3(256), 0, s, from, to, (long long)n, dof, so2_mask,
-                     longest_valid_segment, M.segs);
+                     longest_valid_segment, d_segs);
   HIP_TRY(hipGetLastError());
   // the state count decides the allocation: one synchronisation per call
   std::vector<int32_t> segs((size_t)n);
-  HIP_TRY(hipMemcpyAsync(segs.data(), M.segs, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(segs.data(), d_segs, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   std::vector<long long> offs((size_t)n);
   long long total = 0;
@@ -256,27 +259,30 @@ int mpg_check_motion_batch_free(mpg_world* w, const double* q_from, const double
     offs[e] = total;
     total += segs[e];
   }
-  HIP_TRY(hipMemcpyAsync(M.offs, offs.data(), sizeof(long long) * n, hipMemcpyHostToDevice, s));
-  if ((rc = grow((void**)&M.states, M.states_cap, sizeof(double) * (size_t)total * dof))) return rc;
-  if ((rc = grow((void**)&M.flags, M.flags_cap, (size_t)total))) return rc;
-  hipLaunchKernelGGL(motion_states_kernel, dim3(grid), dim3(256), 0, s, from, to, (long long)n, dof, so2_mask, M.segs,
-                     M.offs, M.states);
+  HIP_TRY(hipMemcpyAsync(d_offs, offs.data(), sizeof(long long) * n, hipMemcpyHostToDevice, s));
+  if ((rc = grow(M.states, (size_t)total * dof))) return rc;
+  if ((rc = grow(M.flags, (size_t)total))) return rc;
+  double* const d_states = M.states.get();
+  uint8_t* const d_flags = M.flags.get();
+  hipLaunchKernelGGL(motion_states_kernel, dim3(grid), dim3(256), 0, s, from, to, (long long)n, dof, so2_mask, d_segs,
+                     d_offs, d_states);
   HIP_TRY(hipGetLastError());
   if (per_edge) {  // every sub-state of edge e with edge e's pose set: a map, not total * n_free poses
-    if ((rc = grow((void**)&M.row_of, M.row_of_cap, sizeof(int32_t) * (size_t)total))) return rc;
-    hipLaunchKernelGGL(motion_rowmap_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, M.offs,
-                       (long long)n, total, M.row_of);
+    if ((rc = grow(M.row_of, (size_t)total))) return rc;
+    hipLaunchKernelGGL(motion_rowmap_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_offs,
+                       (long long)n, total, M.row_of.get());
     HIP_TRY(hipGetLastError());
-    rc = launch_collide_free(w, M.states, fp, (long long)frow, total, M.flags, nullptr, s, nullptr, M.row_of);
+    rc = launch_collide_free(w, d_states, fp, (long long)frow, total, d_flags, nullptr, s, nullptr, M.row_of.get());
   } else if (fp) {
-    rc = launch_collide_free(w, M.states, fp, 0ll, total, M.flags, nullptr, s);
+    rc = launch_collide_free(w, d_states, fp, 0ll, total, d_flags, nullptr, s);
   } else {
-    rc = launch_collide_q(w, M.states, total, M.flags, nullptr, s);
+    rc = launch_collide_q(w, d_states, total, d_flags, nullptr, s);
   }
   if (rc) return rc;
-  uint8_t* d_valid = mem == MPG_MEM_DEVICE ? valid : reinterpret_cast<uint8_t*>(M.out + n);
-  int32_t* d_first = first_invalid ? (mem == MPG_MEM_DEVICE ? first_invalid : M.out) : nullptr;
-  hipLaunchKernelGGL(motion_reduce_kernel, dim3(grid), dim3(256), 0, s, M.flags, (long long)n, M.segs, M.offs, d_valid,
+  int32_t* const out_first = reinterpret_cast<int32_t*>(M.out.get());  // first_invalid[n], then valid[n] bytes
+  uint8_t* d_valid = mem == MPG_MEM_DEVICE ? valid : reinterpret_cast<uint8_t*>(out_first + n);
+  int32_t* d_first = first_invalid ? (mem == MPG_MEM_DEVICE ? first_invalid : out_first) : nullptr;
+  hipLaunchKernelGGL(motion_reduce_kernel, dim3(grid), dim3(256), 0, s, d_flags, (long long)n, d_segs, d_offs, d_valid,
                      d_first);
   HIP_TRY(hipGetLastError());
   if (mem == MPG_MEM_HOST) {
@@ -285,9 +291,9 @@ int mpg_check_motion_batch_free(mpg_world* w, const double* q_from, const double
     HIP_TRY(hipStreamSynchronize(s));
     if (segments) std::memcpy(segments, segs.data(), sizeof(int32_t) * n);
   } else if (segments) {
-    HIP_TRY(hipMemcpyAsync(segments, M.segs, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(segments, d_segs, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, s));
   }
-  HIP_TRY(hipEventRecord(M.last, s));
+  HIP_TRY(hipEventRecord(M.last.get(), s));
   return MPG_OK;
 }
 
@@ -350,54 +356,55 @@ int mpg_distance_batch_free(mpg_world* w, const double* q, const double* free_po
   hipStream_t s = static_cast<hipStream_t>(stream);
   std::lock_guard<std::mutex> lk(w->dist_mu);
   auto& D = w->dist;
-  auto grow = [&](void** p, size_t& cap, size_t want) { return scratch_grow(D.last, p, cap, want); };
+  // scratch_grow waits for D.last (the previous call's work) before it replaces a buffer
+  auto grow = [&](auto& buf, size_t count) { return scratch_grow(D.last, buf, count); };
   int rc = scratch_begin(D.last, s);
   if (rc) return rc;
   const size_t nm = std::max(w->dw.n_moving, 1), ns = std::max(w->dw.bp.n_saves, 1);
-  if ((rc = grow((void**)&D.poses, D.poses_cap, sizeof(double) * kPoseStride * nm * n))) return rc;
-  if ((rc = grow((void**)&D.save64, D.save_cap, sizeof(double) * 12 * ns * n))) return rc;
+  if ((rc = grow(D.poses, kPoseStride * nm * n))) return rc;
+  if ((rc = grow(D.save64, 12 * ns * n))) return rc;
+  double *const d_poses = D.poses.get(), *const d_save64 = D.save64.get();
   const double* qin = q;
   double *ds = d_self, *dd = d_others, *qs = pts_self, *qo = pts_others;
   int32_t *ps = p_self, *po = p_others;
   const size_t out_bytes = (2 * sizeof(double) + 2 * sizeof(int32_t) + (mode ? 12 * sizeof(double) : 0)) * n;
   if (mem == MPG_MEM_HOST) {
-    if ((rc = grow((void**)&D.q, D.q_cap, sizeof(double) * std::max(w->dw.dof, 1) * n))) return rc;
-    if ((rc = grow((void**)&D.out, D.out_cap, out_bytes))) return rc;
-    if (w->dw.dof) HIP_TRY(hipMemcpyAsync(D.q, q, sizeof(double) * w->dw.dof * n, hipMemcpyHostToDevice, s));
-    qin = D.q;
-    ds = reinterpret_cast<double*>(D.out);
+    if ((rc = grow(D.q, (size_t)std::max(w->dw.dof, 1) * n))) return rc;
+    if ((rc = grow(D.out, out_bytes))) return rc;
+    if (w->dw.dof) HIP_TRY(hipMemcpyAsync(D.q.get(), q, sizeof(double) * w->dw.dof * n, hipMemcpyHostToDevice, s));
+    qin = D.q.get();
+    ds = reinterpret_cast<double*>(D.out.get());
     dd = ds + n;
     qs = dd + n;
     qo = qs + (mode ? 6 * n : 0);
     ps = reinterpret_cast<int32_t*>(qo + (mode ? 6 * n : 0));
     po = ps + n;
   } else if (mode && (!qs || !qo)) {  // device buffers: scratch for the points nobody asked for
-    if ((rc = grow((void**)&D.pts, D.pts_cap, 12 * sizeof(double) * n))) return rc;
-    if (!qs) qs = D.pts;
-    if (!qo) qo = D.pts + 6 * n;
+    if ((rc = grow(D.pts, 12 * (size_t)n))) return rc;
+    if (!qs) qs = D.pts.get();
+    if (!qo) qo = D.pts.get() + 6 * n;
   }
   const unsigned grid = (unsigned)((n + 127) / 128);
   if (w->dw.n_free) {  // link-pose rows with the call's or the current free poses, then the objects' transforms
-    if ((rc = grow((void**)&D.links, D.links_cap, sizeof(double) * 7 * w->dw.n_links * n))) return rc;
+    if ((rc = grow(D.links, (size_t)7 * w->dw.n_links * n))) return rc;
     const size_t frow = (size_t)w->dw.n_free * 7;
     const double* fp = free_pose;  // device memory: read where the caller keeps it
     if (free_pose && mem == MPG_MEM_HOST) {
-      const size_t fb = sizeof(double) * frow * (size_t)free_rows;
-      if ((rc = grow((void**)&D.fp, D.fp_cap, fb))) return rc;
-      HIP_TRY(hipMemcpyAsync(D.fp, free_pose, fb, hipMemcpyHostToDevice, s));
-      fp = D.fp;
+      if ((rc = grow(D.fp, frow * (size_t)free_rows))) return rc;
+      HIP_TRY(hipMemcpyAsync(D.fp.get(), free_pose, sizeof(double) * frow * (size_t)free_rows, hipMemcpyHostToDevice, s));
+      fp = D.fp.get();
     }
-    hipLaunchKernelGGL(fk_free_kernel<false>, dim3(grid), dim3(128), 0, s, w->dw, qin, (long long)n, D.links, fp,
+    hipLaunchKernelGGL(fk_free_kernel<false>, dim3(grid), dim3(128), 0, s, w->dw, qin, (long long)n, D.links.get(), fp,
                        free_rows > 1 ? (long long)frow : 0ll, (const int32_t*)nullptr);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL((pose_kernel<true>), dim3(grid), dim3(128), 0, s, w->dw, D.links, (long long)n, D.poses,
-                       D.save64);
+    hipLaunchKernelGGL((pose_kernel<true>), dim3(grid), dim3(128), 0, s, w->dw, D.links.get(), (long long)n, d_poses,
+                       d_save64);
   } else {
-    hipLaunchKernelGGL((pose_kernel<false>), dim3(grid), dim3(128), 0, s, w->dw, qin, (long long)n, D.poses, D.save64);
+    hipLaunchKernelGGL((pose_kernel<false>), dim3(grid), dim3(128), 0, s, w->dw, qin, (long long)n, d_poses, d_save64);
   }
   HIP_TRY(hipGetLastError());
   auto launch = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(128), 0, s, w->dw, D.poses, (long long)n, n_self_pairs, tol, dtol, ds,
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(128), 0, s, w->dw, d_poses, (long long)n, n_self_pairs, tol, dtol, ds,
                        ps, dd, po, qs, qo);
     return hipGetLastError();
   };
@@ -413,21 +420,21 @@ int mpg_distance_batch_free(mpg_world* w, const double* q, const double* free_po
     default: HIP_TRY(launch(distance_kernel<P | NPF | IN>)); break;
   }
   if (mode & SG) {  // EPAs past the private polytope: again with a big one from the pool
-    if ((rc = grow((void**)&D.big, D.big_cap, sizeof(ccdx::BigPolytope) * kBigPool))) return rc;
-    if ((rc = grow((void**)&D.list, D.list_cap, sizeof(unsigned) * (n + 1)))) return rc;
-    HIP_TRY(hipMemsetAsync(D.list, 0, sizeof(unsigned), s));
+    if ((rc = grow(D.big, kBigPool))) return rc;
+    if ((rc = grow(D.list, (size_t)n + 1))) return rc;
+    HIP_TRY(hipMemsetAsync(D.list.get(), 0, sizeof(unsigned), s));
     hipLaunchKernelGGL(overflow_list_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ps, (long long)n,
-                       D.list);
+                       D.list.get());
     HIP_TRY(hipGetLastError());
     auto redo = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(1), dim3(kBigPool), 0, s, w->dw, D.poses, (long long)n, n_self_pairs, tol, dtol,
-                         ds, ps, dd, po, qs, qo, D.big, D.list);
+      hipLaunchKernelGGL(kern, dim3(1), dim3(kBigPool), 0, s, w->dw, d_poses, (long long)n, n_self_pairs, tol, dtol,
+                         ds, ps, dd, po, qs, qo, D.big.get(), D.list.get());
       return hipGetLastError();
     };
     if (mode & NPF) HIP_TRY(redo(distance_redo_kernel<P | SG | NPF>));
     else HIP_TRY(redo(distance_redo_kernel<P | SG>));
   }
-  HIP_TRY(hipEventRecord(D.last, s));
+  HIP_TRY(hipEventRecord(D.last.get(), s));
   if (mem == MPG_MEM_HOST) {
     HIP_TRY(hipMemcpyAsync(d_self, ds, sizeof(double) * n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(d_others, dd, sizeof(double) * n, hipMemcpyDeviceToHost, s));
@@ -499,40 +506,31 @@ int mpg_collide_contacts_free(mpg_world* w, const double* input, const double* f
   // host buffers: grow-only device staging kept by the world (one host call
   // at a time: host_mu), no allocation per call
   std::lock_guard<std::mutex> lk(w->host_mu);
-  if (!s && w->own_stream) s = w->own_stream;
-  auto grow = [&](void** p, size_t& cap, size_t want) -> bool {
-    if (cap >= want) return true;
-    if (*p) hipFree(*p);
-    *p = nullptr;
-    cap = 0;
-    if (hipMalloc(p, want) != hipSuccess) return false;
-    cap = want;
-    return true;
-  };
+  if (!s && w->own_stream) s = w->own_stream.get();
   auto& C = w->contact;
   int rc = MPG_OK;
   do {
-    if (!grow((void**)&C.in, C.in_cap, sizeof(double) * std::max<size_t>(1, row * n)) ||
-        !grow((void**)&C.out, C.out_cap, sizeof(double) * 7 * P * n) || !grow((void**)&C.fl, C.fl_cap, n) ||
-        !grow((void**)&C.mk, C.mk_cap, sizeof(uint32_t) * W * n) ||
-        (free_pose && !grow((void**)&C.fp, C.fp_cap, sizeof(double) * frow * (size_t)free_rows))) {
+    // (no wait before a staging buffer is replaced: this call is synchronous under host_mu)
+    if (C.in.reserve(std::max<size_t>(1, row * n)) != hipSuccess || C.out.reserve(7 * P * n) != hipSuccess ||
+        C.fl.reserve(n) != hipSuccess || C.mk.reserve(W * n) != hipSuccess ||
+        (free_pose && C.fp.reserve(frow * (size_t)free_rows) != hipSuccess)) {
       rc = set_error(MPG_E_NOMEM, "contact staging buffers");
       break;
     }
-    if (free_pose && hipMemcpyAsync(C.fp, free_pose, sizeof(double) * frow * (size_t)free_rows,
+    double *d_in = C.in.get(), *d_out = C.out.get(), *d_fp = C.fp.get();
+    uint8_t* d_fl = C.fl.get();
+    uint32_t* d_mk = C.mk.get();
+    if (free_pose && hipMemcpyAsync(d_fp, free_pose, sizeof(double) * frow * (size_t)free_rows,
                                     hipMemcpyHostToDevice, s) != hipSuccess) {
       rc = set_error(MPG_E_HIP, "copy free poses");
       break;
     }
-    double *d_in = C.in, *d_out = C.out;
-    uint8_t* d_fl = C.fl;
-    uint32_t* d_mk = C.mk;
     if (row && hipMemcpyAsync(d_in, input, sizeof(double) * row * n, hipMemcpyHostToDevice, s) != hipSuccess) {
       rc = set_error(MPG_E_HIP, "copy input");
       break;
     }
     ContactOut co{d_out, d_out + P * n, d_out + 4 * P * n};
-    if (free_pose) rc = launch_collide_free(w, d_in, C.fp, fstride, n, d_fl, d_mk, s, &co);
+    if (free_pose) rc = launch_collide_free(w, d_in, d_fp, fstride, n, d_fl, d_mk, s, &co);
     else rc = poses ? launch_collide<true>(w, d_in, n, d_fl, d_mk, s, &co) : launch_collide_q(w, d_in, n, d_fl, d_mk, s, &co);
     if (rc) break;
     if (hipMemcpyAsync(flags, d_fl, n, hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -568,14 +566,15 @@ int mpg_fk_batch(mpg_world* w, const double* q, int64_t n, double* link_pose, in
   int rc = ensure_staging(w, (size_t)n, std::max<size_t>(nout, 1));
   if (rc) return rc;
   if (n == 0) return MPG_OK;
-  HIP_TRY(hipMemcpyAsync(w->d_q, q, sizeof(double) * n * w->dw.dof, hipMemcpyHostToDevice, s));
+  double *const d_q = w->d_q.get(), *const d_out = w->d_out.get();
+  HIP_TRY(hipMemcpyAsync(d_q, q, sizeof(double) * n * w->dw.dof, hipMemcpyHostToDevice, s));
   if (w->dw.n_free)
-    hipLaunchKernelGGL(fk_free_kernel<false>, dim3(grid), dim3(128), 0, s, w->dw, w->d_q, (long long)n, w->d_out,
+    hipLaunchKernelGGL(fk_free_kernel<false>, dim3(grid), dim3(128), 0, s, w->dw, d_q, (long long)n, d_out,
                        (const double*)nullptr, 0ll, (const int32_t*)nullptr);
   else
-    hipLaunchKernelGGL(fk_kernel, dim3(grid), dim3(128), 0, s, w->dw, w->d_q, (long long)n, w->d_out);
+    hipLaunchKernelGGL(fk_kernel, dim3(grid), dim3(128), 0, s, w->dw, d_q, (long long)n, d_out);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(link_pose, w->d_out, sizeof(double) * nout, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(link_pose, d_out, sizeof(double) * nout, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return MPG_OK;
 }
@@ -601,30 +600,23 @@ int mpg_debug_collide_pairs(mpg_world* w, int32_t geom_a, int32_t geom_b, int64_
   if ((cf == CF_OCTREE && ta == tb) || (cf == CF_MESH && (ta == MPG_GEOM_OCTREE || tb == MPG_GEOM_OCTREE)))
     return set_error(MPG_E_UNSUPPORTED, "geometry pair not supported");
   HIP_TRY(hipSetDevice(w->device));
-  struct Guard {  // every exit path frees the buffers and the private stream
-    double *dA = nullptr, *dB = nullptr;
-    uint8_t* dh = nullptr;
-    hipStream_t s = nullptr;
-    ~Guard() {
-      if (s) hipStreamSynchronize(s);
-      hipFree(dA);
-      hipFree(dB);
-      hipFree(dh);
-      if (s) hipStreamDestroy(s);
-    }
-  } g;
-  HIP_TRY(hipStreamCreateWithFlags(&g.s, hipStreamNonBlocking));
-  HIP_TRY(hipMalloc(&g.dA, sizeof(double) * 12 * n));
-  HIP_TRY(hipMalloc(&g.dB, sizeof(double) * 12 * n));
-  HIP_TRY(hipMalloc(&g.dh, (size_t)n));
-  HIP_TRY(hipMemcpyAsync(g.dA, Ta, sizeof(double) * 12 * n, hipMemcpyHostToDevice, g.s));
-  HIP_TRY(hipMemcpyAsync(g.dB, Tb, sizeof(double) * 12 * n, hipMemcpyHostToDevice, g.s));
+  // every exit path frees the buffers, then the private stream (a failing
+  // path's queued work is waited for when the device memory is freed, which synchronises the device)
+  Stream st;
+  DevBuf<double> dA, dB;
+  DevBuf<uint8_t> dh;
+  HIP_TRY(st.create(hipStreamNonBlocking));
+  HIP_TRY(dA.reserve(12 * (size_t)n));
+  HIP_TRY(dB.reserve(12 * (size_t)n));
+  HIP_TRY(dh.reserve((size_t)n));
+  HIP_TRY(hipMemcpyAsync(dA.get(), Ta, sizeof(double) * 12 * n, hipMemcpyHostToDevice, st.get()));
+  HIP_TRY(hipMemcpyAsync(dB.get(), Tb, sizeof(double) * 12 * n, hipMemcpyHostToDevice, st.get()));
   // (walk_wave_eval finds the octree / mesh argument itself)
-  hipLaunchKernelGGL(debug_pairs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.s, w->dw, geom_a, geom_b, cf,
-                     (long long)n, g.dA, g.dB, g.dh);
+  hipLaunchKernelGGL(debug_pairs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st.get(), w->dw, geom_a,
+                     geom_b, cf, (long long)n, dA.get(), dB.get(), dh.get());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(hit, g.dh, (size_t)n, hipMemcpyDeviceToHost, g.s));
-  HIP_TRY(hipStreamSynchronize(g.s));
+  HIP_TRY(hipMemcpyAsync(hit, dh.get(), (size_t)n, hipMemcpyDeviceToHost, st.get()));
+  HIP_TRY(hipStreamSynchronize(st.get()));
   return MPG_OK;
 }
 
@@ -642,14 +634,13 @@ int mpg_sample_uniform(const double* lower, const double* upper, int32_t dof, in
     r.hi[k] = upper[k];
   }
   HIP_TRY(hipSetDevice(device));
-  double* d = nullptr;
-  HIP_TRY(hipMalloc(&d, sizeof(double) * (size_t)n * dof));
+  DevBuf<double> d;
+  HIP_TRY(d.reserve((size_t)n * dof));
   const long long tot = (long long)n * dof;
   hipLaunchKernelGGL(sample_uniform_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, 0, r, (int)dof,
-                     (long long)n, seed, (long long)row_offset, d);
+                     (long long)n, seed, (long long)row_offset, d.get());
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpy(q, d, sizeof(double) * (size_t)tot, hipMemcpyDeviceToHost);
-  hipFree(d);
+  if (e == hipSuccess) e = hipMemcpy(q, d.get(), sizeof(double) * (size_t)tot, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return set_error(MPG_E_HIP, std::string("mpg_sample_uniform: ") + hipGetErrorString(e));
   return MPG_OK;
 }
@@ -673,43 +664,34 @@ int mpg_collide_count(mpg_world* w, const double* lower, const double* upper, in
   HIP_TRY(hipSetDevice(w->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const long long chunk = std::min<long long>(n, w->max_chunk);
-  struct Bufs {  // freed on every exit path, after the stream drained
-    double* q = nullptr;
-    uint8_t* fl = nullptr;
-    uint32_t* mk = nullptr;
-    unsigned long long* cnt = nullptr;
-    hipStream_t s = nullptr;
-    ~Bufs() {
-      hipStreamSynchronize(s);
-      hipFree(q);
-      hipFree(fl);
-      hipFree(mk);
-      hipFree(cnt);
-    }
-  } b;
-  b.s = s;
-  HIP_TRY(hipMalloc(&b.q, sizeof(double) * (size_t)chunk * std::max(dof, 1)));
-  HIP_TRY(hipMalloc(&b.fl, (size_t)chunk));
-  HIP_TRY(hipMalloc(&b.mk, sizeof(uint32_t) * (size_t)chunk * W));
-  HIP_TRY(hipMalloc(&b.cnt, sizeof(unsigned long long) * P));
-  HIP_TRY(hipMemsetAsync(b.cnt, 0, sizeof(unsigned long long) * P, s));
+  // freed on every exit path (freeing device memory synchronises the device: a failing path's queued work is done)
+  DevBuf<double> bq;
+  DevBuf<uint8_t> bfl;
+  DevBuf<uint32_t> bmk;
+  DevBuf<unsigned long long> bcnt;
+  HIP_TRY(bq.reserve((size_t)chunk * std::max(dof, 1)));
+  HIP_TRY(bfl.reserve((size_t)chunk));
+  HIP_TRY(bmk.reserve((size_t)chunk * W));
+  HIP_TRY(bcnt.reserve(P));
+  HIP_TRY(hipMemsetAsync(bcnt.get(), 0, sizeof(unsigned long long) * P, s));
   for (long long off = 0; off < n; off += chunk) {
     const long long m = std::min(chunk, n - off);
     if (dof > 0) {
       const long long tot = m * dof;
       hipLaunchKernelGGL(sample_uniform_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, r, dof, m, seed,
-                         off, b.q);
+                         off, bq.get());
       HIP_TRY(hipGetLastError());
     }
-    const int rc = w->dw.n_free ? launch_collide_q(w, b.q, m, b.fl, b.mk, s)
-                                : launch_collide_overlapped<false>(w, b.q, m, b.fl, b.mk, s);
+    const int rc = w->dw.n_free ? launch_collide_q(w, bq.get(), m, bfl.get(), bmk.get(), s)
+                                : launch_collide_overlapped<false>(w, bq.get(), m, bfl.get(), bmk.get(), s);
     if (rc) return rc;
     const unsigned grid = (unsigned)std::min<long long>(1024, (m + 255) / 256);
-    hipLaunchKernelGGL(pair_count_kernel, dim3(grid), dim3(256), sizeof(uint32_t) * P, s, b.mk, m, W, P, b.cnt);
+    hipLaunchKernelGGL(pair_count_kernel, dim3(grid), dim3(256), sizeof(uint32_t) * P, s, bmk.get(), m, W, P,
+                       bcnt.get());
     HIP_TRY(hipGetLastError());
   }
   std::vector<unsigned long long> h(P);
-  HIP_TRY(hipMemcpyAsync(h.data(), b.cnt, sizeof(unsigned long long) * P, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(h.data(), bcnt.get(), sizeof(unsigned long long) * P, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   for (int p = 0; p < P; ++p) counts[p] = (int64_t)h[p];
   return MPG_OK;
@@ -719,17 +701,15 @@ int mpg_debug_sincos(const double* x, int64_t n, double* s, double* c, int devic
   if (n < 0 || (n > 0 && (!x || !s || !c))) return set_error(MPG_E_INVALID, "bad arguments");
   if (n == 0) return MPG_OK;
   HIP_TRY(hipSetDevice(device));
-  double *dx = nullptr, *ds = nullptr, *dc = nullptr;
-  HIP_TRY(hipMalloc(&dx, sizeof(double) * n));
-  HIP_TRY(hipMalloc(&ds, sizeof(double) * n));
-  HIP_TRY(hipMalloc(&dc, sizeof(double) * n));
-  HIP_TRY(hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(sincos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dx, (long long)n, ds, dc);
+  DevBuf<double> dx, ds, dc;
+  HIP_TRY(dx.reserve(n));
+  HIP_TRY(ds.reserve(n));
+  HIP_TRY(dc.reserve(n));
+  HIP_TRY(hipMemcpy(dx.get(), x, sizeof(double) * n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(sincos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dx.get(), (long long)n,
+                     ds.get(), dc.get());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(s, ds, sizeof(double) * n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(c, dc, sizeof(double) * n, hipMemcpyDeviceToHost));
-  hipFree(dx);
-  hipFree(ds);
-  hipFree(dc);
+  HIP_TRY(hipMemcpy(s, ds.get(), sizeof(double) * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(c, dc.get(), sizeof(double) * n, hipMemcpyDeviceToHost));
   return MPG_OK;
 }

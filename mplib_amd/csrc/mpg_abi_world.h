@@ -45,9 +45,9 @@ int mpg_profile_enable(mpg_world* w, int enable) {
   if (!w) return set_error(MPG_E_INVALID, "world is NULL");
   HIP_TRY(hipSetDevice(w->device));
   std::lock_guard<std::mutex> lk(w->prof_mu);
-  if (enable && !w->prof_units) {
-    HIP_TRY(hipMalloc(&w->prof_units, sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(w->prof_units, 0, sizeof(unsigned long long)));
+  if (enable && !w->prof_units.get()) {
+    HIP_TRY(w->prof_units.reserve(1));
+    HIP_TRY(hipMemset(w->prof_units.get(), 0, sizeof(unsigned long long)));
   }
   w->prof = enable != 0;
   return MPG_OK;
@@ -58,21 +58,23 @@ int mpg_profile_read(mpg_world* w, double* ms, int64_t* launches, int64_t* units
   HIP_TRY(hipSetDevice(w->device));
   std::lock_guard<std::mutex> lk(w->prof_mu);
   unsigned long long cand = 0;
-  if (w->prof_units) {
+  if (w->prof_units.get()) {
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(&cand, w->prof_units, sizeof(cand), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(w->prof_units, 0, sizeof(cand)));
+    HIP_TRY(hipMemcpy(&cand, w->prof_units.get(), sizeof(cand), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemset(w->prof_units.get(), 0, sizeof(cand)));
   }
   const int64_t u[MPG_NUM_STAGES] = {w->prof_cfg, w->prof_cfg, (int64_t)cand};
   w->prof_cfg = 0;
   for (auto& mk : w->marks) {
-    HIP_TRY(hipEventSynchronize(mk.b));
+    HIP_TRY(hipEventSynchronize(mk.b.get()));
     float t = 0.f;
-    HIP_TRY(hipEventElapsedTime(&t, mk.a, mk.b));
+    HIP_TRY(hipEventElapsedTime(&t, mk.a.get(), mk.b.get()));
     w->prof_ms[mk.stage] += t;
     w->prof_n[mk.stage] += 1;
-    w->ev_pool.push_back(mk.a);
-    w->ev_pool.push_back(mk.b);
+  }
+  for (auto& mk : w->marks) {  // the events go back to the pool once all are read
+    w->ev_pool.push_back(std::move(mk.a));
+    w->ev_pool.push_back(std::move(mk.b));
   }
   w->marks.clear();
   for (int k = 0; k < MPG_NUM_STAGES; ++k) {
@@ -685,7 +687,7 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
     if (d->moving_link[m] >= d->n_links - n_free) free_obj[d->moving_link[m] - (d->n_links - n_free)] = m;
   const size_t o_fob = n_free ? bb.add(free_obj.data(), free_obj.size()) : 0;
 
-  mpg_world* w = new mpg_world();
+  std::unique_ptr<mpg_world> w(new mpg_world());  // every failure below releases what was built
   w->device = device;
   w->n_geoms = d->n_geoms;
   w->geom_type_h.assign(d->geom_type, d->geom_type + d->n_geoms);
@@ -697,18 +699,9 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
     for (const char c : bb.bytes) h = (h ^ (uint8_t)c) * 1099511628211ull;
     w->snapshot_hash = h;
   }
-  hipError_t e = hipMalloc(&w->blob, w->blob_bytes);
-  if (e != hipSuccess) {
-    delete w;
-    return set_error(MPG_E_HIP, std::string("hipMalloc(snapshot): ") + hipGetErrorString(e));
-  }
-  e = hipMemcpy(w->blob, bb.bytes.data(), w->blob_bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    hipFree(w->blob);
-    delete w;
-    return set_error(MPG_E_HIP, std::string("hipMemcpy(snapshot): ") + hipGetErrorString(e));
-  }
-  char* base = static_cast<char*>(w->blob);
+  HIP_TRY(w->blob.reserve(w->blob_bytes));
+  HIP_TRY(hipMemcpy(w->blob.get(), bb.bytes.data(), w->blob_bytes, hipMemcpyHostToDevice));
+  char* base = w->blob.get();
   DevWorld& dw = w->dw;
   dw.nj = d->n_joints;
   dw.dof = d->dof;
@@ -737,9 +730,10 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
       for (int i = 0; i < 3; ++i) p7[i] = lp[9 + i];
       mat_to_quat(lp, &p7[3], &p7[4]);
     }
-    HIP_TRY(hipMalloc(&w->free_dev, sizeof(double) * w->free_host.size()));
-    HIP_TRY(hipMemcpy(w->free_dev, w->free_host.data(), sizeof(double) * w->free_host.size(), hipMemcpyHostToDevice));
-    dw.free_cur = w->free_dev;
+    HIP_TRY(w->free_dev.reserve(w->free_host.size()));
+    HIP_TRY(hipMemcpy(w->free_dev.get(), w->free_host.data(), sizeof(double) * w->free_host.size(),
+                      hipMemcpyHostToDevice));
+    dw.free_cur = w->free_dev.get();
   }
 #ifdef MPG_DIAG  // ablation builds only (changes results)
   if (const char* m = std::getenv("MPG_DEBUG_MARGIN")) {
@@ -757,15 +751,19 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
   dw.big_words = big_words;
   if (big_words > 0) {  // one visited set per resident wave at most (256 CUs x 32 waves)
     dw.big_slots = 8192;
-    HIP_TRY(hipMalloc(&dw.big_vis, sizeof(unsigned long long) * (size_t)dw.big_slots * big_words));
+    HIP_TRY(w->big_vis.reserve((size_t)dw.big_slots * big_words));
+    dw.big_vis = w->big_vis.get();
     HIP_TRY(hipMemset(dw.big_vis, 0, sizeof(unsigned long long) * (size_t)dw.big_slots * big_words));
-    HIP_TRY(hipMalloc(&dw.big_busy, sizeof(int) * (size_t)dw.big_slots));
+    HIP_TRY(w->big_busy.reserve((size_t)dw.big_slots));
+    dw.big_busy = w->big_busy.get();
     HIP_TRY(hipMemset(dw.big_busy, 0, sizeof(int) * (size_t)dw.big_slots));
   }
   dw.stats = nullptr;
   if (std::getenv("MPG_STATS") && std::atoi(std::getenv("MPG_STATS")) > 0) {
-    HIP_TRY(hipMalloc(&dw.stats, 64 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(dw.stats, 0, 64 * sizeof(unsigned long long)));
+    const size_t n_stats = 64;
+    HIP_TRY(w->stats.reserve(n_stats));
+    dw.stats = w->stats.get();
+    HIP_TRY(hipMemset(dw.stats, 0, n_stats * sizeof(unsigned long long)));
   }
   dw.joint_type = to_cptr<int>(base + o_jt);
   dw.joint_parent = to_cptr<int>(base + o_jp);
@@ -909,16 +907,13 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
               d->n_pairs > 0 && w->dw.W <= kSrvMaxW && w->srv_lds <= 144 * 1024 &&  // + ~11 KB static LDS
               n_free == 0;  // the resident server holds a by-value world: it would not see a pose update
   const char* own = std::getenv("MPG_OWN_STREAM");
-  if (!own || std::atoi(own) != 0) HIP_TRY(hipStreamCreateWithFlags(&w->own_stream, hipStreamNonBlocking));
-  *out = w;
+  if (!own || std::atoi(own) != 0) HIP_TRY(w->own_stream.create(hipStreamNonBlocking));
+  *out = w.release();
   return MPG_OK;
 }
 
-int mpg_world_destroy(mpg_world* w) {
-  if (!w) return MPG_OK;
-  hipSetDevice(w->device);
-  if (w->dw.big_vis) hipFree(w->dw.big_vis);
-  if (w->dw.big_busy) hipFree(w->dw.big_busy);
+// the MPG_STATS report of a world that is about to go
+static void print_stats(const mpg_world* w) {
   if (w->dw.stats) {
     unsigned long long st[64];
     hipDeviceSynchronize();
@@ -950,7 +945,6 @@ int mpg_world_destroy(mpg_world* w) {
                  "steps %llu, mean active lanes/step %.1f; hits %llu (%.2f supports each), misses %llu (%.2f)\n",
                  st[3], st[4], st[5], st[7], st[7] ? (double)st[6] / st[7] : 0.0, st[2],
                  st[2] ? (double)st[0] / st[2] : 0.0, st[8], st[8] ? (double)st[1] / st[8] : 0.0);
-    hipFree(w->dw.stats);
   }
   if (w->srv_stats && w->srv_stat[5] > 0)
     std::fprintf(stderr, "[mpg stats] latency server, mean us over %.0f batches: rows %.2f, fk %.2f, spheres %.2f, "
@@ -962,84 +956,20 @@ int mpg_world_destroy(mpg_world* w) {
                  "result wait %.1f, unpack %.1f; whole call %.1f\n", w->hp_stat[0], w->hp_stat[1] / w->hp_stat[0],
                  w->hp_stat[2] / w->hp_stat[0], w->hp_stat[3] / w->hp_stat[0], w->hp_stat[4] / w->hp_stat[0],
                  w->hp_stat[5] / w->hp_stat[0]);
-  if (w->srv_h) {  // the server leaves at its next poll
-    __atomic_store_n(&w->srv_h->quit, 1ull, __ATOMIC_RELEASE);
-    hipStreamSynchronize(w->srv_stream);
-    hipStreamDestroy(w->srv_stream);
-    hipHostFree(w->srv_h);
+}
+
+// what is ordering; the members release everything else (mpg_world.h)
+mpg_world::~mpg_world() {
+  hipSetDevice(device);
+  print_stats(this);  // before the stats buffer goes
+  if (srv.get()) {    // the server leaves at its next poll, before its control block or the snapshot goes
+    __atomic_store_n(&srv.get()->quit, 1ull, __ATOMIC_RELEASE);
+    hipStreamSynchronize(srv_stream.get());
   }
-  hipFree(w->blob);
-  if (w->h_q) hipHostFree(w->h_q);
-  if (w->h_hits) hipHostFree(w->h_hits);
-  hipFree(w->d_qs);
-  if (w->d_ssc) hipFree(w->d_ssc);
-  if (w->h_ssc) hipHostFree(w->h_ssc);
-  if (w->own_stream) hipStreamDestroy(w->own_stream);
-  for (auto& kv : w->sides) {
-    hipStreamDestroy(kv.second.side);
-    hipEventDestroy(kv.second.fork);
-    hipEventDestroy(kv.second.join);
-  }
-  hipFree(w->d_q);
-  hipFree(w->d_flags);
-  hipFree(w->d_masks);
-  hipFree(w->d_out);
-  free_ring(w);
-  w->pool.reset();
-  if (w->ring.h2d) {
-    hipStreamDestroy(w->ring.h2d);
-    hipStreamDestroy(w->ring.side);
-    for (int j = 0; j < mpg_world::kRing; ++j) {
-      hipEventDestroy(w->ring.e_in[j]);
-      hipEventDestroy(w->ring.e_done[j]);
-    }
-  }
-  for (auto& mk : w->marks) {
-    hipEventDestroy(mk.a);
-    hipEventDestroy(mk.b);
-  }
-  for (hipEvent_t e : w->ev_pool) hipEventDestroy(e);
-  hipFree(w->dist.poses);
-  hipFree(w->dist.save64);
-  hipFree(w->dist.q);
-  hipFree(w->dist.out);
-  hipFree(w->dist.pts);
-  hipFree(w->dist.links);
-  hipFree(w->dist.fp);
-  if (w->dist.last) hipEventDestroy(w->dist.last);
-  hipFree(w->dist.big);
-  hipFree(w->dist.list);
-  if (w->gather_ev) hipEventDestroy(w->gather_ev);
-  if (w->motion.last) hipEventDestroy(w->motion.last);
-  hipFree(w->contact.in);
-  hipFree(w->contact.out);
-  hipFree(w->contact.fl);
-  hipFree(w->contact.mk);
-  hipFree(w->contact.fp);
-  hipFree(w->motion.edges);
-  hipFree(w->motion.segs);
-  hipFree(w->motion.offs);
-  hipFree(w->motion.out);
-  hipFree(w->motion.states);
-  hipFree(w->motion.flags);
-  hipFree(w->motion.fp);
-  hipFree(w->motion.row_of);
-  hipFree(w->prof_units);
-  for (auto& kv : w->ws)
-  {
-    for (uint32_t* p : {kv.second.surv, kv.second.cnt, kv.second.seg_len, kv.second.seg_start, kv.second.prefix,
-                        kv.second.cand})
-      hipFree(p);
-    hipFree(kv.second.rq);
-    hipFree(kv.second.sc);
-    hipFree(kv.second.links);
-  }
-  hipFree(w->free_dev);
-  hipFree(w->free_stage.q);
-  hipFree(w->free_stage.fp);
-  hipFree(w->free_stage.links);
-  hipFree(w->free_stage.fl);
-  hipFree(w->free_stage.mk);
+  pool.reset();
+}
+
+int mpg_world_destroy(mpg_world* w) {
   delete w;
   return MPG_OK;
 }

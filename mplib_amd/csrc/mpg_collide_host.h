@@ -11,28 +11,16 @@ int ensure_small(mpg_world* w, size_t ncfg, size_t row) {
   if (ncfg <= w->small_cap && want_q <= w->small_qcap) return MPG_OK;
   ncfg = std::max(ncfg, w->small_cap);
   const size_t qcap = std::max(want_q, w->small_qcap);
-  if (w->h_q) hipHostFree(w->h_q);
-  if (w->h_hits) hipHostFree(w->h_hits);
-  if (w->d_qs) hipFree(w->d_qs);
-  if (w->d_ssc) hipFree(w->d_ssc);
-  if (w->h_ssc) hipHostFree(w->h_ssc);
-  w->d_ssc = nullptr;
-  w->h_ssc = nullptr;
-  w->h_q = nullptr;
-  w->h_hits = nullptr;
-  w->d_qs = nullptr;
+  w->small = mpg_world::Small{};  // no wait: the latency path's calls are synchronous under host_mu
   w->small_cap = 0;
   w->small_qcap = 0;
   const size_t P = (size_t)std::max(w->dw.n_pairs, 1);
-  HIP_TRY(hipHostMalloc((void**)&w->h_q, sizeof(double) * qcap, hipHostMallocMapped | hipHostMallocCoherent));
-  HIP_TRY(hipHostGetDevicePointer((void**)&w->d_qmap, w->h_q, 0));
-  HIP_TRY(hipHostMalloc((void**)&w->h_hits, P * ncfg, hipHostMallocMapped | hipHostMallocCoherent));
-  HIP_TRY(hipHostGetDevicePointer((void**)&w->d_hits, w->h_hits, 0));
-  HIP_TRY(hipMalloc(&w->d_qs, sizeof(double) * qcap));
-  HIP_TRY(hipMalloc(&w->d_ssc, sizeof(double) * 2 * ncfg * std::max<int>(w->dw.dof, 1)));
-  HIP_TRY(hipHostMalloc((void**)&w->h_ssc, sizeof(double) * 2 * ncfg * std::max<int>(w->dw.dof, 1),
-                        hipHostMallocMapped | hipHostMallocCoherent));
-  HIP_TRY(hipHostGetDevicePointer((void**)&w->d_sscmap, w->h_ssc, 0));
+  auto& S = w->small;
+  HIP_TRY(S.h_q.reserve(qcap, kPinCoherent));
+  HIP_TRY(S.h_hits.reserve(P * ncfg, kPinCoherent));
+  HIP_TRY(S.d_qs.reserve(qcap));
+  HIP_TRY(S.d_ssc.reserve(2 * ncfg * std::max<int>(w->dw.dof, 1)));
+  HIP_TRY(S.h_ssc.reserve(2 * ncfg * std::max<int>(w->dw.dof, 1), kPinCoherent));
   w->small_cap = ncfg;
   w->small_qcap = qcap;
   return MPG_OK;
@@ -40,19 +28,19 @@ int ensure_small(mpg_world* w, size_t ncfg, size_t row) {
 
 // (re)start the latency server; it takes `done` as the last batch served
 int srv_start(mpg_world* w) {
-  if (!w->srv_h) {
-    HIP_TRY(hipHostMalloc((void**)&w->srv_h, sizeof(SrvCtl), hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(w->srv_h, 0, sizeof(SrvCtl));
-    HIP_TRY(hipHostGetDevicePointer((void**)&w->srv_d, w->srv_h, 0));
-    HIP_TRY(hipStreamCreateWithFlags(&w->srv_stream, hipStreamNonBlocking));
+  if (!w->srv.get()) {
+    HIP_TRY(w->srv.reserve(1, kPinCoherent));
+    std::memset(w->srv.get(), 0, sizeof(SrvCtl));
+    HIP_TRY(w->srv_stream.create(hipStreamNonBlocking));
     HIP_TRY(hipFuncSetAttribute((const void*)lat_server_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)w->srv_lds));
   }
-  for (int k = 0; k < kSrvMaxG; ++k) __atomic_store_n(&w->srv_h->gone[k], 0ull, __ATOMIC_RELAXED);
-  __atomic_store_n(&w->srv_h->quit, 0ull, __ATOMIC_RELEASE);
+  SrvCtl* const C = w->srv.get();
+  for (int k = 0; k < kSrvMaxG; ++k) __atomic_store_n(&C->gone[k], 0ull, __ATOMIC_RELAXED);
+  __atomic_store_n(&C->quit, 0ull, __ATOMIC_RELEASE);
   ++w->srv_starts;
-  hipLaunchKernelGGL(lat_server_kernel, dim3(w->srv_g), dim3(kSrvThreads), w->srv_lds, w->srv_stream, w->dw, w->srv_d,
-                     (unsigned long long)w->srv_idle_us * 100ull, w->srv_stats ? 1 : 0);
+  hipLaunchKernelGGL(lat_server_kernel, dim3(w->srv_g), dim3(kSrvThreads), w->srv_lds, w->srv_stream.get(), w->dw,
+                     w->srv.dev(), (unsigned long long)w->srv_idle_us * 100ull, w->srv_stats ? 1 : 0);
   HIP_TRY(hipGetLastError());
   w->srv_running = true;
   return MPG_OK;
@@ -68,7 +56,7 @@ int srv_start(mpg_world* w) {
 // launches instead for a while, then tries the server again).
 int collide_served(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint32_t* pair_mask) {
   if (w->srv_running && w->srv_quitting) {  // told to quit after a missed answer
-    if (hipStreamQuery(w->srv_stream) != hipSuccess) return set_error(MPG_E_HIP, "latency server has not left yet");
+    if (hipStreamQuery(w->srv_stream.get()) != hipSuccess) return set_error(MPG_E_HIP, "latency server has not left yet");
     w->srv_running = false;
     w->srv_quitting = false;
   }
@@ -76,7 +64,7 @@ int collide_served(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uin
     const int rc = srv_start(w);
     if (rc) return rc;
   }
-  SrvCtl* C = w->srv_h;
+  SrvCtl* C = w->srv.get();
   const int dof = w->dw.dof, W = w->dw.W;
   for (int64_t c = 0; c < n; ++c) {
     double* r = C->rows + c * 3 * dof;
@@ -99,7 +87,7 @@ int collide_served(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uin
         std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
     if (us < next_us) continue;
     next_us = us + 50;
-    hipError_t e = hipStreamQuery(w->srv_stream);
+    hipError_t e = hipStreamQuery(w->srv_stream.get());
     bool partial = false;  // a workgroup left before this request, others are still resident
     for (int k = 0; k < w->srv_g && e == hipErrorNotReady; ++k)
       partial |= __atomic_load_n(&C->gone[k], __ATOMIC_ACQUIRE) != 0ull &&
@@ -108,7 +96,7 @@ int collide_served(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uin
       // stop the ones still polling and start all again (once per request);
       // they see quit within one poll, so this wait is short
       __atomic_store_n(&C->quit, 1ull, __ATOMIC_RELEASE);
-      e = hipStreamSynchronize(w->srv_stream);
+      e = hipStreamSynchronize(w->srv_stream.get());
       forced = true;
     }
     if (e == hipSuccess) {  // it left before this request: start it again
@@ -146,6 +134,31 @@ int collide_served(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uin
   return MPG_OK;
 }
 
+// folds the latency path's hit bytes h[P][n] into flags and pair masks (both
+// cleared by the caller).  The only host loop of that path over n_pairs * n
+// elements: a function of its own with a fixed alignment, so that where its
+// loops fall in a fetch line does not depend on the code around the call
+__attribute__((noinline, aligned(64))) void fold_hits(const uint8_t* h, int P, int64_t n, int W, uint8_t* flags,
+                                                      uint32_t* pair_mask) {
+  for (int p = 0; p < P; ++p) {
+    const uint8_t* hp = h + (size_t)p * n;
+    const uint32_t bit = 1u << (p & 31);
+    for (int64_t c0 = 0; c0 < n; c0 += 8) {
+      const int64_t c1 = std::min<int64_t>(c0 + 8, n);
+      if (c1 - c0 == 8) {  // most hit bytes are zero: eight at a time
+        uint64_t v;
+        std::memcpy(&v, hp + c0, 8);
+        if (!v) continue;
+      }
+      for (int64_t c = c0; c < c1; ++c)
+        if (hp[c]) {
+          flags[c] = 1;
+          if (pair_mask) pair_mask[(size_t)c * W + (p >> 5)] |= bit;
+        }
+    }
+  }
+}
+
 // one round trip: input to the device, one small_kernel launch writing hit
 // bytes straight into host memory, one synchronisation; the host folds the
 // hits into flags / pair masks
@@ -177,11 +190,12 @@ int collide_small(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint
   std::memset(flags, 0, (size_t)n);
   if (pair_mask) std::memset(pair_mask, 0, sizeof(uint32_t) * (size_t)n * W);
   if (P == 0) return MPG_OK;
-  const double* qin = dev_in ? dev_in : w->small_zero_copy ? w->d_qmap : w->d_qs;
+  const auto& S = w->small;
+  const double* qin = dev_in ? dev_in : w->small_zero_copy ? S.h_q.dev() : S.d_qs.get();
   if (row && !dev_in) {  // zero-copy: the kernel reads the pinned rows directly, no copy launch
-    std::memcpy(w->h_q, q, sizeof(double) * (size_t)n * row);
+    std::memcpy(S.h_q.get(), q, sizeof(double) * (size_t)n * row);
     if (!w->small_zero_copy)
-      HIP_TRY(hipMemcpyAsync(w->d_qs, w->h_q, sizeof(double) * (size_t)n * row, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(S.d_qs.get(), S.h_q.get(), sizeof(double) * (size_t)n * row, hipMemcpyHostToDevice, s));
   }
   const int n_tiles = (int)((n + 63) / 64);
   const long long waves = (long long)P * n_tiles;
@@ -193,22 +207,23 @@ int collide_small(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint
   // with sin/cos inline; larger: a sin/cos launch first
   const bool host_sc = !FROM_POSES && w->dw.dof > 0 && n <= w->small_host_sc;
   const bool inline_sc = !host_sc && (FROM_POSES || (n <= w->small_inline_sc && w->dw.dof <= kLatScDof));
-  double* sc_src = w->d_ssc;
+  double* sc_src = S.d_ssc.get();
+  double* const h_ssc = S.h_ssc.get();
   if (host_sc) {
     const int dof = w->dw.dof;
     for (int64_t c = 0; c < n; ++c)
       for (const int src : w->h_rev_src) {
         double sv, cv;
         mpg_sincos(q[c * dof + src], &sv, &cv);
-        w->h_ssc[(c * dof + src) * 2] = sv;
-        w->h_ssc[(c * dof + src) * 2 + 1] = cv;
+        h_ssc[(c * dof + src) * 2] = sv;
+        h_ssc[(c * dof + src) * 2 + 1] = cv;
       }
-    sc_src = w->d_sscmap;
+    sc_src = S.h_ssc.dev();
   }
   if (!inline_sc && !host_sc && w->dw.dof > 0) {
     const long long nt = n * w->dw.dof;
     hipLaunchKernelGGL(small_sincos_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, w->dw, qin,
-                       (long long)n, w->d_ssc);
+                       (long long)n, S.d_ssc.get());
     HIP_TRY(hipGetLastError());
   }
   const dim3 grid((unsigned)((waves + 3) / 4));
@@ -221,11 +236,11 @@ int collide_small(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint
     for (int64_t c = 0; c < n; ++c) {
       double* r = args.d + c * 3 * dof;
       std::memcpy(r, q + c * dof, sizeof(double) * (size_t)dof);
-      std::memcpy(r + dof, w->h_ssc + c * 2 * dof, sizeof(double) * 2 * (size_t)dof);
+      std::memcpy(r + dof, h_ssc + c * 2 * dof, sizeof(double) * 2 * (size_t)dof);
     }
   }
   auto launch = [&](auto kern) {  // every class instance reads the same sin/cos source
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, w->dw, qin, (long long)n, n_tiles, w->d_hits, sc_src, args);
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, w->dw, qin, (long long)n, n_tiles, S.h_hits.dev(), sc_src, args);
     return hipGetLastError();
   };
   auto pick = [&](auto k0, auto k1, auto k2, auto k3) {
@@ -244,16 +259,7 @@ int collide_small(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint
                  small_kernel<FROM_POSES, CLS_GJK, 2>, small_kernel<FROM_POSES, CLS_GJK, 3>));
   t_small.stop();
   HIP_TRY(hipStreamSynchronize(s));
-  const uint8_t* h = w->h_hits;
-  for (int p = 0; p < P; ++p) {
-    const uint8_t* hp = h + (size_t)p * n;
-    const uint32_t bit = 1u << (p & 31);
-    for (int64_t c = 0; c < n; ++c)
-      if (hp[c]) {
-        flags[c] = 1;
-        if (pair_mask) pair_mask[(size_t)c * W + (p >> 5)] |= bit;
-      }
-  }
+  fold_hits(S.h_hits.get(), P, n, W, flags, pair_mask);
   return MPG_OK;
 }
 
@@ -273,20 +279,23 @@ int launch_collide_overlapped(mpg_world* w, const double* in, long long n, uint8
   // different streams (one host thread each, include/mpgpu.h) never record
   // into or wait on each other's events, and each side stream has its own
   // workspace (get_workspace keys by stream)
-  mpg_world::Side sd;
+  struct {
+    hipStream_t side;
+    hipEvent_t fork, join;
+  } sd;  // the entry's handles: pinned, so it outlives this call
   {
     std::lock_guard<std::mutex> lk(w->ws_mu);
     auto it = w->sides.find(s);
     if (it == w->sides.end()) {
       if (w->ws.find(s) == w->ws.end()) evict_streams_locked(w);
-      mpg_world::Side n{};
-      HIP_TRY(hipStreamCreateWithFlags(&n.side, hipStreamNonBlocking));
-      HIP_TRY(hipEventCreateWithFlags(&n.fork, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&n.join, hipEventDisableTiming));
-      it = w->sides.emplace(s, n).first;
+      mpg_world::Side n;
+      HIP_TRY(n.side.create(hipStreamNonBlocking));
+      HIP_TRY(n.fork.create(hipEventDisableTiming));
+      HIP_TRY(n.join.create(hipEventDisableTiming));
+      it = w->sides.emplace(s, std::move(n)).first;
     }
     it->second.last = ++w->ws_tick;
-    sd = it->second;
+    sd = {it->second.side.get(), it->second.fork.get(), it->second.join.get()};
   }
   const size_t row = FROM_POSES ? (size_t)w->dw.n_links * 7 : (size_t)w->dw.dof;
   // parts alternate between the caller's stream and the side stream
@@ -346,9 +355,9 @@ struct HostPipeOps {
     auto& R = w->ring;
     const auto t0 = std::chrono::steady_clock::now();
     hipError_t e = hipSuccess;
-    if (row) e = hipMemcpyAsync(R.d_in[j], q + (size_t)start * row, sizeof(double) * (size_t)m * row,
-                                hipMemcpyHostToDevice, R.h2d);
-    if (e == hipSuccess) e = hipEventRecord(R.e_in[j], R.h2d);
+    if (row) e = hipMemcpyAsync(R.slot[j].d_in.get(), q + (size_t)start * row, sizeof(double) * (size_t)m * row,
+                                hipMemcpyHostToDevice, R.h2d.get());
+    if (e == hipSuccess) e = hipEventRecord(R.e_in[j].get(), R.h2d.get());
     t_in += us_since(t0);
     if (e != hipSuccess) return thread_fail(MPG_E_HIP, std::string("host pipeline input copy failed: ") + hipGetErrorString(e));
     return MPG_OK;
@@ -360,49 +369,53 @@ struct HostPipeOps {
   int issue_chunk(int64_t k, int j, int64_t, int64_t m) {
     auto& R = w->ring;
     const auto t0 = std::chrono::steady_clock::now();
-    const hipStream_t cs = (w->ring_streams > 1 && (k & 1)) ? R.side : s;
-    HIP_TRY(hipStreamWaitEvent(cs, R.e_in[j], 0));
-    const int rc = launch_collide<FROM_POSES>(w, R.d_in[j], m, R.d_fl[j], R.d_mk[j], cs);
+    const hipStream_t cs = (w->ring_streams > 1 && (k & 1)) ? R.side.get() : s;
+    HIP_TRY(hipStreamWaitEvent(cs, R.e_in[j].get(), 0));
+    const auto& S = R.slot[j];
+    uint8_t* const d_fl = S.d_fl.get();
+    uint32_t *const d_mk = S.d_mk.get(), *const d_bcnt = S.d_bcnt.get();
+    const int rc = launch_collide<FROM_POSES>(w, S.d_in.get(), m, d_fl, d_mk, cs);
     if (rc) return rc;
     // results straight into pinned host memory: the flags, and with masks the
     // block counts and the packed rows (no copy launches)
     const int Wp = pair_mask ? w->dw.W : 0;
     const unsigned nb = (unsigned)((m + kPackCfg - 1) / kPackCfg);
     if (Wp > 0) {
-      hipLaunchKernelGGL(flag_count_kernel, dim3(nb), dim3(256), 0, cs, R.d_fl[j], (long long)m, R.d_bcnt[j],
-                         R.h_bcnt_d[j]);
+      hipLaunchKernelGGL(flag_count_kernel, dim3(nb), dim3(256), 0, cs, d_fl, (long long)m, d_bcnt, S.h_bcnt.dev());
       HIP_TRY(hipGetLastError());
     }
     const size_t lds = sizeof(uint32_t) * 256 * (size_t)Wp;
     if (lds <= 64 * 1024)
-      hipLaunchKernelGGL(mask_pack_kernel<true>, dim3(nb), dim3(256), lds, cs, R.d_fl[j], R.d_mk[j], (long long)m, Wp,
-                         R.d_bcnt[j], R.h_mk_d[j], R.h_fl_d[j]);
+      hipLaunchKernelGGL(mask_pack_kernel<true>, dim3(nb), dim3(256), lds, cs, d_fl, d_mk, (long long)m, Wp, d_bcnt,
+                         S.h_mk.dev(), S.h_fl.dev());
     else
-      hipLaunchKernelGGL(mask_pack_kernel<false>, dim3(nb), dim3(256), 0, cs, R.d_fl[j], R.d_mk[j], (long long)m, Wp,
-                         R.d_bcnt[j], R.h_mk_d[j], R.h_fl_d[j]);
+      hipLaunchKernelGGL(mask_pack_kernel<false>, dim3(nb), dim3(256), 0, cs, d_fl, d_mk, (long long)m, Wp, d_bcnt,
+                         S.h_mk.dev(), S.h_fl.dev());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(R.e_done[j], cs));
+    HIP_TRY(hipEventRecord(R.e_done[j].get(), cs));
     t_issue += us_since(t0);
     return MPG_OK;
   }
   int finish(int64_t, int j, int64_t start, int64_t m) {
     auto& R = w->ring;
     const auto t0 = std::chrono::steady_clock::now();
-    const hipError_t e = hipEventSynchronize(R.e_done[j]);
+    const hipError_t e = hipEventSynchronize(R.e_done[j].get());
     if (e != hipSuccess) {
       fin_failed = true;
       return set_error(MPG_E_HIP, std::string("host pipeline: ") + hipGetErrorString(e));
     }
     const auto t1 = std::chrono::steady_clock::now();
     t_wait += std::chrono::duration<double, std::micro>(t1 - t0).count();
-    mpg_hostpipe::unpack_chunk(w->pool.get(), R.h_fl[j], R.h_mk[j], R.h_bcnt[j], kPackCfg, m, w->dw.W, flags + start,
+    const auto& S = R.slot[j];
+    mpg_hostpipe::unpack_chunk(w->pool.get(), S.h_fl.get(), S.h_mk.get(), S.h_bcnt.get(), kPackCfg, m, w->dw.W,
+                               flags + start,
                                pair_mask && w->dw.W > 0 ? pair_mask + (size_t)start * w->dw.W : nullptr);
     t_unpack += us_since(t1);
     return MPG_OK;
   }
   void drain() {
-    hipStreamSynchronize(w->ring.h2d);
-    hipStreamSynchronize(w->ring.side);
+    hipStreamSynchronize(w->ring.h2d.get());
+    hipStreamSynchronize(w->ring.side.get());
     hipStreamSynchronize(s);
   }
 };
@@ -454,7 +467,7 @@ int collide_common(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uin
   if (mem == MPG_MEM_DEVICE) return launch_collide_overlapped<FROM_POSES>(w, q, n, flags, pair_mask, s);
   if (mem != MPG_MEM_HOST) return set_error(MPG_E_INVALID, "bad mem kind");
   std::lock_guard<std::mutex> lk(w->host_mu);
-  if (!s && w->own_stream) s = w->own_stream;
+  if (!s && w->own_stream) s = w->own_stream.get();
   if (n == 0) return MPG_OK;
   if (n <= w->small_max) return collide_small<FROM_POSES>(w, q, n, flags, pair_mask, s);
   return collide_host_pipelined<FROM_POSES>(w, q, n, flags, pair_mask, s);
@@ -485,31 +498,28 @@ int launch_collide_free(mpg_world* w, const double* q, const double* free_pose, 
   int rc = get_workspace(w, s, chunk, &ws);
   if (rc) return rc;
   const size_t lrow = (size_t)w->dw.n_links * 7;
-  if (ws->links_cap < chunk) {  // this stream's queued work may still read the old rows
-    if (ws->links) {
-      HIP_TRY(hipStreamSynchronize(s));
-      HIP_TRY(hipFree(ws->links));
-    }
-    ws->links = nullptr;
+  if (ws->links_cap < chunk) {
+    if (ws->links.get()) HIP_TRY(hipStreamSynchronize(s));  // this stream's queued work may still read the old rows
     ws->links_cap = 0;
-    HIP_TRY(hipMalloc(&ws->links, sizeof(double) * lrow * (size_t)chunk));
+    HIP_TRY(ws->links.reserve(lrow * (size_t)chunk));
     ws->links_cap = chunk;
   }
+  double* const links = ws->links.get();
   const size_t P = (size_t)w->dw.n_pairs;
   for (long long off = 0; off < n; off += chunk) {
     const long long m = std::min(chunk, n - off);
     const double* qoff = q ? q + (size_t)off * w->dw.dof : nullptr;
     if (row_of && free_pose)
       hipLaunchKernelGGL(fk_free_kernel<true>, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, w->dw, qoff, m,
-                         ws->links, free_pose, free_stride, row_of + off);
+                         links, free_pose, free_stride, row_of + off);
     else
       hipLaunchKernelGGL(fk_free_kernel<false>, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, w->dw, qoff, m,
-                         ws->links, free_pose ? free_pose + (size_t)off * free_stride : nullptr, free_stride,
+                         links, free_pose ? free_pose + (size_t)off * free_stride : nullptr, free_stride,
                          (const int32_t*)nullptr);
     HIP_TRY(hipGetLastError());
     ContactOut sub{};
     if (co) sub = ContactOut{co->depth + off * P, co->normal + off * P * 3, co->pos + off * P * 3};
-    rc = launch_collide<true>(w, ws->links, m, flags + off, masks ? masks + (size_t)off * w->dw.W : nullptr, s,
+    rc = launch_collide<true>(w, links, m, flags + off, masks ? masks + (size_t)off * w->dw.W : nullptr, s,
                               co ? &sub : nullptr);
     if (rc) return rc;
   }
@@ -549,46 +559,41 @@ int check_free_args(const mpg_world* w, const double* free_pose, int64_t free_ro
 int collide_free_host(mpg_world* w, const double* q, const double* free_pose, long long free_rows, int64_t n,
                       uint8_t* flags, uint32_t* pair_mask, hipStream_t s) {
   auto& F = w->free_stage;
-  auto grow = [&](void** p, size_t& cap, size_t want) -> int {
-    if (cap >= want) return MPG_OK;
-    if (*p) HIP_TRY(hipFree(*p));
-    *p = nullptr;
-    cap = 0;
-    HIP_TRY(hipMalloc(p, want));
-    cap = want;
-    return MPG_OK;
-  };
   const size_t dof = (size_t)w->dw.dof, frow = (size_t)w->dw.n_free * 7, lrow = (size_t)w->dw.n_links * 7;
   const size_t W = (size_t)w->dw.W;
   const long long chunk = std::min<long long>(n, kFreeChunk);
-  int rc;
-  if ((rc = grow((void**)&F.q, F.q_cap, sizeof(double) * std::max<size_t>(1, dof * chunk)))) return rc;
-  if ((rc = grow((void**)&F.fp, F.fp_cap, sizeof(double) * frow * (free_rows > 1 ? chunk : 1)))) return rc;
-  if ((rc = grow((void**)&F.links, F.links_cap, sizeof(double) * lrow * chunk))) return rc;
+  // no wait before a staging buffer is replaced: these calls are synchronous under host_mu
+  HIP_TRY(F.q.reserve(std::max<size_t>(1, dof * chunk)));
+  HIP_TRY(F.fp.reserve(frow * (free_rows > 1 ? chunk : 1)));
+  HIP_TRY(F.links.reserve(lrow * chunk));
   // the latency kernel reads all n rows at once: only a batch that one pass
   // assembles (small_batch_max may be set above kFreeChunk)
   const bool small = n <= w->small_max && n <= chunk;
   if (!small) {
-    if ((rc = grow((void**)&F.fl, F.fl_cap, (size_t)chunk))) return rc;
-    if ((rc = grow((void**)&F.mk, F.mk_cap, sizeof(uint32_t) * W * chunk))) return rc;
+    HIP_TRY(F.fl.reserve((size_t)chunk));
+    HIP_TRY(F.mk.reserve(W * chunk));
   }
+  double *const d_q = F.q.get(), *const d_fp = F.fp.get(), *const d_links = F.links.get();
+  uint8_t* const d_fl = F.fl.get();
+  uint32_t* const d_mk = F.mk.get();
   if (free_pose && free_rows == 1)
-    HIP_TRY(hipMemcpyAsync(F.fp, free_pose, sizeof(double) * frow, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_fp, free_pose, sizeof(double) * frow, hipMemcpyHostToDevice, s));
+  int rc;
   for (long long off = 0; off < n; off += chunk) {
     const long long m = std::min<long long>(chunk, n - off);
-    if (dof) HIP_TRY(hipMemcpyAsync(F.q, q + (size_t)off * dof, sizeof(double) * dof * m, hipMemcpyHostToDevice, s));
+    if (dof) HIP_TRY(hipMemcpyAsync(d_q, q + (size_t)off * dof, sizeof(double) * dof * m, hipMemcpyHostToDevice, s));
     if (free_pose && free_rows > 1)
-      HIP_TRY(hipMemcpyAsync(F.fp, free_pose + (size_t)off * frow, sizeof(double) * frow * m, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(fk_free_kernel<false>, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, w->dw, F.q, m,
-                       F.links, free_pose ? F.fp : nullptr, free_rows > 1 ? (long long)frow : 0ll,
+      HIP_TRY(hipMemcpyAsync(d_fp, free_pose + (size_t)off * frow, sizeof(double) * frow * m, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(fk_free_kernel<false>, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, w->dw, d_q, m,
+                       d_links, free_pose ? d_fp : nullptr, free_rows > 1 ? (long long)frow : 0ll,
                        (const int32_t*)nullptr);
     HIP_TRY(hipGetLastError());
-    if (small) return collide_small<true>(w, nullptr, n, flags, pair_mask, s, F.links);
-    rc = launch_collide<true>(w, F.links, m, F.fl, pair_mask ? F.mk : nullptr, s);
+    if (small) return collide_small<true>(w, nullptr, n, flags, pair_mask, s, d_links);
+    rc = launch_collide<true>(w, d_links, m, d_fl, pair_mask ? d_mk : nullptr, s);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(flags + off, F.fl, (size_t)m, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(flags + off, d_fl, (size_t)m, hipMemcpyDeviceToHost, s));
     if (pair_mask)
-      HIP_TRY(hipMemcpyAsync(pair_mask + (size_t)off * W, F.mk, sizeof(uint32_t) * W * m, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(pair_mask + (size_t)off * W, d_mk, sizeof(uint32_t) * W * m, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
   }
   return MPG_OK;
@@ -613,7 +618,7 @@ int collide_free(mpg_world* w, const double* q, const double* free_pose, int64_t
     if (rc) return rc;
   }
   std::lock_guard<std::mutex> lk(w->host_mu);
-  if (!s && w->own_stream) s = w->own_stream;
+  if (!s && w->own_stream) s = w->own_stream.get();
   if (n == 0) return MPG_OK;
   return collide_free_host(w, q, free_pose, free_rows, n, flags, pair_mask, s);
 }

@@ -6734,6 +6734,7 @@ __global__ __launch_bounds__(256) void mask_pack_kernel(const uint8_t* __restric
 // ---------------------------------------------------------------------------
 // host side: snapshot build + C ABI
 // ---------------------------------------------------------------------------
+#include "mpg_devbuf.h"
 #include "mpg_world.h"
 
 namespace {

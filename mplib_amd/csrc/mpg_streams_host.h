@@ -3,15 +3,6 @@
 // mpg_kernels.hip in an anonymous namespace, after mpg_snapshot_host.h's choose_block).
 #pragma once
 
-void free_workspace(mpg_world::Workspace& ws) {
-  for (uint32_t* p : {ws.surv, ws.cnt, ws.seg_len, ws.seg_start, ws.prefix, ws.cand})
-    if (p) hipFree(p);
-  if (ws.rq) hipFree(ws.rq);
-  if (ws.sc) hipFree(ws.sc);
-  if (ws.links) hipFree(ws.links);
-  ws = mpg_world::Workspace{};
-}
-
 // drops the state kept for caller stream s (its workspace, its side stream
 // and the side stream's workspace); the device is synchronised first, so no
 // queued kernel still uses the buffers.  Caller holds ws_mu.
@@ -20,19 +11,9 @@ void release_stream_locked(mpg_world* w, hipStream_t s) {
   const auto si = w->sides.find(s);
   if (wi == w->ws.end() && si == w->sides.end()) return;
   hipDeviceSynchronize();
-  if (wi != w->ws.end()) {
-    free_workspace(wi->second);
-    w->ws.erase(wi);
-  }
+  if (wi != w->ws.end()) w->ws.erase(wi);
   if (si != w->sides.end()) {
-    const auto sw = w->ws.find(si->second.side);
-    if (sw != w->ws.end()) {
-      free_workspace(sw->second);
-      w->ws.erase(sw);
-    }
-    hipStreamDestroy(si->second.side);
-    hipEventDestroy(si->second.fork);
-    hipEventDestroy(si->second.join);
+    w->ws.erase(si->second.side.get());
     w->sides.erase(si);
   }
 }
@@ -44,7 +25,7 @@ void evict_streams_locked(mpg_world* w) {
   std::map<hipStream_t, uint64_t> callers;
   for (auto& kv : w->ws) callers[kv.first] = kv.second.last;
   for (auto& kv : w->sides) {
-    callers.erase(kv.second.side);
+    callers.erase(kv.second.side.get());
     uint64_t& t = callers[kv.first];
     t = std::max(t, kv.second.last);
   }
@@ -78,7 +59,7 @@ struct StreamPin {
 
 bool is_side_stream_locked(const mpg_world* w, hipStream_t s) {
   for (auto& kv : w->sides)
-    if (kv.second.side == s) return true;
+    if (kv.second.side.get() == s) return true;
   return false;
 }
 
@@ -90,31 +71,31 @@ int get_workspace(mpg_world* w, hipStream_t s, long long want, mpg_world::Worksp
   ws.last = ++w->ws_tick;
   const long long np = std::max(w->dw.n_pairs, 1);
   if (ws.cap < want) {
-    free_workspace(ws);
+    ws = mpg_world::Workspace{};  // no wait of its own: freeing device memory waits for the queued work that reads it
     ws.last = w->ws_tick;
     const long long tiles = (want + 63) / 64;
-    HIP_TRY(hipMalloc(&ws.surv, sizeof(uint32_t) * w->dw.W * want));
-    HIP_TRY(hipMalloc(&ws.cnt, sizeof(uint32_t) * np * tiles));
-    HIP_TRY(hipMalloc(&ws.seg_len, sizeof(uint32_t) * np));
-    HIP_TRY(hipMalloc(&ws.seg_start, sizeof(uint32_t) * np));
-    HIP_TRY(hipMalloc(&ws.prefix, sizeof(uint32_t) * (np + 4)));
-    HIP_TRY(hipMalloc(&ws.cand, sizeof(uint32_t) * np * want));
-    HIP_TRY(hipMalloc(&ws.rq, sizeof(float) * 4 * std::max(w->dw.n_moving, 1) * want));
-    HIP_TRY(hipMalloc(&ws.sc, sizeof(double) * 2 * std::max(w->dw.dof, 1) * want));
+    HIP_TRY(ws.surv.reserve((size_t)w->dw.W * want));
+    HIP_TRY(ws.cnt.reserve((size_t)np * tiles));
+    HIP_TRY(ws.seg_len.reserve(np));
+    HIP_TRY(ws.seg_start.reserve(np));
+    HIP_TRY(ws.prefix.reserve(np + 4));
+    HIP_TRY(ws.cand.reserve((size_t)np * want));
+    HIP_TRY(ws.rq.reserve((size_t)4 * std::max(w->dw.n_moving, 1) * want));
+    HIP_TRY(ws.sc.reserve((size_t)2 * std::max(w->dw.dof, 1) * want));
     ws.cap = want;
   }
   *out = &ws;
   return MPG_OK;
 }
 
-hipEvent_t prof_event(mpg_world* w) {
+Event prof_event(mpg_world* w) {  // empty when none could be created
+  Event e;
   if (!w->ev_pool.empty()) {
-    hipEvent_t e = w->ev_pool.back();
+    e = std::move(w->ev_pool.back());
     w->ev_pool.pop_back();
-    return e;
+  } else {
+    e.create(hipEventDefault);
   }
-  hipEvent_t e = nullptr;
-  if (hipEventCreate(&e) != hipSuccess) return nullptr;
   return e;
 }
 
@@ -123,21 +104,20 @@ struct StageTimer {
   mpg_world* w;
   hipStream_t s;
   int stage;
-  hipEvent_t a = nullptr;
+  Event a;
   StageTimer(mpg_world* w_, hipStream_t s_, int st) : w(w_), s(s_), stage(st) {
     if (!w->prof) return;
     std::lock_guard<std::mutex> lk(w->prof_mu);
     a = prof_event(w);
-    if (a) hipEventRecord(a, s);
+    if (a) hipEventRecord(a.get(), s);
   }
   void stop() {
     if (!a) return;
     std::lock_guard<std::mutex> lk(w->prof_mu);
-    hipEvent_t b = prof_event(w);
+    Event b = prof_event(w);
     if (!b) return;
-    hipEventRecord(b, s);
-    w->marks.push_back({stage, a, b});
-    a = nullptr;
+    hipEventRecord(b.get(), s);
+    w->marks.push_back({stage, std::move(a), std::move(b)});
   }
   ~StageTimer() { stop(); }
 };
@@ -152,9 +132,16 @@ int launch_collide(mpg_world* w, const double* in, long long n, uint8_t* flags, 
   if (n == 0) return MPG_OK;
   StreamPin pin(w, stream);
   const long long chunk = std::min<long long>(n, w->max_chunk);
-  mpg_world::Workspace* ws = nullptr;
-  int rc = get_workspace(w, stream, chunk, &ws);
+  mpg_world::Workspace* owner = nullptr;
+  int rc = get_workspace(w, stream, chunk, &owner);
   if (rc) return rc;
+  // the workspace as the kernels take it
+  uint32_t *const surv = owner->surv.get(), *const cnt = owner->cnt.get(), *const seg_len = owner->seg_len.get(),
+                  *const seg_start = owner->seg_start.get(), *const prefix = owner->prefix.get(),
+                  *const cand = owner->cand.get();
+  float* const rq = owner->rq.get();
+  double* const sc = owner->sc.get();
+  const long long cap = owner->cap;
   const size_t row = FROM_POSES ? (size_t)w->dw.n_links * 7 : (size_t)w->dw.dof;
   for (long long off = 0; off < n; off += chunk) {
     const long long m = std::min(chunk, n - off);
@@ -165,19 +152,19 @@ int launch_collide(mpg_world* w, const double* in, long long n, uint8_t* flags, 
     const int n_tiles = (int)((m + 63) / 64);
     StageTimer t_cull(w, stream, MPG_STAGE_CULL);
     if (w->prof) w->prof_cfg += m;
-    HIP_TRY(hipMemsetAsync(ws->cnt, 0, sizeof(uint32_t) * std::max(w->dw.n_pairs, 1) * (size_t)n_tiles, stream));
+    HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(uint32_t) * std::max(w->dw.n_pairs, 1) * (size_t)n_tiles, stream));
     switch (w->block) {
       case 256:
         hipLaunchKernelGGL((cull_kernel<256, FROM_POSES>), dim3(grid), dim3(256), w->lds_bytes, stream, w->dw, qin,
-                           m, fl, mk, ws->surv, ws->rq, ws->sc, ws->cap, ws->cnt, n_tiles);
+                           m, fl, mk, surv, rq, sc, cap, cnt, n_tiles);
         break;
       case 128:
         hipLaunchKernelGGL((cull_kernel<128, FROM_POSES>), dim3(grid), dim3(128), w->lds_bytes, stream, w->dw, qin,
-                           m, fl, mk, ws->surv, ws->rq, ws->sc, ws->cap, ws->cnt, n_tiles);
+                           m, fl, mk, surv, rq, sc, cap, cnt, n_tiles);
         break;
       default:
         hipLaunchKernelGGL((cull_kernel<64, FROM_POSES>), dim3(grid), dim3(64), w->lds_bytes, stream, w->dw, qin, m,
-                           fl, mk, ws->surv, ws->rq, ws->sc, ws->cap, ws->cnt, n_tiles);
+                           fl, mk, surv, rq, sc, cap, cnt, n_tiles);
         break;
     }
     HIP_TRY(hipGetLastError());
@@ -186,41 +173,41 @@ int launch_collide(mpg_world* w, const double* in, long long n, uint8_t* flags, 
     const long long tw = (long long)n_tiles * w->dw.W;  // one wave per (word, tile)
     const unsigned gb = (unsigned)((tw + 3) / 4);
     if (w->dw.n_pairs > 0) {
-      hipLaunchKernelGGL(pair_scan_kernel, dim3(w->dw.n_pairs), dim3(1024), 0, stream, ws->cnt, n_tiles, ws->seg_len);
+      hipLaunchKernelGGL(pair_scan_kernel, dim3(w->dw.n_pairs), dim3(1024), 0, stream, cnt, n_tiles, seg_len);
       HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(chunk_scan_kernel, dim3(1), dim3(256), 0, stream, ws->seg_len, w->dw.n_pairs, ws->seg_start,
-                       ws->prefix, w->prof ? w->prof_units : nullptr, (uint32_t)(4 * w->narrow_blocks));
+    hipLaunchKernelGGL(chunk_scan_kernel, dim3(1), dim3(256), 0, stream, seg_len, w->dw.n_pairs, seg_start,
+                       prefix, w->prof ? w->prof_units.get() : nullptr, (uint32_t)(4 * w->narrow_blocks));
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(scatter_kernel, dim3(gb), dim3(256), 0, stream, ws->surv, m, ws->cap, w->dw.n_pairs, w->dw.W,
-                       n_tiles, ws->cnt, ws->seg_start, ws->cand);
+    hipLaunchKernelGGL(scatter_kernel, dim3(gb), dim3(256), 0, stream, surv, m, cap, w->dw.n_pairs, w->dw.W,
+                       n_tiles, cnt, seg_start, cand);
     HIP_TRY(hipGetLastError());
     t_bucket.stop();
     StageTimer t_narrow(w, stream, MPG_STAGE_NARROW);
     // persistent narrow phase: enough waves to fill the chip, fewer for tiny batches
     const long long want_waves = (m * std::max(w->dw.n_pairs, 1) + kTaskMin - 1) / kTaskMin;
     const unsigned nb = (unsigned)std::max<long long>(1, std::min<long long>(w->narrow_blocks, (want_waves + 3) / 4));
-    hipLaunchKernelGGL((narrow_kernel<FROM_POSES>), dim3(nb), dim3(256), 0, stream, w->dw, qin, ws->seg_len,
-                       ws->seg_start, ws->prefix, ws->cand, fl, mk, ws->prefix + w->dw.n_pairs + 1, ws->sc);
+    hipLaunchKernelGGL((narrow_kernel<FROM_POSES>), dim3(nb), dim3(256), 0, stream, w->dw, qin, seg_len,
+                       seg_start, prefix, cand, fl, mk, prefix + w->dw.n_pairs + 1, sc);
     HIP_TRY(hipGetLastError());
     if (w->any_closed_form) {
       hipLaunchKernelGGL((closed_form_kernel<FROM_POSES, CLS_CLOSED>), dim3(w->narrow_blocks), dim3(256), 0, stream,
-                         w->dw, qin, ws->seg_len, ws->seg_start, ws->prefix, ws->cand, fl, mk, ws->sc);
+                         w->dw, qin, seg_len, seg_start, prefix, cand, fl, mk, sc);
       HIP_TRY(hipGetLastError());
     }
     if (w->any_octree) {
       hipLaunchKernelGGL((closed_form_kernel<FROM_POSES, CLS_OCTREE>), dim3(w->narrow_blocks), dim3(256), 0, stream,
-                         w->dw, qin, ws->seg_len, ws->seg_start, ws->prefix, ws->cand, fl, mk, ws->sc);
+                         w->dw, qin, seg_len, seg_start, prefix, cand, fl, mk, sc);
       HIP_TRY(hipGetLastError());
     }
     if (w->any_mesh) {
       hipLaunchKernelGGL((closed_form_kernel<FROM_POSES, CLS_MESH>), dim3(w->narrow_blocks), dim3(256), 0, stream,
-                         w->dw, qin, ws->seg_len, ws->seg_start, ws->prefix, ws->cand, fl, mk, ws->sc);
+                         w->dw, qin, seg_len, seg_start, prefix, cand, fl, mk, sc);
       HIP_TRY(hipGetLastError());
     }
     if (w->any_gjk) {
       hipLaunchKernelGGL((closed_form_kernel<FROM_POSES, CLS_GJK>), dim3(w->narrow_blocks), dim3(256), 0, stream,
-                         w->dw, qin, ws->seg_len, ws->seg_start, ws->prefix, ws->cand, fl, mk, ws->sc);
+                         w->dw, qin, seg_len, seg_start, prefix, cand, fl, mk, sc);
       HIP_TRY(hipGetLastError());
     }
     if (co) {  // penetration info of the reported pairs (enable_contact)
@@ -228,8 +215,8 @@ int launch_collide(mpg_world* w, const double* in, long long n, uint8_t* flags, 
       HIP_TRY(hipMemsetAsync(co->depth + off * P, 0, sizeof(double) * m * P, stream));
       HIP_TRY(hipMemsetAsync(co->normal + off * P * 3, 0, sizeof(double) * m * P * 3, stream));
       HIP_TRY(hipMemsetAsync(co->pos + off * P * 3, 0, sizeof(double) * m * P * 3, stream));
-      hipLaunchKernelGGL((contact_kernel<FROM_POSES>), dim3(nb), dim3(256), 0, stream, w->dw, qin, ws->seg_len,
-                         ws->seg_start, ws->prefix, ws->cand, mk, ws->sc, co->depth + off * P, co->normal + off * P * 3,
+      hipLaunchKernelGGL((contact_kernel<FROM_POSES>), dim3(nb), dim3(256), 0, stream, w->dw, qin, seg_len,
+                         seg_start, prefix, cand, mk, sc, co->depth + off * P, co->normal + off * P * 3,
                          co->pos + off * P * 3);
       HIP_TRY(hipGetLastError());
     }
@@ -238,51 +225,23 @@ int launch_collide(mpg_world* w, const double* in, long long n, uint8_t* flags, 
 }
 
 int ensure_staging(mpg_world* w, size_t ncfg, size_t nout) {
+  // no wait: the calls that use the staging are synchronous under host_mu
   if (ncfg > w->cap_cfg) {
-    hipFree(w->d_q);
-    hipFree(w->d_flags);
-    hipFree(w->d_masks);
-    w->d_q = nullptr;
-    w->d_flags = nullptr;
-    w->d_masks = nullptr;
-    HIP_TRY(hipMalloc(&w->d_q, sizeof(double) * std::max<size_t>(1, ncfg * std::max(w->dw.dof, 1))));
-    HIP_TRY(hipMalloc(&w->d_flags, std::max<size_t>(1, ncfg)));
-    HIP_TRY(hipMalloc(&w->d_masks, sizeof(uint32_t) * std::max<size_t>(1, ncfg * w->dw.W)));
+    w->d_q.reset();
+    w->d_flags.reset();
+    w->d_masks.reset();
+    w->cap_cfg = 0;
+    HIP_TRY(w->d_q.reserve(std::max<size_t>(1, ncfg * std::max(w->dw.dof, 1))));
+    HIP_TRY(w->d_flags.reserve(std::max<size_t>(1, ncfg)));
+    HIP_TRY(w->d_masks.reserve(std::max<size_t>(1, ncfg * w->dw.W)));
     w->cap_cfg = ncfg;
   }
   if (nout > w->cap_out) {
-    hipFree(w->d_out);
-    w->d_out = nullptr;
-    HIP_TRY(hipMalloc(&w->d_out, sizeof(double) * nout));
+    w->cap_out = 0;
+    HIP_TRY(w->d_out.reserve(nout));
     w->cap_out = nout;
   }
   return MPG_OK;
-}
-
-// the host pipeline's slot buffers (not its stream and events)
-void free_ring(mpg_world* w) {
-  auto& R = w->ring;
-  for (int j = 0; j < mpg_world::kRing; ++j) {
-    if (R.d_in[j]) hipFree(R.d_in[j]);
-    if (R.d_fl[j]) hipFree(R.d_fl[j]);
-    if (R.d_mk[j]) hipFree(R.d_mk[j]);
-    if (R.d_bcnt[j]) hipFree(R.d_bcnt[j]);
-    if (R.h_fl[j]) hipHostFree(R.h_fl[j]);
-    if (R.h_mk[j]) hipHostFree(R.h_mk[j]);
-    if (R.h_bcnt[j]) hipHostFree(R.h_bcnt[j]);
-    R.h_bcnt[j] = nullptr;
-    R.h_fl_d[j] = nullptr;
-    R.h_bcnt_d[j] = nullptr;
-    R.d_in[j] = nullptr;
-    R.d_fl[j] = nullptr;
-    R.d_mk[j] = nullptr;
-    R.d_bcnt[j] = nullptr;
-    R.h_fl[j] = nullptr;
-    R.h_mk[j] = nullptr;
-    R.h_mk_d[j] = nullptr;
-  }
-  R.cap = 0;
-  R.in_cap = 0;
 }
 
 // World-owned scratch (distance, motion validation) used by calls on any
@@ -291,21 +250,15 @@ void free_ring(mpg_world* w) {
 // so two host threads on two streams never run over the same buffers at once
 // (calls on one world are serialised on the device; their enqueueing already
 // is, by the world's mutex).  Caller holds the scratch's mutex.
-int scratch_begin(hipEvent_t& last, hipStream_t s) {
-  if (!last) HIP_TRY(hipEventCreateWithFlags(&last, hipEventDisableTiming));
-  else HIP_TRY(hipStreamWaitEvent(s, last, 0));
+int scratch_begin(Event& last, hipStream_t s) {
+  if (!last) HIP_TRY(last.create(hipEventDisableTiming));
+  else HIP_TRY(hipStreamWaitEvent(s, last.get(), 0));
   return MPG_OK;
 }
-int scratch_grow(hipEvent_t last, void** p, size_t& cap, size_t want) {
-  if (cap >= want) return MPG_OK;
-  if (*p) {
-    if (last) HIP_TRY(hipEventSynchronize(last));
-    HIP_TRY(hipFree(*p));
-  }
-  *p = nullptr;
-  cap = 0;
-  HIP_TRY(hipMalloc(p, want));
-  cap = want;
+template <class T>
+int scratch_grow(const Event& last, DevBuf<T>& buf, size_t n) {
+  if (buf.get() && buf.cap() < n && last) HIP_TRY(hipEventSynchronize(last.get()));  // the old block's last reader
+  HIP_TRY(buf.reserve(n));
   return MPG_OK;
 }
 
@@ -313,31 +266,31 @@ int scratch_grow(hipEvent_t last, void** p, size_t& cap, size_t want) {
 int ensure_ring(mpg_world* w, size_t cap, size_t row) {
   auto& R = w->ring;
   if (!R.h2d) {
-    HIP_TRY(hipStreamCreateWithFlags(&R.h2d, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&R.side, hipStreamNonBlocking));
+    HIP_TRY(R.h2d.create(hipStreamNonBlocking));
+    HIP_TRY(R.side.create(hipStreamNonBlocking));
     for (int j = 0; j < mpg_world::kRing; ++j) {
-      HIP_TRY(hipEventCreateWithFlags(&R.e_in[j], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&R.e_done[j], hipEventDisableTiming));
+      HIP_TRY(R.e_in[j].create(hipEventDisableTiming));
+      HIP_TRY(R.e_done[j].create(hipEventDisableTiming));
     }
   }
   const size_t in = cap * std::max<size_t>(row, 1);
   if (cap <= R.cap && in <= R.in_cap) return MPG_OK;
   cap = std::max(cap, R.cap);
   const size_t in_cap = std::max(in, R.in_cap);
-  free_ring(w);
+  // no wait: the pipeline's calls are synchronous under host_mu.  The slot
+  // buffers go, the streams and events stay.
+  for (auto& S : R.slot) S = mpg_world::Ring::Slot{};
+  R.cap = R.in_cap = 0;
   const size_t W = (size_t)std::max(w->dw.W, 1);
-  for (int j = 0; j < mpg_world::kRing; ++j) {
-    HIP_TRY(hipMalloc(&R.d_in[j], sizeof(double) * in_cap));
-    HIP_TRY(hipMalloc(&R.d_fl[j], cap));
-    HIP_TRY(hipMalloc(&R.d_mk[j], sizeof(uint32_t) * W * cap));
-    HIP_TRY(hipMalloc(&R.d_bcnt[j], sizeof(uint32_t) * ((cap + kPackCfg - 1) / kPackCfg)));
-    HIP_TRY(hipHostMalloc((void**)&R.h_fl[j], cap, hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void**)&R.h_fl_d[j], R.h_fl[j], 0));
-    HIP_TRY(hipHostMalloc((void**)&R.h_mk[j], sizeof(uint32_t) * W * cap, hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void**)&R.h_mk_d[j], R.h_mk[j], 0));
-    HIP_TRY(hipHostMalloc((void**)&R.h_bcnt[j], sizeof(uint32_t) * ((cap + kPackCfg - 1) / kPackCfg),
-                          hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void**)&R.h_bcnt_d[j], R.h_bcnt[j], 0));
+  const size_t blocks = (cap + kPackCfg - 1) / kPackCfg;
+  for (auto& S : R.slot) {
+    HIP_TRY(S.d_in.reserve(in_cap));
+    HIP_TRY(S.d_fl.reserve(cap));
+    HIP_TRY(S.d_mk.reserve(W * cap));
+    HIP_TRY(S.d_bcnt.reserve(blocks));
+    HIP_TRY(S.h_fl.reserve(cap, kPinMapped));
+    HIP_TRY(S.h_mk.reserve(W * cap, kPinMapped));
+    HIP_TRY(S.h_bcnt.reserve(blocks, kPinMapped));
   }
   R.cap = cap;
   R.in_cap = in_cap;

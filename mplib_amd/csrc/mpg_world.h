@@ -1,78 +1,93 @@
 // mpg_world.h -- struct mpg_world, the host object behind the C ABI's opaque
 // handle: snapshot, per-stream workspaces, ring, scratch (included by
 // mpg_kernels.hip at global scope, after the device code's anonymous namespace).
+//
+// Every device / pinned buffer, stream and event below is an owner of
+// mpg_devbuf.h, released by ~mpg_world in reverse declaration order.  That
+// order matters: the snapshot blob is declared first, so it goes last among
+// device memory, and within the world and each nested struct the streams and
+// events come before the buffers, so they are destroyed after the buffers are
+// freed (which synchronises the device) -- nothing is queued on a stream when
+// it goes.  What is ordering beyond that is in the destructor's body.
 #pragma once
 
 struct mpg_world {
+  ~mpg_world();  // mpg_abi_world.h
   int device = 0;
   DevWorld dw{};
   int n_geoms = 0;
   std::vector<int> geom_type_h;  // host copy of the geometry kinds (diagnostics)
-  void* blob = nullptr;
+  DevBuf<char> blob;             // the snapshot dw points into
   size_t blob_bytes = 0;
   uint64_t snapshot_hash = 0;  // FNV-1a of the snapshot blob (mpg_collide_batch_multi's same-scene check)
-  hipEvent_t gather_ev = nullptr;  // mpg_collide_batch_multi_device: this shard's gather copies are queued
+  // host-buffer calls without a stream run on this non-blocking stream (not
+  // the legacy default stream, whose synchronisation covers every blocking
+  // stream of the device); MPG_OWN_STREAM=0 keeps the caller's NULL stream
+  Stream own_stream;
+  Event gather_ev;  // mpg_collide_batch_multi_device: this shard's gather copies are queued
+  // owners of what dw holds as raw pointers: big_vis, big_busy, stats, free_cur
+  DevBuf<unsigned long long> big_vis;
+  DevBuf<int> big_busy;
+  DevBuf<unsigned long long> stats;
+  DevBuf<double> free_dev;
   int block = 128;
   size_t lds_bytes = 0;
   // staging for MPG_MEM_HOST
   std::mutex host_mu;
-  double* d_q = nullptr;
-  uint8_t* d_flags = nullptr;
-  uint32_t* d_masks = nullptr;
-  double* d_out = nullptr;
+  DevBuf<double> d_q, d_out;
+  DevBuf<uint8_t> d_flags;
+  DevBuf<uint32_t> d_masks;
   size_t cap_cfg = 0;
   size_t cap_out = 0;
   // phase A/B workspace, one per stream so concurrent streams never share it
   struct Workspace {
-    uint32_t* surv = nullptr;       // [W * cap] survivor bits, word-major
-    uint32_t* cnt = nullptr;        // [n_pairs * n_tiles] tile counts -> offsets
-    uint32_t* seg_len = nullptr;    // [n_pairs]
-    uint32_t* seg_start = nullptr;  // [n_pairs]
-    uint32_t* prefix = nullptr;     // [n_pairs + 2] task prefix + task counter
-    uint32_t* cand = nullptr;       // [n_pairs * cap] worst case
-    float* rq = nullptr;            // [n_moving * 4 * cap] phase-A rotations (quaternions) for the SAT stage
-    double* sc = nullptr;           // [cap * dof * 2] exact joint (sin, cos) for phase B
-    double* links = nullptr;        // [links_cap * n_links * 7] link-pose rows (worlds with free frames)
-    long long links_cap = 0;
-    long long cap = 0;
-    uint64_t last = 0;              // LRU tick (get_workspace)
+    DevBuf<uint32_t> surv;       // [W * cap] survivor bits, word-major
+    DevBuf<uint32_t> cnt;        // [n_pairs * n_tiles] tile counts -> offsets
+    DevBuf<uint32_t> seg_len;    // [n_pairs]
+    DevBuf<uint32_t> seg_start;  // [n_pairs]
+    DevBuf<uint32_t> prefix;     // [n_pairs + 2] task prefix + task counter
+    DevBuf<uint32_t> cand;       // [n_pairs * cap] worst case
+    DevBuf<float> rq;            // [n_moving * 4 * cap] phase-A rotations (quaternions) for the SAT stage
+    DevBuf<double> sc;           // [cap * dof * 2] exact joint (sin, cos) for phase B
+    DevBuf<double> links;        // [links_cap * n_links * 7] link-pose rows (worlds with free frames)
+    long long links_cap = 0;     // rows
+    long long cap = 0;           // configurations: the stride cull_kernel and scatter_kernel read
+    uint64_t last = 0;           // LRU tick (get_workspace)
+  };
+  // large batches: half of the parts on a side stream (per caller stream)
+  struct Side {
+    Stream side;
+    Event fork, join;
+    uint64_t last = 0;
   };
   std::mutex ws_mu;
+  std::map<hipStream_t, Side> sides;  // guarded by ws_mu
   std::map<hipStream_t, Workspace> ws;
-  // free frames: the current poses (host copy, device buffer DevWorld::free_cur
-  // points to) and the grow-only staging of host-buffer calls (host_mu)
+  // free frames: the current poses (host copy; free_dev is the device buffer
+  // DevWorld::free_cur points to) and the grow-only staging of host-buffer
+  // calls (host_mu)
   std::vector<double> free_host;
-  double* free_dev = nullptr;
   struct FreeStage {
-    double *q = nullptr, *fp = nullptr, *links = nullptr;
-    uint8_t* fl = nullptr;
-    uint32_t* mk = nullptr;
-    size_t q_cap = 0, fp_cap = 0, links_cap = 0, fl_cap = 0, mk_cap = 0;
+    DevBuf<double> q, fp, links;
+    DevBuf<uint8_t> fl;
+    DevBuf<uint32_t> mk;
   } free_stage;
   // optional per-stage timing (mpg_profile_enable)
   struct Mark {
     int stage;
-    hipEvent_t a, b;
+    Event a, b;
   };
   // batched motion validation buffers (grow-only)
   struct Motion {
-    double* edges = nullptr;
-    size_t edges_cap = 0;
-    int32_t* segs = nullptr;
-    size_t segs_cap = 0;
-    long long* offs = nullptr;
-    size_t offs_cap = 0;
-    int32_t* out = nullptr;  // staging: first_invalid[n] then valid[n] bytes
-    size_t out_cap = 0;
-    double* states = nullptr;
-    size_t states_cap = 0;
-    uint8_t* flags = nullptr;
-    size_t flags_cap = 0;
-    double* fp = nullptr;  // host-memory free poses of the call: [free_rows * n_free * 7]
-    size_t fp_cap = 0;
-    int32_t* row_of = nullptr;  // per-edge free poses: the edge of each sub-state (motion_rowmap_kernel)
-    size_t row_of_cap = 0;
-    hipEvent_t last = nullptr;  // the previous call's work (scratch order across streams)
+    Event last;  // the previous call's work (scratch order across streams)
+    DevBuf<double> edges;
+    DevBuf<int32_t> segs;
+    DevBuf<long long> offs;
+    DevBuf<char> out;  // staging: first_invalid[n] (int32) then valid[n] bytes
+    DevBuf<double> states;
+    DevBuf<uint8_t> flags;
+    DevBuf<double> fp;       // host-memory free poses of the call: [free_rows * n_free * 7]
+    DevBuf<int32_t> row_of;  // per-edge free poses: the edge of each sub-state (motion_rowmap_kernel)
   } motion;
   std::mutex motion_mu;
   bool has_closed_form = false;  // a non-allowed pair uses an FCL closed form
@@ -86,56 +101,37 @@ struct mpg_world {
   bool has_octree2 = false;      // a non-allowed pair of two OcTrees
   // batched distance buffers (grow-only)
   struct Dist {
-    double* poses = nullptr;
-    size_t poses_cap = 0;
-    double* save64 = nullptr;
-    size_t save_cap = 0;
-    double* q = nullptr;
-    size_t q_cap = 0;
-    char* out = nullptr;
-    size_t out_cap = 0;
-    double* pts = nullptr;  // device-buffer calls: points nobody asked for
-    size_t pts_cap = 0;
-    double* links = nullptr;  // worlds with free frames: link-pose rows
-    size_t links_cap = 0;
-    double* fp = nullptr;  // host-memory free poses of the call: [free_rows * n_free * 7]
-    size_t fp_cap = 0;
-    hipEvent_t last = nullptr;  // the previous call's work (scratch order across streams)
-    ccdx::BigPolytope* big = nullptr;  // kBigPool EPA polytopes (distance_redo_kernel)
-    size_t big_cap = 0;
-    unsigned* list = nullptr;  // overflowed configurations: [count, ids...]
-    size_t list_cap = 0;
+    Event last;  // the previous call's work (scratch order across streams)
+    DevBuf<double> poses, save64, q;
+    DevBuf<char> out;
+    DevBuf<double> pts;               // device-buffer calls: points nobody asked for
+    DevBuf<double> links;             // worlds with free frames: link-pose rows
+    DevBuf<double> fp;                // host-memory free poses of the call: [free_rows * n_free * 7]
+    DevBuf<ccdx::BigPolytope> big;    // kBigPool EPA polytopes (distance_redo_kernel)
+    DevBuf<unsigned> list;            // overflowed configurations: [count, ids...]
   } dist;
   // host-buffer contact calls: grow-only device staging (guarded by host_mu)
   struct ContactStage {
-    double *in = nullptr, *out = nullptr;
-    uint8_t* fl = nullptr;
-    uint32_t* mk = nullptr;
-    double* fp = nullptr;  // host-memory free poses of the call
-    size_t in_cap = 0, out_cap = 0, fl_cap = 0, mk_cap = 0, fp_cap = 0;
+    DevBuf<double> in, out;
+    DevBuf<uint8_t> fl;
+    DevBuf<uint32_t> mk;
+    DevBuf<double> fp;  // host-memory free poses of the call
   } contact;
   std::mutex dist_mu;
   std::mutex prof_mu;
   bool prof = false;
   std::vector<Mark> marks;
-  std::vector<hipEvent_t> ev_pool;
+  std::vector<Event> ev_pool;
   double prof_ms[MPG_NUM_STAGES] = {0, 0, 0};
   int64_t prof_n[MPG_NUM_STAGES] = {0, 0, 0};
   int64_t prof_cfg = 0;                       // configurations launched while profiling
-  unsigned long long* prof_units = nullptr;   // device counter: narrow candidates
+  DevBuf<unsigned long long> prof_units;      // device counter: narrow candidates
   long long max_chunk = 1 << 20;
   int narrow_blocks = 1024;
   // large batches: two halves, the second on an internal stream, so one
   // half's latency-bound bucketing overlaps the other's compute
   long long overlap_min = 1 << 18;  // 0 disables (env MPG_OVERLAP_MIN)
   int overlap_parts = 2;             // env MPG_OVERLAP_PARTS
-  // large batches: half of the parts on a side stream (per caller stream)
-  struct Side {
-    hipStream_t side;
-    hipEvent_t fork, join;
-    uint64_t last;
-  };
-  std::map<hipStream_t, Side> sides;  // guarded by ws_mu
   // per-stream state (workspaces, side streams) is kept for at most
   // kMaxStreamState caller streams, least recently used evicted first;
   // mpg_release_stream drops one explicitly
@@ -147,28 +143,22 @@ struct mpg_world {
   // small-batch latency path (host buffers, n <= small_max): pinned input
   // staging + host-mapped hit bytes written by small_kernel
   long long small_max = 1024;
-  double* h_q = nullptr;       // pinned, [small cap * row]
-  uint8_t* h_hits = nullptr;   // pinned coherent host-mapped, [n_pairs * small cap]
-  uint8_t* d_hits = nullptr;   // device alias of h_hits
-  double* d_qs = nullptr;      // device input of the latency path
-  double* d_qmap = nullptr;    // h_q as the device sees it (zero-copy input)
-  double* d_ssc = nullptr;     // latency path joint (sin, cos) [small cap * dof * 2]
-  double* h_ssc = nullptr;     // pinned host-mapped twin: sin/cos computed on the host (small batches)
-  double* d_sscmap = nullptr;  // h_ssc as the device sees it
+  struct Small {
+    PinnedBuf<double> h_q;      // pinned, [small cap * row]; dev(): the zero-copy input
+    PinnedBuf<uint8_t> h_hits;  // pinned coherent host-mapped, [n_pairs * small cap]
+    DevBuf<double> d_qs;        // device input of the latency path
+    DevBuf<double> d_ssc;       // latency path joint (sin, cos) [small cap * dof * 2]
+    PinnedBuf<double> h_ssc;    // pinned host-mapped twin: sin/cos computed on the host (small batches)
+  } small;
   int64_t small_host_sc = 64;  // latency batches up to this size: sin/cos on the host (MPG_SMALL_HOST_SC)
   bool small_args = true;      // the fewest states' rows in the kernel arguments (MPG_SMALL_ARGS=0: off)
   std::vector<int> h_rev_src;  // move-group slots of revolute joints (host copy of the snapshot's rule)
-  // host-buffer calls without a stream run on this non-blocking stream (not
-  // the legacy default stream, whose synchronisation covers every blocking
-  // stream of the device); MPG_OWN_STREAM=0 keeps the caller's NULL stream
-  hipStream_t own_stream = nullptr;
   bool small_zero_copy = true; // MPG_SMALL_ZEROCOPY=0: stage through d_qs
   int64_t small_inline_sc = 256;  // latency batches up to this size: sin/cos inline (MPG_SMALL_INLINE_SC)
   // latency server (lat_server_kernel): control block in host-mapped memory,
   // its own stream; started on demand, leaves after srv_idle_us idle
-  SrvCtl* srv_h = nullptr;
-  SrvCtl* srv_d = nullptr;
-  hipStream_t srv_stream = nullptr;
+  Stream srv_stream;
+  PinnedBuf<SrvCtl> srv;  // one control block
   unsigned long long srv_seq = 0;
   bool srv_running = false;
   bool srv_ok = false;      // the world fits the server (closed-form / MPR pairs only, records, LDS)
@@ -184,26 +174,25 @@ struct mpg_world {
   bool srv_stats = false;
   double srv_stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   size_t small_cap = 0;   // configurations (hit bytes per pair)
-  size_t small_qcap = 0;  // input doubles (h_q, d_qs)
+  size_t small_qcap = 0;  // input doubles (small.h_q, small.d_qs)
   // host-buffer batches above small_max (collide_host_pipelined): chunks
   // through a ring of slots -- the input of one chunk crosses PCIe while the
   // previous one computes and the one before is unpacked on the host.
   // Grow-only, guarded by host_mu.
   static constexpr int kRing = 3;
   struct Ring {
-    double* d_in[kRing] = {};
-    uint8_t* d_fl[kRing] = {};
-    uint32_t* d_mk[kRing] = {};
-    uint32_t* d_bcnt[kRing] = {};  // colliding configurations per kPackCfg block
-    uint8_t* h_fl[kRing] = {};     // pinned, host-mapped: the chunk's flags (mask_pack_kernel)
-    uint32_t* h_mk[kRing] = {};    // pinned, host-mapped: packed mask rows (mask_pack_kernel)
-    uint32_t* h_mk_d[kRing] = {};  // h_mk as the device sees it
-    uint32_t* h_bcnt[kRing] = {};  // pinned, host-mapped copy of d_bcnt (where each block's packed rows start)
-    uint8_t* h_fl_d[kRing] = {};   // device aliases of h_fl, h_bcnt
-    uint32_t* h_bcnt_d[kRing] = {};
-    hipEvent_t e_in[kRing] = {}, e_done[kRing] = {};
-    hipStream_t h2d = nullptr;     // input copies
-    hipStream_t side = nullptr;    // odd chunks compute here (one chunk's narrow tail overlaps the next's cull)
+    Stream h2d;   // input copies
+    Stream side;  // odd chunks compute here (one chunk's narrow tail overlaps the next's cull)
+    Event e_in[kRing], e_done[kRing];
+    struct Slot {
+      DevBuf<double> d_in;
+      DevBuf<uint8_t> d_fl;
+      DevBuf<uint32_t> d_mk;
+      DevBuf<uint32_t> d_bcnt;    // colliding configurations per kPackCfg block
+      PinnedBuf<uint8_t> h_fl;    // pinned, host-mapped: the chunk's flags (mask_pack_kernel)
+      PinnedBuf<uint32_t> h_mk;   // pinned, host-mapped: packed mask rows (mask_pack_kernel)
+      PinnedBuf<uint32_t> h_bcnt; // pinned, host-mapped copy of d_bcnt (where each block's packed rows start)
+    } slot[kRing];
     size_t cap = 0;                // configurations per slot
     size_t in_cap = 0;             // input doubles per slot
   } ring;
