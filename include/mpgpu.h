@@ -568,7 +568,7 @@ int mpg_fk_batch(mpg_world *world, const double *q, int64_t n, double *link_pose
  * for CULL and BUCKET, narrow-phase (configuration, pair) candidates for
  * NARROW.  Any output pointer may be NULL.
  *   MPG_STAGE_CULL    phase A broad phase           (cull_kernel)
- *   MPG_STAGE_BUCKET  survivor bucketing            (tile_count/pair_scan/chunk_scan/scatter)
+ *   MPG_STAGE_BUCKET  survivor bucketing            (range_sum/range_scan/scatter)
  *   MPG_STAGE_NARROW  phase B exact narrow phase    (narrow_kernel)
  */
 #define MPG_STAGE_CULL 0

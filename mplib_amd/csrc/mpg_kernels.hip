@@ -12,7 +12,7 @@
 //   A  cull_kernel      lane per configuration: fp32 FK + conservative broad
 //                       phase (mpg_broadphase.h) -> survivor bits [word][cfg]
 //      (cull also writes the per-tile survivor counts)
-//      pair_scan / chunk_scan / scatter: bucket the survivors
+//      range_sum / range_scan / scatter: bucket the survivors
 //                       into per-pair candidate lists (deterministic, no
 //                       global atomics)
 //   B  narrow_kernel    wave per 64 candidates of ONE pair: exact fp64 FK of
@@ -44,6 +44,7 @@
 #include "../../include/mpgpu.h"
 #include "mpg_math.h"
 #include "mpg_fk.h"
+#include "mpg_bucket.h"
 #include "mpg_hostpipe.h"
 
 using namespace mpg;
@@ -1320,14 +1321,17 @@ __global__ __launch_bounds__(BLOCK) void cull_kernel(DevWorld w, const double* _
     return;
   }
   // survivor words -> surv, and this wave's candidate count per pair ->
-  // cnt[pair][tile] (the bucketing's tile counts; cnt is zeroed before the
-  // launch, pairs without a survivor in the tile are skipped).  The counts
-  // are a per-wave histogram in the idle queue area: 8-bit counters (<= 64
-  // each), four per word, every lane adding its own survivors, then each lane
-  // writes the counts of pairs lane, lane + 64, ...  Worlds with more pairs
-  // than the area holds (W > kQueue / 8) take one ballot per distinct pair.
+  // its tile's row of byte counts cnt8[tile][W * 32] (mpg_bucket.h).  The
+  // counts are a per-wave histogram in the idle queue area: 8-bit counters
+  // (<= 64 each), four per word, every lane adding its own survivors; the
+  // histogram is the row, stored whole (zeros included, so nothing clears
+  // cnt between calls) by every wave that has a tile, live lanes or not.
+  // Worlds with more pairs than the area holds (W > kQueue / 8) take one
+  // ballot per distinct pair and write single bytes into a row that
+  // launch_collide has zeroed.
   bool any = false;
-  const long long tile = (cfg0 >> 6) + (tid >> 6);
+  const long long tile = bk_wave_tile(blockIdx.x, BLOCK, tid);
+  const bool has_row = bk_tile_has_row(tile, n_tiles);
   if (w.W * 8 <= kQueue) {
     uint32_t* hist = queue;
     for (int i = (int)lane; i < w.W * 8; i += 64) hist[i] = 0u;
@@ -1343,9 +1347,9 @@ __global__ __launch_bounds__(BLOCK) void cull_kernel(DevWorld w, const double* _
       }
     }
     wave_lds_sync();
-    for (int p = (int)lane; p < w.W * 32; p += 64) {
-      const uint32_t c = (hist[p >> 2] >> (8 * (p & 3))) & 0xffu;
-      if (c) cnt[(long long)p * n_tiles + tile] = c;
+    if (has_row) {
+      uint32_t* row = cnt + tile * bk_row_words(w.W);
+      for (int i = (int)lane; i < bk_row_words(w.W); i += 64) row[i] = hist[i];
     }
   } else {
     for (int k = 0; k < w.W; ++k) {
@@ -1359,7 +1363,8 @@ __global__ __launch_bounds__(BLOCK) void cull_kernel(DevWorld w, const double* _
         const int b = __builtin_ctz(xl);
         const unsigned long long bb = __ballot((x >> b) & 1u);
         x &= ~(1u << b);
-        if (lane == 0) cnt[(long long)(k * 32 + b) * n_tiles + tile] = (uint32_t)__popcll(bb);
+        if (lane == 0 && has_row)
+          reinterpret_cast<uint8_t*>(cnt)[tile * bk_cols(w.W) + k * 32 + b] = (uint8_t)__popcll(bb);
       }
     }
   }
@@ -1397,95 +1402,179 @@ __global__ __launch_bounds__(BLOCK) void cull_kernel(DevWorld w, const double* _
 
 // ---------------------------------------------------------------------------
 // Deterministic bucketing of the survivor bits into per-pair candidate lists
-// (no global atomics): count per (pair, 64-config tile) -> per-pair scan ->
-// scatter.  Candidates of a pair end up contiguous and sorted by config.
+// (no global atomics, no block waits for another): the cull's byte counts per
+// (64-config tile, pair) -> sums per range of tiles, prefixed inside groups of
+// ranges -> scan of the group totals per pair + task prefix -> scatter.
+// Candidates of a pair end up contiguous and sorted by config.  Layouts and
+// index arithmetic: mpg_bucket.h.
 // ---------------------------------------------------------------------------
-// one block per pair: exclusive scan of its tile counts (in place) + total.
-// Each thread holds up to 16 consecutive counts in registers (loads issued
-// together), one wave scan + one LDS exchange of the 16 wave totals.
-__global__ __launch_bounds__(1024) void pair_scan_kernel(uint32_t* __restrict__ cnt, int n_tiles,
-                                                        uint32_t* __restrict__ seg_len) {
-  __shared__ uint32_t part[16];
-  uint32_t* c = cnt + (long long)blockIdx.x * n_tiles;
-  const int per = (n_tiles + 1023) / 1024;
-  const int lo = threadIdx.x * per, hi = min(n_tiles, lo + per);
-  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  uint32_t v[16];
-  uint32_t sum = 0;
-  if (per <= 16) {
+constexpr int kSumCols = 256;  // count-row dwords summed at a time
+static_assert(kGroupRanges * kSumCols <= kSumSlots, "a group's sums must fit the block's LDS");
+
+// The range sums of the groups [g0, g0 + ng) by one block of NT threads
+// (ranges of these groups x min(row dwords, kSumCols) <= kSumSlots).  Lanes
+// run along the count row (one dword = four pairs each), so every load is a
+// contiguous piece of a row; the four byte counts are summed as two words of
+// two 16-bit halves.  Then one thread per (group, dword) walks the group's
+// ranges: part[range] = the exclusive prefix inside the group, grp[group] =
+// the group's total (four pairs = one 16-byte store per lane).
+template <int NT>
+__device__ __forceinline__ void range_sum_groups(const uint32_t* __restrict__ cnt, int n_tiles, int W,
+                                                 uint32_t* __restrict__ part, uint32_t* __restrict__ grp, int g0,
+                                                 int ng, uint2* sums) {
+  const int rw = bk_row_words(W), C = bk_cols(W);
+  const int n_ranges = bk_ranges(n_tiles);
+  const int r0 = bk_group_first(g0), nr = bk_group_end(g0 + ng - 1, n_ranges) - r0;
+  for (int j0 = 0; j0 < rw; j0 += kSumCols) {
+    const int jc = min(kSumCols, rw - j0);
+    for (int i = threadIdx.x; i < nr * jc; i += NT) {
+      const int rl = i / jc, jl = i % jc;
+      const int t0 = bk_range_first(r0 + rl), t1 = bk_range_end(r0 + rl, n_tiles);
+      const uint32_t* col = cnt + j0 + jl;
+      uint32_t lo = 0, hi = 0;  // pairs 4j, 4j + 2 and 4j + 1, 4j + 3
 #pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      v[k] = lo + k < hi ? c[lo + k] : 0u;
-      sum += v[k];
+      for (int k = 0; k < kRangeTiles; ++k) {
+        const uint32_t x = t0 + k < t1 ? col[(long long)(t0 + k) * rw] : 0u;
+        lo += x & 0x00ff00ffu;
+        hi += (x >> 8) & 0x00ff00ffu;
+      }
+      sums[i] = make_uint2(lo, hi);
     }
-  } else {
-    for (int i = lo; i < hi; ++i) sum += c[i];
-  }
-  const uint32_t incl = wave_inclusive_scan(sum, lane);
-  if (lane == 63u) part[wv] = incl;
-  __syncthreads();
-  uint32_t pre = 0, tot = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < 16; ++k) {
-    const uint32_t x = part[k];
-    pre += k < wv ? x : 0u;
-    tot += x;
-  }
-  uint32_t run = pre + incl - sum;
-  if (per <= 16) {
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      if (lo + k < hi) c[lo + k] = run;
-      run += v[k];
+    __syncthreads();
+    for (int i = threadIdx.x; i < ng * jc; i += NT) {
+      const int gl = i / jc, jl = i % jc;
+      const int rl1 = bk_group_end(g0 + gl, n_ranges) - r0;
+      uint32_t lo = 0, hi = 0;
+      for (int rl = bk_group_first(gl); rl < rl1; ++rl) {
+        *reinterpret_cast<uint4*>(part + (long long)(r0 + rl) * C + 4 * (j0 + jl)) =
+            make_uint4(lo & 0xffffu, hi & 0xffffu, lo >> 16, hi >> 16);
+        const uint2 s = sums[rl * jc + jl];
+        lo += s.x;
+        hi += s.y;
+      }
+      *reinterpret_cast<uint4*>(grp + (long long)(g0 + gl) * C + 4 * (j0 + jl)) =
+          make_uint4(lo & 0xffffu, hi & 0xffffu, lo >> 16, hi >> 16);
     }
-  } else {
-    for (int i = lo; i < hi; ++i) {
-      const uint32_t x = c[i];
-      c[i] = run;
-      run += x;
-    }
+    __syncthreads();
   }
-  if (threadIdx.x == 0) seg_len[blockIdx.x] = tot;
 }
 
-// segment starts + prefix of narrow-phase tasks (ts candidates of one pair
-// each): one block, 256 pairs per round.  The task size adapts to the batch:
+// one block per group of ranges
+__global__ __launch_bounds__(256) void range_sum_kernel(const uint32_t* __restrict__ cnt, int n_tiles, int W,
+                                                       uint32_t* __restrict__ part, uint32_t* __restrict__ grp) {
+  __shared__ uint2 sums[kSumSlots];
+  range_sum_groups<256>(cnt, n_tiles, W, part, grp, blockIdx.x, 1, sums);
+}
+
+#ifndef MPG_TASK_MIN
+#define MPG_TASK_MIN 8
+#endif
+constexpr uint32_t kTaskMin = MPG_TASK_MIN;
+
+constexpr int kScanRegs = 24;  // a 2^20 chunk of 5 mask words: 128 groups in 6 slabs of 22
+
+__device__ __forceinline__ uint32_t block_sum1024(uint32_t v, uint32_t* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  __syncthreads();
+  if ((threadIdx.x & 63u) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  uint32_t s = 0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) s += red[k];
+  return s;
+}
+
+// one block.  First the scan of the group totals: threads run along the pair
+// index (each load instruction reads one contiguous piece of a grp row), the
+// groups are cut into slabs across the block's threads (up to kScanRegs groups
+// of a slab in registers, loads issued together) and combined through LDS; grp
+// becomes the exclusive base of each group inside its pair and seg_len[p] the
+// pair's total.  Worlds with more pair columns than the block has threads loop
+// over the columns.  Small launches (cnt given: bk_fold_sum) first do
+// range_sum_kernel's work for every group here, which saves its launch.
+// Then the segment starts + prefix of narrow-phase tasks (ts candidates of
+// one pair each), 1024 pairs per round.  The task size adapts to the batch:
 // ts = total candidates / target tasks (the narrow grid's resident waves),
 // clamped to [kTaskMin, kTask] and rounded up to a multiple of 8 -- small
 // batches (cfg2's 2^16 self pairs: ~27k candidates) spread over the whole
 // chip instead of a few hundred full waves.  prefix[n_pairs] = task count,
 // prefix[n_pairs + 1] = the narrow phase's task counter, prefix[n_pairs + 2]
 // = ts, prefix[n_pairs + 3] = the candidate count.
-#ifndef MPG_TASK_MIN
-#define MPG_TASK_MIN 8
-#endif
-constexpr uint32_t kTaskMin = MPG_TASK_MIN;
-
-__device__ __forceinline__ uint32_t block_sum256(uint32_t v, uint32_t* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  __syncthreads();
-  if ((threadIdx.x & 63u) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
-__global__ __launch_bounds__(256) void chunk_scan_kernel(const uint32_t* __restrict__ seg_len, int n_pairs,
-                                                        uint32_t* __restrict__ seg_start,
-                                                        uint32_t* __restrict__ prefix, unsigned long long* units,
-                                                        uint32_t target_tasks) {
-  __shared__ uint32_t wl[4], wt[4], red[4];
+__global__ __launch_bounds__(1024) void range_scan_kernel(const uint32_t* __restrict__ cnt, int n_tiles, int W,
+                                                         uint32_t* __restrict__ part, uint32_t* __restrict__ grp,
+                                                         int n_groups, int n_pairs, uint32_t* seg_len,
+                                                         uint32_t* __restrict__ seg_start,
+                                                         uint32_t* __restrict__ prefix, unsigned long long* units,
+                                                         uint32_t target_tasks) {
+  __shared__ uint2 sums[kSumSlots];
+  __shared__ uint32_t wl[16], wt[16], red[16];
+  uint32_t* slab = reinterpret_cast<uint32_t*>(sums);  // [1024], after the sums are done with
+  const int tid = threadIdx.x;
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  uint32_t part = 0;
-  for (int p = (int)threadIdx.x; p < n_pairs; p += 256) part += seg_len[p];
-  const uint32_t all = block_sum256(part, red);
+  const int C = bk_cols(W);
+  if (cnt) range_sum_groups<1024>(cnt, n_tiles, W, part, grp, 0, n_groups, sums);  // ends with a block barrier
+  const bool one = C <= 1024;  // one column pass: thread p < n_pairs keeps seg_len[p] in a register
+  uint32_t my_len = 0;
+  {
+    const int CP = min(C, 1024), S = 1024 / CP, per = (n_groups + S - 1) / S;
+    const int s = tid / CP, cl = tid % CP;
+    for (int c0 = 0; c0 < C; c0 += CP) {
+      const int col = c0 + cl;
+      const bool act = s < S && col < C;
+      const int lo = s * per, hi = act ? min(n_groups, lo + per) : lo;
+      const uint32_t i0 = (uint32_t)lo * C + col;  // grp[i0 + k * C], read only for lo + k < hi
+      uint32_t v[kScanRegs];
+      uint32_t sum = 0;
+      if (per <= kScanRegs) {
+#pragma unroll
+        for (int k = 0; k < kScanRegs; ++k) {
+          v[k] = lo + k < hi ? grp[i0 + (uint32_t)k * C] : 0u;
+          sum += v[k];
+        }
+      } else {
+        for (int i = lo; i < hi; ++i) sum += grp[i0 + (uint32_t)(i - lo) * C];
+      }
+      slab[tid] = sum;
+      __syncthreads();
+      uint32_t run = 0, tot = 0;
+      for (int k = 0; k < S; ++k) {
+        const uint32_t x = slab[k * CP + cl];
+        run += k < s ? x : 0u;
+        tot += x;
+      }
+      if (per <= kScanRegs) {
+#pragma unroll
+        for (int k = 0; k < kScanRegs; ++k) {
+          if (lo + k < hi) grp[i0 + (uint32_t)k * C] = run;
+          run += v[k];
+        }
+      } else {
+        for (int i = lo; i < hi; ++i) {
+          const uint32_t x = grp[i0 + (uint32_t)(i - lo) * C];
+          grp[i0 + (uint32_t)(i - lo) * C] = run;
+          run += x;
+        }
+      }
+      if (act && s == 0 && col < n_pairs) {
+        seg_len[col] = tot;
+        my_len = tot;
+      }
+      __syncthreads();  // slab is reused; seg_len is read below
+    }
+  }
+  uint32_t psum = 0;
+  if (one) psum = my_len;
+  else
+    for (int p = tid; p < n_pairs; p += 1024) psum += seg_len[p];
+  const uint32_t all = block_sum1024(psum, red);
   uint32_t ts = target_tasks ? (all + target_tasks - 1) / target_tasks : kTask;
   ts = ts < kTaskMin ? kTaskMin : (ts > kTask ? kTask : ts);
   ts = (ts + 7u) & ~7u;
   uint32_t cl = 0, ct = 0;  // carries over rounds
-  for (int p0 = 0; p0 < n_pairs; p0 += 256) {
-    const int p = p0 + (int)threadIdx.x;
-    const uint32_t len = p < n_pairs ? seg_len[p] : 0u;
+  for (int p0 = 0; p0 < n_pairs; p0 += 1024) {
+    const int p = p0 + tid;
+    const uint32_t len = one ? my_len : (p < n_pairs ? seg_len[p] : 0u);
     const uint32_t tasks = (len + ts - 1) / ts;
     const uint32_t il = wave_inclusive_scan(len, lane), it = wave_inclusive_scan(tasks, lane);
     if (lane == 63) {
@@ -1502,7 +1591,7 @@ __global__ __launch_bounds__(256) void chunk_scan_kernel(const uint32_t* __restr
       seg_start[p] = bl + il - len;
       prefix[p] = bt + it - tasks;
     }
-    for (uint32_t k = 0; k < 4; ++k) {
+    for (uint32_t k = 0; k < 16; ++k) {
       cl += wl[k];
       ct += wt[k];
     }
@@ -1517,31 +1606,39 @@ __global__ __launch_bounds__(256) void chunk_scan_kernel(const uint32_t* __restr
   }
 }
 
-// one wave per (survivor word, 64-config tile): the slot bases of the
-// word's surviving pairs come in one parallel load (lane b: pair 32 wd + b),
-// then each surviving pair's configurations are written at base + rank
+// one wave per (survivor word, 64-config tile).  Lane b < 32 holds the slot
+// base of pair 32 wd + b in the tile: the pair's segment start + its group's
+// base + the range's prefix inside the group + the counts of the range's
+// tiles before this one.  Every term is a load of its own, issued together
+// with the tile's own counts and its surv word column, so a wave waits for
+// memory once.  The surviving pairs are the ballot of count != 0; each one's
+// configurations are written at base + rank.
 __global__ __launch_bounds__(256) void scatter_kernel(const uint32_t* __restrict__ surv, long long n, long long cap,
                                                      int n_pairs, int W, int n_tiles,
-                                                     const uint32_t* __restrict__ off,
+                                                     const uint32_t* __restrict__ cnt,
+                                                     const uint32_t* __restrict__ part,
+                                                     const uint32_t* __restrict__ grp,
                                                      const uint32_t* __restrict__ seg_start,
                                                      uint32_t* __restrict__ cand) {
   const uint32_t lane = lane_id();
   const long long wid = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
   if (wid >= (long long)n_tiles * W) return;
-  const int wd = (int)(wid / n_tiles), t = (int)(wid % n_tiles);
+  const int wd = (int)(wid % W), t = (int)(wid / W);
+  const int r = t / kRangeTiles, t0 = bk_range_first(r);
+  const int C = bk_cols(W);
   const long long cfg = (long long)t * 64 + lane;
   const uint32_t x = cfg < n ? surv[(long long)wd * cap + cfg] : 0u;
-  uint32_t o = x;
-#pragma unroll
-  for (int sh = 1; sh < 64; sh <<= 1) o |= (uint32_t)__shfl_xor((int)o, sh);
-  o = __builtin_amdgcn_readfirstlane(o);
-  if (o == 0u) return;
-  uint32_t base = 0u;
-  if (lane < 32u && ((o >> lane) & 1u)) {
+  uint32_t c = 0u, base = 0u;
+  if (lane < 32u) {
     const int p = wd * 32 + (int)lane;
-    base = seg_start[p] + off[(long long)p * n_tiles + t];
+    const uint8_t* c8 = reinterpret_cast<const uint8_t*>(cnt) + p;  // column p of the count rows
+    c = c8[(long long)t * C];
+    uint32_t pre = 0u;
+#pragma unroll
+    for (int k = 0; k < kRangeTiles - 1; ++k) pre += t0 + k < t ? c8[(long long)(t0 + k) * C] : 0u;
+    if (p < n_pairs) base = seg_start[p] + grp[(long long)bk_group_of(r) * C + p] + part[(long long)r * C + p] + pre;
   }
-  for (uint32_t m = o; m; m &= m - 1u) {
+  for (uint32_t m = (uint32_t)__ballot(c != 0u); m; m &= m - 1u) {  // lanes >= 32 hold no count
     const int b = __builtin_ctz(m);
     const uint32_t bit = (x >> b) & 1u;
     const unsigned long long bal = __ballot(bit);

@@ -73,9 +73,10 @@ int get_workspace(mpg_world* w, hipStream_t s, long long want, mpg_world::Worksp
   if (ws.cap < want) {
     ws = mpg_world::Workspace{};  // no wait of its own: freeing device memory waits for the queued work that reads it
     ws.last = w->ws_tick;
-    const long long tiles = (want + 63) / 64;
     HIP_TRY(ws.surv.reserve((size_t)w->dw.W * want));
-    HIP_TRY(ws.cnt.reserve((size_t)np * tiles));
+    HIP_TRY(ws.cnt.reserve(bk_cnt_words(w->dw.W, want)));
+    HIP_TRY(ws.part.reserve(bk_part_words(w->dw.W, want)));
+    HIP_TRY(ws.grp.reserve(bk_grp_words(w->dw.W, want)));
     HIP_TRY(ws.seg_len.reserve(np));
     HIP_TRY(ws.seg_start.reserve(np));
     HIP_TRY(ws.prefix.reserve(np + 4));
@@ -136,7 +137,8 @@ int launch_collide(mpg_world* w, const double* in, long long n, uint8_t* flags, 
   int rc = get_workspace(w, stream, chunk, &owner);
   if (rc) return rc;
   // the workspace as the kernels take it
-  uint32_t *const surv = owner->surv.get(), *const cnt = owner->cnt.get(), *const seg_len = owner->seg_len.get(),
+  uint32_t *const surv = owner->surv.get(), *const cnt = owner->cnt.get(), *const part = owner->part.get(),
+                  *const grp = owner->grp.get(), *const seg_len = owner->seg_len.get(),
                   *const seg_start = owner->seg_start.get(), *const prefix = owner->prefix.get(),
                   *const cand = owner->cand.get();
   float* const rq = owner->rq.get();
@@ -152,7 +154,13 @@ int launch_collide(mpg_world* w, const double* in, long long n, uint8_t* flags, 
     const int n_tiles = (int)((m + 63) / 64);
     StageTimer t_cull(w, stream, MPG_STAGE_CULL);
     if (w->prof) w->prof_cfg += m;
-    HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(uint32_t) * std::max(w->dw.n_pairs, 1) * (size_t)n_tiles, stream));
+    // the cull's histogram path writes every count row whole; the ballot
+    // path (more mask words than the histogram holds) writes single bytes
+    // and the ablation modes of diagnostic builds leave before the rows
+#ifndef MPG_DIAG
+    if (w->dw.W * 8 > kQueue)
+#endif
+      HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(uint32_t) * bk_cnt_words(w->dw.W, m), stream));
     switch (w->block) {
       case 256:
         hipLaunchKernelGGL((cull_kernel<256, FROM_POSES>), dim3(grid), dim3(256), w->lds_bytes, stream, w->dw, qin,
@@ -170,17 +178,21 @@ int launch_collide(mpg_world* w, const double* in, long long n, uint8_t* flags, 
     HIP_TRY(hipGetLastError());
     t_cull.stop();
     StageTimer t_bucket(w, stream, MPG_STAGE_BUCKET);
+    const int n_ranges = bk_ranges(n_tiles), n_groups = bk_groups(n_ranges);
     const long long tw = (long long)n_tiles * w->dw.W;  // one wave per (word, tile)
     const unsigned gb = (unsigned)((tw + 3) / 4);
-    if (w->dw.n_pairs > 0) {
-      hipLaunchKernelGGL(pair_scan_kernel, dim3(w->dw.n_pairs), dim3(1024), 0, stream, cnt, n_tiles, seg_len);
+    // small launches: the scan's block sums the ranges itself (one launch fewer)
+    const bool fold = bk_fold_sum(n_ranges, w->dw.W);
+    if (!fold) {
+      hipLaunchKernelGGL(range_sum_kernel, dim3(n_groups), dim3(256), 0, stream, cnt, n_tiles, w->dw.W, part, grp);
       HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(chunk_scan_kernel, dim3(1), dim3(256), 0, stream, seg_len, w->dw.n_pairs, seg_start,
-                       prefix, w->prof ? w->prof_units.get() : nullptr, (uint32_t)(4 * w->narrow_blocks));
+    hipLaunchKernelGGL(range_scan_kernel, dim3(1), dim3(1024), 0, stream, fold ? cnt : nullptr, n_tiles, w->dw.W,
+                       part, grp, n_groups, w->dw.n_pairs, seg_len, seg_start, prefix,
+                       w->prof ? w->prof_units.get() : nullptr, (uint32_t)(4 * w->narrow_blocks));
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(scatter_kernel, dim3(gb), dim3(256), 0, stream, surv, m, cap, w->dw.n_pairs, w->dw.W,
-                       n_tiles, cnt, seg_start, cand);
+                       n_tiles, cnt, part, grp, seg_start, cand);
     HIP_TRY(hipGetLastError());
     t_bucket.stop();
     StageTimer t_narrow(w, stream, MPG_STAGE_NARROW);

@@ -42,10 +42,12 @@ struct mpg_world {
   // phase A/B workspace, one per stream so concurrent streams never share it
   struct Workspace {
     DevBuf<uint32_t> surv;       // [W * cap] survivor bits, word-major
-    DevBuf<uint32_t> cnt;        // [n_pairs * n_tiles] tile counts -> offsets
+    DevBuf<uint32_t> cnt;        // [n_tiles][W * 8] byte counts per (tile, pair), a row per tile (mpg_bucket.h)
+    DevBuf<uint32_t> part;       // [n_ranges][W * 32] candidates per (range, pair), prefixed inside the group
+    DevBuf<uint32_t> grp;        // [n_groups][W * 32] group totals -> each group's base inside its pair
     DevBuf<uint32_t> seg_len;    // [n_pairs]
     DevBuf<uint32_t> seg_start;  // [n_pairs]
-    DevBuf<uint32_t> prefix;     // [n_pairs + 2] task prefix + task counter
+    DevBuf<uint32_t> prefix;     // [n_pairs + 4] task prefix, task count, task counter, ts, candidates
     DevBuf<uint32_t> cand;       // [n_pairs * cap] worst case
     DevBuf<float> rq;            // [n_moving * 4 * cap] phase-A rotations (quaternions) for the SAT stage
     DevBuf<double> sc;           // [cap * dof * 2] exact joint (sin, cos) for phase B
