@@ -607,6 +607,80 @@ int mpg_sample_uniform(const double *lower, const double *upper, int32_t dof, in
                        int64_t row_offset, double *q, int device);
 
 /*
+ * Planner.IK's loop (mplib/planner.py:256-350) as one device call: for every
+ * goal pose of one user link, rows_per_goal seeds run the closed-loop IK
+ * (PinocchioModelTpl::computeIKCLIK, src/pinocchio_model.cpp:376-433,
+ * pinocchio's computeIKCLIK with a mask), the answers are wrapped into the
+ * joint limits (check_joint_limit, planner.py:170-191), checked by the world's
+ * collide() (planner.py:301-303) and compared with the goal by distance_6D
+ * (planner.py:165-168, 306-313).  Nothing leaves the device between the steps.
+ *
+ * Row (goal g, seed r) is stored at g * rows_per_goal + r.
+ *  1. CLIK, fp64: err = log6(joint_pose^-1 * oMi[jid]), joint_pose = goal *
+ *     link_placement^-1, jid the link's parent joint.  ||err|| < eps ends the
+ *     row with MPG_IK_CONVERGED, max_iter iterations end it without.  Else
+ *     v = -J^T (J J^T + damp I)^-1 err dt with J the joint-frame (LOCAL)
+ *     Jacobian over the supporting joints, and q = integrate(q, v); continuous
+ *     joints keep pinocchio's (cos, sin) pair and first-order renormalisation,
+ *     their answer is atan2.  Joints that move: the chain's joints with a dof
+ *     slot whose mask byte is 0; every other joint is a constant.  A
+ *     non-positive Cholesky pivot (the host version throws there) ends the row
+ *     with MPG_IK_SINGULAR, without MPG_IK_CONVERGED, at the joint values from
+ *     before that step.  iters: steps taken; err: the last log6 error.
+ *  2. limits, every dof slot: revolute and continuous joints keep q when
+ *     |q - lo| < 1e-3, else q -= 2 pi floor((q - lo) / (2 pi)), and fail when
+ *     q > hi + 1e-3; prismatic joints fail when q < lo - 1e-3 or q > hi + 1e-3;
+ *     a joint without finite limits never fails and is not wrapped.  q_out
+ *     holds the wrapped values; MPG_IK_IN_LIMITS: no slot fails.
+ *  3. MPG_IK_COLLISION_FREE: mpg_collide_batch's flag of q_out is 0 (the same
+ *     device pipeline on the device-resident rows; movable objects at their
+ *     current poses).  MPG_IK_WITHIN_THRESHOLD: |dp| + min(|q1 - q2|,
+ *     |q1 + q2|) < threshold between the goal and the link pose mpg_fk_batch
+ *     gives at q_out.
+ * A row is a usable solution when status & MPG_IK_VALID == MPG_IK_VALID.
+ *
+ * Seeds: q_init [n_goals * rows_per_goal * dof], or NULL: seed 0 of each goal
+ * is q_start, seed r > 0 is row g * rows_per_goal + r of mpg_sample_uniform
+ * (seed opt->seed) over the joint limits, [-pi, pi] for continuous joints,
+ * masked slots overwritten with q_start.  A move-group joint with neither
+ * finite limits nor a continuous type is then MPG_E_INVALID.
+ *
+ * mem: MPG_MEM_HOST buffers are staged and the call synchronises (poses and
+ * joint values checked: finite, quaternion norm within 1e-6);
+ * MPG_MEM_DEVICE: goal_pose, q_init, q_start and the outputs are device
+ * memory, everything is enqueued on `stream`, nothing synchronises.  opt and
+ * its mask are host memory, read during the call.  MPG_E_INVALID: a free-frame
+ * link, a link index out of range, q_init and q_start both NULL, max_iter
+ * outside [0, 100000]; MPG_E_UNSUPPORTED: dof > 32 or more than 15 joints
+ * above the link.  Every loop of the kernel is bounded by max_iter and the row
+ * count, so the call ends for any input (a NaN error never converges).
+ */
+#define MPG_IK_CONVERGED 1
+#define MPG_IK_IN_LIMITS 2
+#define MPG_IK_COLLISION_FREE 4
+#define MPG_IK_WITHIN_THRESHOLD 8
+#define MPG_IK_SINGULAR 16
+#define MPG_IK_VALID 15
+
+typedef struct mpg_ik_options {
+  double eps;           /* 1e-5 */
+  int32_t max_iter;     /* 1000; 0 .. 100000, else MPG_E_INVALID */
+  double dt;            /* 0.1 */
+  double damp;          /* 1e-12 */
+  double threshold;     /* 1e-3 */
+  const uint8_t *mask;  /* [dof], host memory, 1 = frozen; NULL = none */
+  uint64_t seed;
+  int32_t max_waves;    /* 0 = as many as are resident; a tuning and test knob */
+} mpg_ik_options;
+
+int mpg_ik_batch(mpg_world *world, int32_t link, const double *goal_pose /* [n_goals*7] (p, wxyz) */,
+                 int64_t n_goals, int64_t rows_per_goal,
+                 const double *q_init /* [n_goals*rows_per_goal*dof] or NULL */,
+                 const double *q_start /* [dof] or NULL */, const mpg_ik_options *opt /* NULL = defaults */,
+                 double *q_out, uint8_t *status, double *err /* [rows*6] or NULL */,
+                 int32_t *iters /* [rows] or NULL */, int mem, void *stream);
+
+/*
  * Diagnostics (host only, no device): the FCL 0.7.0 BVHModel<OBBRSS> tree the
  * snapshot builds for a BVH mesh (BVHModel::endModel -> buildTree:
  * BVFitter<OBBRSS>::fit, SPLIT_METHOD_MEAN; OBB half), whose OBB tests gate

@@ -61,6 +61,21 @@ class DistanceRequest(ctypes.Structure):
     _fields_ = [("flags", ctypes.c_int32), ("distance_tolerance", ctypes.c_double)]
 
 
+class IkOptions(ctypes.Structure):
+    """mpg_ik_options (include/mpgpu.h); the defaults are the reference's."""
+    _fields_ = [("eps", ctypes.c_double), ("max_iter", ctypes.c_int32), ("dt", ctypes.c_double),
+                ("damp", ctypes.c_double), ("threshold", ctypes.c_double), ("mask", ctypes.c_void_p),
+                ("seed", ctypes.c_uint64), ("max_waves", ctypes.c_int32)]
+
+
+MPG_IK_CONVERGED = 1
+MPG_IK_IN_LIMITS = 2
+MPG_IK_COLLISION_FREE = 4
+MPG_IK_WITHIN_THRESHOLD = 8
+MPG_IK_SINGULAR = 16
+MPG_IK_VALID = 15
+
+
 class WorldInfo(ctypes.Structure):
     _fields_ = [("n_pairs", ctypes.c_int32), ("mask_words", ctypes.c_int32), ("dof", ctypes.c_int32),
                 ("n_links", ctypes.c_int32), ("device", ctypes.c_int32), ("block_size", ctypes.c_int32),
@@ -128,6 +143,9 @@ SIGNATURES = {
                                                  ctypes.c_void_p]),
     "mpg_fk_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                     ctypes.c_int, ctypes.c_void_p]),
+    "mpg_ik_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(IkOptions), ctypes.c_void_p,
+                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "mpg_profile_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "mpg_profile_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
                                         ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_int]),

@@ -226,6 +226,61 @@ class DeviceWorld:
                                      out.ctypes.data_as(ctypes.c_void_p), C.MPG_MEM_HOST, None), "mpg_fk_batch")
         return out
 
+    def ik_batch(self, link: int, goal_poses, *, start_qpos=None, q_init=None, n_init_qpos: int = 20, mask=None,
+                 seed: int = 0, eps: float = 1e-5, max_iter: int = 1000, dt: float = 0.1, damp: float = 1e-12,
+                 threshold: float = 1e-3, max_waves: int = 0, out=None, stream: Optional[int] = None):
+        """Planner.IK's loop for every goal pose of world link ``link`` in one
+        call (mpg_ik_batch): per (goal, seed) row the closed-loop IK, the
+        joint-limit wrap, ``collide()`` and the distance_6D threshold.
+        Host path (numpy ``goal_poses`` (7,) / [M, 7]; ``q_init`` [M, S, dof]
+        or None: ``n_init_qpos`` seeds per goal drawn on the device, seed 0 =
+        ``start_qpos``): returns (q [M, S, dof], status [M, S] u8 of
+        ``_capi.MPG_IK_*`` bits, err [M, S, 6], iters [M, S] i32).
+        Device path (tensors with data_ptr(); ``q_init`` [M, S, dof] or None
+        with ``n_init_qpos``): ``out`` = (q, status, err or None, iters or
+        None) preallocated tensors, filled on ``stream`` without
+        synchronising and returned.  ``mask`` is always a host array."""
+        o = C.IkOptions(eps, int(max_iter), dt, damp, threshold, None, int(seed), int(max_waves))
+        mk = None
+        if mask is not None:
+            mk = np.ascontiguousarray(np.asarray(mask, dtype=bool).reshape(-1)).astype(np.uint8)
+            if mk.size != self.dof:
+                raise ValueError(f"mask must hold {self.dof} values")
+            o.mask = mk.ctypes.data
+        P = ctypes.c_void_p
+        if hasattr(goal_poses, "data_ptr"):
+            M = goal_poses.numel() // 7
+            S = int(n_init_qpos) if q_init is None else (q_init.numel() // max(self.dof, 1)) // max(M, 1)
+            if out is None:
+                raise ValueError("device path needs out=(q, status, err, iters) preallocated")
+            q, status, err, iters = out
+            ptr = lambda t: P(t.data_ptr() if t is not None else 0)  # noqa: E731
+            C.check(C.lib().mpg_ik_batch(self._h, int(link), ptr(goal_poses), M, S, ptr(q_init), ptr(start_qpos),
+                                         ctypes.byref(o), ptr(q), ptr(status), ptr(err), ptr(iters), C.MPG_MEM_DEVICE,
+                                         P(stream or 0)), "mpg_ik_batch")
+            return out
+        g = np.ascontiguousarray(np.asarray(goal_poses, dtype=np.float64)).reshape(-1, 7)
+        M = g.shape[0]
+        qi = qs = None
+        S = int(n_init_qpos)
+        if q_init is not None:
+            qi = np.ascontiguousarray(np.asarray(q_init, dtype=np.float64))
+            if M == 0 or qi.size % (M * max(self.dof, 1)):
+                raise ValueError(f"q_init must be [{M}, S, {self.dof}]")
+            S = qi.size // (M * max(self.dof, 1))
+        if start_qpos is not None:
+            qs = np.ascontiguousarray(np.asarray(start_qpos, dtype=np.float64).reshape(-1))
+            if qs.size != self.dof:
+                raise ValueError(f"start_qpos must hold {self.dof} values")
+        q = np.zeros((M, S, self.dof))
+        status = np.zeros((M, S), np.uint8)
+        err = np.zeros((M, S, 6))
+        iters = np.zeros((M, S), np.int32)
+        hp = lambda a: P(a.ctypes.data if a is not None else 0)  # noqa: E731
+        C.check(C.lib().mpg_ik_batch(self._h, int(link), hp(g), M, S, hp(qi), hp(qs), ctypes.byref(o), hp(q),
+                                     hp(status), hp(err), hp(iters), C.MPG_MEM_HOST, P(stream or 0)), "mpg_ik_batch")
+        return q, status, err, iters
+
 
 def device_sincos(x, device: int = 0):
     xa = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))

@@ -802,6 +802,12 @@ class PlanningWorld {
                              const void* poses = nullptr, int64_t pose_rows = 0);
   int mask_words();
   mpg_world* device_world();  // rebuilds the snapshot if the world changed
+  // Planner.IK's loop batched (mpg_ik_batch): the world link index of a planned
+  // articulation's user link, and the call itself (mem: MPG_MEM_*)
+  int ik_link_index(const std::string& link_name);
+  void ik_batch(int link, const double* goal_pose, int64_t n_goals, int64_t rows_per_goal, const double* q_init,
+                const double* q_start, const mpg_ik_options& opt, double* q_out, uint8_t* status, double* err,
+                int32_t* iters, int mem, void* stream);
   // batched OMPL motion validation over the planner's state space
   // (src/ompl_planner.cpp:248-293): SO2 dofs and the space's maximum extent
   struct MotionSpace {
@@ -853,6 +859,7 @@ class PlanningWorld {
   uint64_t world_key_ = ~0ull;
   std::vector<PairInfo> pairs_;
   int state_dim_ = 0;
+  std::vector<std::pair<ArtPtr, int>> planned_link_base_;  // first world link index of each planned articulation
   // the same snapshot with every joint of the planned articulations a state
   // value (sample_pair_counts)
   std::vector<int32_t> full_src_;

@@ -1156,6 +1156,101 @@ PYBIND11_MODULE(pymp, m_all) {
            "Enqueue the batched check on device buffers (float64 [n, dim], uint8 [n], uint32 [n, W]).  "
            "object_poses_ptr: float64 [object_pose_rows, M, 7] device array of the movable objects' poses in "
            "get_movable_object_names() order, object_pose_rows = n or 1 (0: their current poses).")
+      .def("ik_batch",
+           [](PW& w, py::object link, py::array_t<double, py::array::c_style | py::array::forcecast> goal_poses,
+              std::optional<py::array_t<double, py::array::c_style | py::array::forcecast>> start_qpos,
+              std::optional<py::array_t<double, py::array::c_style | py::array::forcecast>> q_init, int64_t n_init_qpos,
+              std::optional<py::array_t<bool, py::array::c_style | py::array::forcecast>> mask, uint64_t seed,
+              double eps, int max_iter, double dt, double damp, double threshold, int max_waves) {
+             const int dim = w.state_dim();
+             const int li = py::isinstance<py::str>(link) ? w.ik_link_index(link.cast<std::string>()) : link.cast<int>();
+             if (!((goal_poses.ndim() == 1 && goal_poses.shape(0) == 7) ||
+                   (goal_poses.ndim() == 2 && goal_poses.shape(1) == 7)))
+               throw std::invalid_argument("goal_poses must be (7,) or [M, 7] float64 (p, wxyz)");
+             const int64_t M = goal_poses.ndim() == 1 ? 1 : goal_poses.shape(0);
+             int64_t S = n_init_qpos;
+             if (q_init) {
+               const auto& qi = *q_init;
+               if (qi.ndim() == 3 && qi.shape(0) == M && qi.shape(2) == dim) S = qi.shape(1);
+               else if (qi.ndim() == 2 && qi.shape(1) == dim && M > 0 && qi.shape(0) % M == 0) S = qi.shape(0) / M;
+               else throw std::invalid_argument("q_init must be [M, S, " + std::to_string(dim) + "] float64");
+             }
+             if (S < 0) throw std::invalid_argument("n_init_qpos must be >= 0");
+             if (start_qpos && (start_qpos->ndim() != 1 || start_qpos->shape(0) != dim))
+               throw std::invalid_argument("start_qpos must hold the state's " + std::to_string(dim) + " values");
+             if (mask && (mask->ndim() != 1 || mask->shape(0) != dim))
+               throw std::invalid_argument("mask must hold the state's " + std::to_string(dim) + " values");
+             std::vector<uint8_t> mk;
+             if (mask) mk.assign(mask->data(), mask->data() + dim);
+             mpg_ik_options o{eps, max_iter, dt, damp, threshold, mask ? mk.data() : nullptr, seed, max_waves};
+             py::array_t<double> q({(ssize_t)M, (ssize_t)S, (ssize_t)dim}), err({(ssize_t)M, (ssize_t)S, (ssize_t)6});
+             py::array_t<uint8_t> status({(ssize_t)M, (ssize_t)S});
+             py::array_t<int32_t> iters({(ssize_t)M, (ssize_t)S});
+             const double* gp = goal_poses.data();
+             const double* qi = q_init ? q_init->data() : nullptr;
+             const double* qs = start_qpos ? start_qpos->data() : nullptr;
+             double *qo = q.mutable_data(), *eo = err.mutable_data();
+             uint8_t* so = status.mutable_data();
+             int32_t* io = iters.mutable_data();
+             {
+               py::gil_scoped_release rel;
+               w.ik_batch(li, gp, M, S, qi, qs, o, qo, so, eo, io, MPG_MEM_HOST, nullptr);
+             }
+             return py::make_tuple(q, status, err, iters);
+           },
+           py::arg("link"), py::arg("goal_poses"), py::kw_only(), py::arg("start_qpos") = py::none(),
+           py::arg("q_init") = py::none(), py::arg("n_init_qpos") = 20, py::arg("mask") = py::none(),
+           py::arg("seed") = 0, py::arg("eps") = 1e-5, py::arg("max_iter") = 1000, py::arg("dt") = 0.1,
+           py::arg("damp") = 1e-12, py::arg("threshold") = 1e-3, py::arg("max_waves") = 0,
+           "Planner.IK's loop for M goal poses of one link in one device call (include/mpgpu.h mpg_ik_batch): per "
+           "(goal, seed) row the closed-loop IK, the joint-limit wrap, collide() and the distance_6D threshold.  "
+           "link: a planned articulation's user link name, or a world link index.  Seeds: q_init [M, S, dim], or "
+           "n_init_qpos per goal drawn on the device (seed 0 = start_qpos).  mask: True freezes a state value.  "
+           "Returns (q [M, S, dim], status [M, S] uint8 of MPG_IK_* bits, err [M, S, 6], iters [M, S]); a row is a "
+           "solution when status & 15 == 15.")
+      .def("ik_batch_device",
+           [](PW& w, int link, uintptr_t goal_poses, int64_t n_goals, int64_t rows_per_goal, uintptr_t q_init,
+              uintptr_t q_start, uintptr_t q_out, uintptr_t status, uintptr_t err, uintptr_t iters, uintptr_t stream,
+              std::optional<py::array_t<bool, py::array::c_style | py::array::forcecast>> mask, uint64_t seed,
+              double eps, int max_iter, double dt, double damp, double threshold, int max_waves) {
+             const int dim = w.state_dim();
+             if (mask && (mask->ndim() != 1 || mask->shape(0) != dim))
+               throw std::invalid_argument("mask must hold the state's " + std::to_string(dim) + " values");
+             std::vector<uint8_t> mk;
+             if (mask) mk.assign(mask->data(), mask->data() + dim);
+             mpg_ik_options o{eps, max_iter, dt, damp, threshold, mask ? mk.data() : nullptr, seed, max_waves};
+             w.ik_batch(link, reinterpret_cast<const double*>(goal_poses), n_goals, rows_per_goal,
+                        reinterpret_cast<const double*>(q_init), reinterpret_cast<const double*>(q_start), o,
+                        reinterpret_cast<double*>(q_out), reinterpret_cast<uint8_t*>(status),
+                        reinterpret_cast<double*>(err), reinterpret_cast<int32_t*>(iters), MPG_MEM_DEVICE,
+                        reinterpret_cast<void*>(stream));
+           },
+           py::arg("link"), py::arg("goal_poses_ptr"), py::arg("n_goals"), py::arg("rows_per_goal"),
+           py::arg("q_init_ptr"), py::arg("q_start_ptr"), py::arg("q_out_ptr"), py::arg("status_ptr"),
+           py::arg("err_ptr") = 0, py::arg("iters_ptr") = 0, py::arg("stream") = 0, py::arg("mask") = py::none(),
+           py::arg("seed") = 0, py::arg("eps") = 1e-5, py::arg("max_iter") = 1000, py::arg("dt") = 0.1,
+           py::arg("damp") = 1e-12, py::arg("threshold") = 1e-3, py::arg("max_waves") = 0,
+           "Enqueue ik_batch on device buffers (float64 goal poses [n_goals, 7], q_init [rows, dim] or 0, q_start "
+           "[dim] or 0 -> float64 q [rows, dim], uint8 status [rows], optional float64 err [rows, 6], int32 iters "
+           "[rows]; rows = n_goals * rows_per_goal).  link: a world link index (ik_link_index).  No synchronisation.")
+      .def("fk_link_pose",
+           [](PW& w, py::array_t<double, py::array::c_style | py::array::forcecast> state, int link) {
+             const int dim = w.state_dim();
+             if (state.ndim() != 1 || state.shape(0) != dim)
+               throw std::invalid_argument("state must hold " + std::to_string(dim) + " values");
+             mpg_world_info info{};
+             check_status(mpg_world_get_info(w.device_world(), &info), "mpg_world_get_info");
+             if (link < 0 || link >= info.n_links) throw std::invalid_argument("link index out of range");
+             std::vector<double> poses((size_t)info.n_links * 7);
+             check_status(mpg_fk_batch(w.device_world(), state.data(), 1, poses.data(), MPG_MEM_HOST, nullptr),
+                          "mpg_fk_batch");
+             return vec(poses.data() + 7 * link, 7);
+           },
+           py::arg("state"), py::arg("link"),
+           "getLinkPose (p, wxyz) of world link `link` at one state (mpg_fk_batch), the pose ik_batch's "
+           "threshold bit compares with the goal.")
+      .def("ik_link_index", &PW::ik_link_index, py::arg("link_name"),
+           "The world link index of a planned articulation's user link, as ik_batch_device takes it.")
       .def("distance_batch_device",
            [](PW& w, uintptr_t q, int64_t n, uintptr_t d_self, uintptr_t p_self, uintptr_t d_others,
               uintptr_t p_others, uintptr_t pts_self, uintptr_t pts_others, uintptr_t stream,

@@ -493,6 +493,7 @@ void PlanningWorld::ensure_snapshot(const CollisionRequest& r, bool need_device)
   d.gjk_tolerance = r.gjk_tolerance;
   d.gjk_solver = r.gjk_solver_type == GST_INDEP ? MPG_GJK_INDEP : MPG_GJK_LIBCCD;
   pairs_.clear();
+  planned_link_base_.clear();
   full_src_.clear();
   full_lo_.clear();
   full_hi_.clear();
@@ -539,6 +540,7 @@ void PlanningWorld::ensure_snapshot(const CollisionRequest& r, bool need_device)
       full_dof_ += pin->nv();
     }
     const int link_base = (int)d.link_parent.size();
+    if (planned) planned_link_base_.push_back({a, link_base});
     pin->fill_kinematics(d, joint_offset, src, cst);
     if (planned) dof += (int)slots.size();
     auto fcl = a->get_fcl_model();
@@ -742,6 +744,23 @@ int PlanningWorld::mask_words() {
 mpg_world* PlanningWorld::device_world() {
   ensure_snapshot(CollisionRequest());
   return world_->get();
+}
+int PlanningWorld::ik_link_index(const std::string& link_name) {
+  ensure_snapshot(CollisionRequest(), false);
+  for (auto& pb : planned_link_base_) {
+    const auto& names = pb.first->get_user_link_names();
+    const auto it = std::find(names.begin(), names.end(), link_name);
+    if (it != names.end()) return pb.second + (int)(it - names.begin());
+  }
+  throw std::invalid_argument("no planned articulation has a user link named " + link_name);
+}
+void PlanningWorld::ik_batch(int link, const double* goal_pose, int64_t n_goals, int64_t rows_per_goal,
+                             const double* q_init, const double* q_start, const mpg_ik_options& opt, double* q_out,
+                             uint8_t* status, double* err, int32_t* iters, int mem, void* stream) {
+  ensure_snapshot(CollisionRequest());
+  check_status(mpg_ik_batch(world_->get(), link, goal_pose, n_goals, rows_per_goal, q_init, q_start, &opt, q_out, status,
+                            err, iters, mem, stream),
+               "mpg_ik_batch");
 }
 void PlanningWorld::collide_batch(const double* q, int64_t n, uint8_t* flags, uint32_t* masks) {
   ensure_snapshot(CollisionRequest());

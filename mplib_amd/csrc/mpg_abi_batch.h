@@ -579,6 +579,138 @@ int mpg_fk_batch(mpg_world* w, const double* q, int64_t n, double* link_pose, in
   return MPG_OK;
 }
 
+// device buffers: seeds (q_init NULL), CLIK, limits + threshold, the collide
+// pass of the MPG_MEM_DEVICE callers on q_out, its flags folded into status
+static int launch_ik(mpg_world* w, const IkView& iv, const double* goal, long long n_goals, long long rpg,
+                     const double* q_init, const double* q_start, uint64_t seed, int max_waves, double* q_out,
+                     uint8_t* status, double* err, int32_t* iters, hipStream_t s) {
+  const long long rows = n_goals * rpg;
+  const int dof = w->dw.dof;
+  StreamPin pin(w, s);
+  mpg_world::IkWork* K = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(w->ws_mu);
+    K = &w->ik_ws[s];
+  }
+  if (K->flags.get() && K->flags.cap() < (size_t)rows) HIP_TRY(hipStreamSynchronize(s));  // queued work may still read it
+  HIP_TRY(K->flags.reserve((size_t)rows));
+  HIP_TRY(K->counter.reserve(1));
+  HIP_TRY(hipMemsetAsync(K->counter.get(), 0, sizeof(unsigned long long), s));
+  const double* q_in = q_init;
+  if (!q_init) {
+    const long long tot = rows * dof;
+    hipLaunchKernelGGL(ik_seed_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, iv, dof, rows, rpg, seed,
+                       q_start, q_out);
+    HIP_TRY(hipGetLastError());
+    q_in = q_out;
+  }
+  // one wave per block; the grid: the waves the LDS lets be resident, fewer for small batches
+  const size_t cl = (size_t)std::max(iv.cl, 1);
+  const size_t lds = sizeof(double) * (kIkSlot * 64 + IKT_DOUBLES) * cl + sizeof(int) * IKT_INTS * cl;
+  const long long resident = (long long)w->ik.cus * std::max<long long>(1, std::min<long long>(8, (160 * 1024) / lds));
+  long long waves = std::min<long long>((rows + 63) / 64, resident);
+  if (max_waves > 0) waves = std::min<long long>(waves, max_waves);
+  hipLaunchKernelGGL(ik_clik_kernel, dim3((unsigned)waves), dim3(64), lds, s, w->dw, iv, goal, rows, rpg, q_in, q_out,
+                     status, err, iters, K->counter.get());
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(ik_finish_kernel, dim3((unsigned)((rows + 127) / 128)), dim3(128), 0, s, w->dw, iv, goal, rows,
+                     rpg, q_out, status);
+  HIP_TRY(hipGetLastError());
+  const int rc = mpg_collide_batch(w, q_out, rows, K->flags.get(), nullptr, MPG_MEM_DEVICE, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ik_fold_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, K->flags.get(), rows,
+                     status);
+  HIP_TRY(hipGetLastError());
+  return MPG_OK;
+}
+
+int mpg_ik_batch(mpg_world* w, int32_t link, const double* goal_pose, int64_t n_goals, int64_t rows_per_goal,
+                 const double* q_init, const double* q_start, const mpg_ik_options* opt, double* q_out,
+                 uint8_t* status, double* err, int32_t* iters, int mem, void* stream) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  if (n_goals < 0 || rows_per_goal < 0) return set_error(MPG_E_INVALID, "n_goals / rows_per_goal < 0");
+  if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
+  const auto& T = w->ik;
+  if (link < 0 || link >= w->dw.n_links) return set_error(MPG_E_INVALID, "link index out of range");
+  if (link >= w->dw.n_links - w->dw.n_free) return set_error(MPG_E_INVALID, "link is a free frame: no joint moves it");
+  if (!q_init && !q_start) return set_error(MPG_E_INVALID, "q_init and q_start are both NULL");
+  mpg_ik_options o{1e-5, 1000, 0.1, 1e-12, 1e-3, nullptr, 0, 0};
+  if (opt) o = *opt;
+  if (o.max_iter < 0 || o.max_iter > 100000) return set_error(MPG_E_INVALID, "max_iter outside [0, 100000]");
+  if (o.max_waves < 0) return set_error(MPG_E_INVALID, "max_waves < 0");
+  const int dof = w->dw.dof;
+  if (dof > kIkDof) return set_error(MPG_E_UNSUPPORTED, "mpg_ik_batch supports dof <= 32");
+  if (T.chain_len[link] > kIkChain) return set_error(MPG_E_UNSUPPORTED, "mpg_ik_batch supports at most 15 joints above the link");
+  if (n_goals > (int64_t)1 << 40 || rows_per_goal > (int64_t)1 << 20 || n_goals * rows_per_goal > (int64_t)1 << 40)
+    return set_error(MPG_E_UNSUPPORTED, "mpg_ik_batch supports at most 2^40 rows");
+  IkView iv{};
+  iv.link = link;
+  iv.cs = T.chain_start[link];
+  iv.cl = T.chain_len[link];
+  iv.max_iter = o.max_iter;
+  iv.eps = o.eps;
+  iv.dt = o.dt;
+  iv.damp = o.damp;
+  iv.threshold = o.threshold;
+  constexpr double kPi = 3.14159265358979323846;
+  for (int d = 0; d < dof; ++d) {
+    iv.kind[d] = T.kind[d];
+    iv.bounded[d] = std::isfinite(T.lo[d]) && std::isfinite(T.hi[d]);
+    iv.frozen[d] = o.mask && o.mask[d] ? 1 : 0;
+    iv.lo[d] = T.continuous[d] ? -kPi : T.lo[d];
+    iv.hi[d] = T.continuous[d] ? kPi : T.hi[d];
+    if (!q_init && !iv.frozen[d] && !T.continuous[d] && !iv.bounded[d])
+      return set_error(MPG_E_INVALID, "dof slot " + std::to_string(d) +
+                                          ": a joint with neither finite limits nor a continuous type cannot be sampled");
+  }
+  for (int k = 0; k < iv.cl; ++k) {
+    const int src = T.joint_q_source[T.chain_joints[iv.cs + k] - 1];
+    iv.move[k] = src >= 0 && !iv.frozen[src];
+  }
+  const int64_t rows = n_goals * rows_per_goal;
+  if (rows > 0 && (!goal_pose || !q_out || !status)) return set_error(MPG_E_INVALID, "goal_pose / q_out / status is NULL");
+  if (mem == MPG_MEM_HOST && rows > 0) {
+    for (int64_t g = 0; g < n_goals; ++g) {
+      const double* p = goal_pose + 7 * g;
+      if (!finite_all(p, 7)) return set_error(MPG_E_INVALID, "non-finite goal pose");
+      const double nq = std::sqrt(p[3] * p[3] + p[4] * p[4] + p[5] * p[5] + p[6] * p[6]);
+      if (!(std::fabs(nq - 1.0) <= kFreeQuatTol))
+        return set_error(MPG_E_INVALID, "goal pose quaternion is not of unit norm (within 1e-6)");
+    }
+    if (q_init && !finite_all(q_init, (size_t)rows * dof)) return set_error(MPG_E_INVALID, "non-finite q_init");
+    if (q_start && !finite_all(q_start, (size_t)dof)) return set_error(MPG_E_INVALID, "non-finite q_start");
+  }
+  if (rows == 0) return MPG_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (mem == MPG_MEM_DEVICE)
+    return launch_ik(w, iv, goal_pose, n_goals, rows_per_goal, q_init, q_start, o.seed, o.max_waves, q_out, status, err,
+                     iters, s);
+  // host buffers: grow-only device staging kept by the world (one host call at
+  // a time: host_mu; no wait before a buffer is replaced, the call is synchronous)
+  std::lock_guard<std::mutex> lk(w->host_mu);
+  if (!s && w->own_stream) s = w->own_stream.get();
+  auto& S = w->ik_stage;
+  const size_t nq = (size_t)rows * std::max(dof, 1);
+  if (S.goal.reserve(7 * (size_t)n_goals) != hipSuccess || S.q.reserve(nq) != hipSuccess ||
+      S.start.reserve(std::max(dof, 1)) != hipSuccess || S.err.reserve(6 * (size_t)rows) != hipSuccess ||
+      S.status.reserve((size_t)rows) != hipSuccess || S.iters.reserve((size_t)rows) != hipSuccess)
+    return set_error(MPG_E_NOMEM, "IK staging buffers");
+  HIP_TRY(hipMemcpyAsync(S.goal.get(), goal_pose, sizeof(double) * 7 * n_goals, hipMemcpyHostToDevice, s));
+  if (q_init && dof) HIP_TRY(hipMemcpyAsync(S.q.get(), q_init, sizeof(double) * rows * dof, hipMemcpyHostToDevice, s));
+  if (q_start && dof) HIP_TRY(hipMemcpyAsync(S.start.get(), q_start, sizeof(double) * dof, hipMemcpyHostToDevice, s));
+  const int rc = launch_ik(w, iv, S.goal.get(), n_goals, rows_per_goal, q_init ? S.q.get() : nullptr,
+                           q_start ? S.start.get() : nullptr, o.seed, o.max_waves, S.q.get(), S.status.get(),
+                           S.err.get(), S.iters.get(), s);
+  if (rc) return rc;
+  if (dof) HIP_TRY(hipMemcpyAsync(q_out, S.q.get(), sizeof(double) * rows * dof, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(status, S.status.get(), (size_t)rows, hipMemcpyDeviceToHost, s));
+  if (err) HIP_TRY(hipMemcpyAsync(err, S.err.get(), sizeof(double) * 6 * rows, hipMemcpyDeviceToHost, s));
+  if (iters) HIP_TRY(hipMemcpyAsync(iters, S.iters.get(), sizeof(int32_t) * rows, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return MPG_OK;
+}
+
 int mpg_debug_collide_pairs(mpg_world* w, int32_t geom_a, int32_t geom_b, int64_t n, const double* Ta,
                             const double* Tb, uint8_t* hit) {
   if (!w || n < 0 || (n > 0 && (!Ta || !Tb || !hit))) return set_error(MPG_E_INVALID, "bad arguments");

@@ -878,6 +878,31 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, narrow_kernel<false>, 256, 0) != hipSuccess || per_cu <= 0)
     per_cu = 2;
   w->narrow_blocks = cus * per_cu;
+  // mpg_ik_batch's tables: host copies of the chains and, per dof slot, the
+  // kind and limits of the joint behind it
+  {
+    auto& K = w->ik;
+    K.cus = cus;
+    K.chain_start = chain_start;
+    K.chain_len = chain_len;
+    K.chain_joints = chain_joints;
+    K.joint_q_source.assign(d->joint_q_source, d->joint_q_source + d->n_joints);
+    const size_t nd = (size_t)std::max(d->dof, 0);
+    K.lo.assign(nd, -INFINITY);
+    K.hi.assign(nd, INFINITY);
+    K.kind.assign(nd, IKK_NONE);
+    K.continuous.assign(nd, 0);
+    for (int j = 0; j < d->n_joints; ++j) {
+      const int s = d->joint_q_source[j];
+      if (s < 0 || s >= d->dof || K.kind[s] != IKK_NONE) continue;
+      K.kind[s] = joint_is_revolute(d->joint_type[j]) ? IKK_REVOLUTE : IKK_PRISMATIC;
+      K.continuous[s] = d->joint_type[j] >= MPG_JOINT_RUBX;
+      if (d->joint_lower && d->joint_upper) {
+        K.lo[s] = d->joint_lower[j];
+        K.hi[s] = d->joint_upper[j];
+      }
+    }
+  }
   // bound the candidate lists to 1 GiB: cap * n_pairs * 4 B
   w->max_chunk = std::max<long long>(4096, std::min<long long>(1 << 20, (1ll << 28) / std::max(d->n_pairs, 1)));
   if (const char* e = std::getenv("MPG_SMALL_BATCH_MAX")) w->small_max = std::atoll(e);

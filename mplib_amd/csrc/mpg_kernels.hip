@@ -44,6 +44,7 @@
 #include "../../include/mpgpu.h"
 #include "mpg_math.h"
 #include "mpg_fk.h"
+#include "mpg_ik.h"
 #include "mpg_bucket.h"
 #include "mpg_hostpipe.h"
 
@@ -6725,6 +6726,134 @@ __global__ __launch_bounds__(256) void sample_uniform_kernel(SampleRange r, int 
   const int k = (int)(i % dof);
   const double u = splitmix_u01(seed, (uint64_t)(row0 * dof + i));
   out[i] = r.lo[k] + (r.hi[k] - r.lo[k]) * u;
+}
+
+// ---------------------------------------------------------------------------
+// Planner.IK's loop (mplib/planner.py:256-350), batched: mpg_ik_batch.  The
+// per-row arithmetic is mpg_ik.h's.
+// ---------------------------------------------------------------------------
+// the seeds of a call without q_init: seed 0 of each goal and every masked
+// slot from q_start, the rest row g * rows_per_goal + r of the sampler above
+__global__ __launch_bounds__(256) void ik_seed_kernel(IkView iv, int dof, long long n_rows, long long rows_per_goal,
+                                                     uint64_t seed, const double* __restrict__ q_start,
+                                                     double* __restrict__ q) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_rows * dof) return;
+  const int d = (int)(i % dof);
+  const long long r = (i / dof) % rows_per_goal;
+  if (r == 0 || iv.frozen[d]) q[i] = q_start[d];
+  else q[i] = iv.lo[d] + (iv.hi[d] - iv.lo[d]) * splitmix_u01(seed, (uint64_t)i);
+}
+
+// One lane per row, one wave per block, the whole iteration in one launch.
+// Rows need some 60 to 1000 iterations, so a lane that has finished its row
+// writes it and claims the next unclaimed one from *counter (zeroed on the
+// stream before the launch): one atomic per wave and pass for all its claiming
+// lanes (ballot + popcount).  A row's arithmetic is its lane's alone, so its
+// result does not depend on the lane that ran it.  Each pass of the loop gives
+// every lane that holds a row one iteration or its last check, so n_rows *
+// (max_iter + 2) passes bound the loop for any input.
+// A lane asks for a row only when kIkRefill lanes of its wave are idle (or all
+// are): every pass with a claim pays an atomic, the row's loads and the
+// previous row's stores, and with lanes finishing at different passes that
+// was nearly every pass.
+// LDS: the lanes' IkLane state, [chain joint][component][lane], then the
+// chain's joint constants (IkJointsTable), filled once per wave.
+constexpr int kIkRefill = 16;
+__global__ __launch_bounds__(64) void ik_clik_kernel(DevWorld w, IkView iv, const double* __restrict__ goal,
+                                                    long long n_rows, long long rows_per_goal, const double* q_in,
+                                                    double* q_out, uint8_t* __restrict__ status,
+                                                    double* __restrict__ err_out, int32_t* __restrict__ iters_out,
+                                                    unsigned long long* __restrict__ counter) {
+  extern __shared__ double ik_lds[];
+  const int lane = threadIdx.x;
+  const IkLane L{ik_lds + lane, 64};
+  double* const td = ik_lds + (size_t)iv.cl * kIkSlot * 64;
+  int* const ti = reinterpret_cast<int*>(td + (size_t)iv.cl * IKT_DOUBLES);
+  for (int k = lane; k < iv.cl; k += 64) {
+    const int j0 = w.chain_joints[iv.cs + k] - 1;
+    ti[IKT_INTS * k + IKT_TYPE] = w.joint_type[j0];
+    ti[IKT_INTS * k + IKT_SRC] = w.joint_q_source[j0];
+    ti[IKT_INTS * k + IKT_MOVE] = iv.move[k];
+    td[IKT_DOUBLES * k + IKT_QCONST] = w.joint_q_const[j0];
+    for (int c = 0; c < 3; ++c) td[IKT_DOUBLES * k + IKT_AXIS + c] = w.joint_axis[3 * j0 + c];
+    for (int c = 0; c < 12; ++c) td[IKT_DOUBLES * k + IKT_PLACE + c] = w.joint_place[12 * j0 + c];
+  }
+  __syncthreads();
+  const IkJointsTable jt{td, ti};
+  const int dof = w.dof;
+  long long row = -1;
+  int it = 0;
+  bool rows_left = true;
+  SE3 Ginv;
+  se3_identity(Ginv);
+  const long long bound = n_rows * ((long long)iv.max_iter + 2) + 2;
+  for (long long pass = 0; pass < bound; ++pass) {
+    const bool want = row < 0 && rows_left;
+    const unsigned long long wants = __ballot(want);
+    if (wants && (__popcll(wants) >= kIkRefill || !__ballot(row >= 0))) {
+      const int leader = __ffsll((long long)wants) - 1;
+      unsigned long long base = 0;
+      if (lane == leader) base = atomicAdd(counter, (unsigned long long)__popcll(wants));
+      const unsigned lo32 = __shfl((unsigned)base, leader), hi32 = __shfl((unsigned)(base >> 32), leader);
+      base = ((unsigned long long)hi32 << 32) | lo32;
+      if (want) {
+        const unsigned long long r = base + (unsigned long long)__popcll(wants & ((1ull << lane) - 1ull));
+        if (r < (unsigned long long)n_rows) {
+          row = (long long)r;
+          it = 0;
+          const double* g = goal + 7 * (row / rows_per_goal);
+          Ginv = se3_mul(load_se3(w.link_place + 12 * iv.link), ik_se3_inverse(ik_pose_se3(g)));
+          const double* qi = q_in + row * dof;
+          ik_load_row(jt, iv, L, qi);
+          if (q_in != q_out)  // the slots outside the chain pass through
+            for (int d = 0; d < dof; ++d) q_out[row * dof + d] = qi[d];
+        } else {
+          rows_left = false;
+        }
+      }
+    }
+    if (!__ballot(row >= 0)) break;  // no lane of the wave holds a row: none is left
+    if (row >= 0) {
+      const SE3 T = ik_fk(jt, iv, L);
+      double err[6];
+      ik_log6(se3_mul(Ginv, T), err);
+      int st = 0;
+      bool fin = true;
+      if (ik_norm6(err) < iv.eps) st = MPG_IK_CONVERGED;
+      else if (it >= iv.max_iter) st = 0;
+      else if (!ik_update(jt, iv, L, T, err)) st = MPG_IK_SINGULAR;
+      else fin = false;
+      if (fin) {
+        ik_store_row(jt, iv, L, q_out + row * dof);
+        status[row] = (uint8_t)st;
+        if (err_out)
+          for (int k = 0; k < 6; ++k) err_out[row * 6 + k] = err[k];
+        if (iters_out) iters_out[row] = it;
+        row = -1;
+      } else {
+        ++it;
+      }
+    }
+  }
+}
+
+// check_joint_limit and the distance_6D bit of every row (steps 2 and 3 of
+// mpg_ik_batch, before the collide pass on the wrapped values)
+__global__ __launch_bounds__(128) void ik_finish_kernel(DevWorld w, IkView iv, const double* __restrict__ goal,
+                                                       long long n_rows, long long rows_per_goal,
+                                                       double* __restrict__ q_out, uint8_t* __restrict__ status) {
+  const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n_rows) return;
+  status[row] |= (uint8_t)ik_finish_row(w, iv, goal + 7 * (row / rows_per_goal), q_out + row * w.dof);
+}
+
+// folds the collide pass's flags into the status bytes
+__global__ __launch_bounds__(256) void ik_fold_kernel(const uint8_t* __restrict__ flags, long long n_rows,
+                                                     uint8_t* __restrict__ status) {
+  const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n_rows) return;
+  if (flags[row] == 0) status[row] |= MPG_IK_COLLISION_FREE;
 }
 
 // per pair, the configurations whose pair mask has its bit: LDS counters per

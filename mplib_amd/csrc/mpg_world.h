@@ -65,6 +65,26 @@ struct mpg_world {
   std::mutex ws_mu;
   std::map<hipStream_t, Side> sides;  // guarded by ws_mu
   std::map<hipStream_t, Workspace> ws;
+  // mpg_ik_batch: per caller stream the row counter ik_clik_kernel's lanes
+  // claim rows from and the collide pass's flags (guarded by ws_mu, released
+  // with the stream's workspace); the staging of host-buffer calls (host_mu);
+  // host tables built by mpg_world_create
+  struct IkWork {
+    DevBuf<unsigned long long> counter;
+    DevBuf<uint8_t> flags;  // [rows]
+  };
+  std::map<hipStream_t, IkWork> ik_ws;
+  struct IkStage {
+    DevBuf<double> goal, q, start, err;
+    DevBuf<uint8_t> status;
+    DevBuf<int32_t> iters;
+  } ik_stage;
+  struct IkTables {
+    int cus = 256;
+    std::vector<int> chain_start, chain_len, chain_joints, joint_q_source;
+    std::vector<double> lo, hi;                  // [dof]
+    std::vector<unsigned char> kind, continuous;  // [dof] IKK_*, continuous joint
+  } ik;
   // free frames: the current poses (host copy; free_dev is the device buffer
   // DevWorld::free_cur points to) and the grow-only staging of host-buffer
   // calls (host_mu)

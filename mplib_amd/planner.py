@@ -87,3 +87,105 @@ def generate_collision_pair(world, link_names: Sequence[str], urdf_path: str, sa
     if verbose:
         print("Saving the SRDF file to %s" % srdf)
     return srdf
+
+
+# ---------------------------------------------------------------------------
+# Planner.IK (planner.py:256-356): the n_init_qpos CLIK runs, their limit /
+# collision / distance_6D filter and the selection of the answers, with the
+# loop's body done for every (goal, seed) row by one device call
+# (PlanningWorld.ik_batch, C ABI mpg_ik_batch).
+# ---------------------------------------------------------------------------
+IK_CONVERGED, IK_IN_LIMITS, IK_COLLISION_FREE, IK_WITHIN_THRESHOLD, IK_SINGULAR, IK_VALID = 1, 2, 4, 8, 16, 15
+_IK_SUCCESS = IK_CONVERGED | IK_IN_LIMITS | IK_COLLISION_FREE  # the loop's `success` before the distance test
+
+
+def distance_6d(p1, q1, p2, q2) -> float:
+    """Planner.distance_6D (planner.py:165-168)."""
+    p1, q1, p2, q2 = (np.asarray(a, np.float64) for a in (p1, q1, p2, q2))
+    return float(np.linalg.norm(p1 - p2) + min(np.linalg.norm(q1 - q2), np.linalg.norm(q1 + q2)))
+
+
+def select_ik(q, status, start_qpos, *, threshold: float = 1e-3, return_closest: bool = False, equiv_mask=None,
+              upper=None, distance=None):
+    """What Planner.IK keeps of one goal's rows (planner.py:289-356).
+    ``q`` [S, dof] and ``status`` [S] are the rows in seed order.  The rows
+    with every MPG_IK_VALID bit are taken in that order, one within 0.1 (L2
+    norm) of an earlier kept one is dropped.  No row kept: the reference's two
+    failure strings -- the minimum distance_6D of the rows that converged inside
+    the limits without collision (``distance(r)`` gives row r's; it is only
+    called for those), or "Cannot find valid solution" when there is none.
+    ``return_closest``: the 2 pi-equivalent choice of planner.py:337-355 for
+    the joints of ``equiv_mask`` (revolute with a range above 2 pi) against
+    their ``upper`` limits, then the answer nearest to ``start_qpos``.
+    Returns (status_string, q_goals or None)."""
+    q = np.asarray(q, np.float64)
+    status = np.asarray(status)
+    kept: List[np.ndarray] = []
+    min_dis = 1e9
+    for r in range(len(q)):
+        if (int(status[r]) & _IK_SUCCESS) != _IK_SUCCESS:
+            continue
+        if int(status[r]) & IK_WITHIN_THRESHOLD:
+            min_dis = min(min_dis, 0.0 if distance is None else float(distance(r)))
+            if all(np.linalg.norm(k - q[r]) >= 0.1 for k in kept):
+                kept.append(q[r].copy())
+        else:
+            min_dis = min(min_dis, float("inf") if distance is None else float(distance(r)))
+    if not kept:
+        if min_dis != 1e9:
+            return f"IK Failed! Distance {min_dis} is greater than {threshold=}.", None
+        return "IK Failed! Cannot find valid solution.", None
+    if not return_closest:
+        return "Success", kept
+    goals = np.asarray(kept)
+    start = np.asarray(start_qpos, np.float64)[None]
+    if equiv_mask is not None and np.any(equiv_mask):
+        em = np.asarray(equiv_mask, bool)
+        q1 = goals[:, em]
+        q2 = q1 + 2 * np.pi
+        s = start[:, em]
+        closer = (q2 < np.asarray(upper, np.float64)[None, em]) & (np.abs(q1 - s) > np.abs(q2 - s))
+        goals[:, em] = np.where(closer, q2, q1)
+    return "Success", goals[np.linalg.norm(goals - start, axis=1).argmin()]
+
+
+def _state_joint_info(world):
+    """(types, limits [dof, 2]) of the world's state: the move-group joints of
+    the planned articulations in map order (the layout of set_qpos_all)."""
+    types, lims = [], []
+    for art in world.get_planned_articulations():
+        pin = art.get_pinocchio_model()
+        t, l = pin.get_joint_types(), pin.get_joint_limits()
+        for i in art.get_move_group_joint_indices():
+            types.append(t[i])
+            lims.append(l[i][0])
+    return types, np.asarray(lims, np.float64).reshape(-1, 2)
+
+
+def ik(world, link, goal_pose, start_qpos, mask=None, *, n_init_qpos: int = 20, threshold: float = 1e-3,
+       return_closest: bool = False, seed: int = 0):
+    """Planner.IK over the world's state (the planned articulations' move-group
+    joints): ``goal_pose`` (7,) returns (status_string, q_goals or None) as the
+    reference does -- q_goals a list of states, or one state with
+    ``return_closest``; an (M, 7) array returns a list of such pairs, all from
+    one device call.  ``link``: a planned articulation's user link name (or a
+    world link index); ``mask``: True freezes a state value; seed 0 of each
+    goal is ``start_qpos``, the others are drawn on the device."""
+    goals = np.asarray(goal_pose, np.float64)
+    single = goals.ndim == 1
+    goals = goals.reshape(-1, 7)
+    start = np.asarray(start_qpos, np.float64).reshape(-1)
+    q, status, _, _ = world.ik_batch(link, goals, start_qpos=start, n_init_qpos=int(n_init_qpos),
+                                     mask=None if mask is None or len(mask) == 0 else np.asarray(mask, bool),
+                                     seed=int(seed), threshold=float(threshold))
+    types, lims = _state_joint_info(world)
+    equiv = np.array([t.startswith("JointModelR") for t in types], bool) & (lims[:, 1] - lims[:, 0] > 2 * np.pi)
+    li = world.ik_link_index(link) if isinstance(link, str) else int(link)
+    out = []
+    for g in range(len(goals)):
+        def distance(r, g=g):  # only for the failure string's minimum
+            pose = world.fk_link_pose(q[g, r], li)
+            return distance_6d(goals[g, :3], goals[g, 3:], pose[:3], pose[3:])
+        out.append(select_ik(q[g], status[g], start, threshold=threshold, return_closest=return_closest,
+                             equiv_mask=equiv, upper=lims[:, 1], distance=distance))
+    return out[0] if single else out
