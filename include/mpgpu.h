@@ -681,6 +681,89 @@ int mpg_ik_batch(mpg_world *world, int32_t link, const double *goal_pose /* [n_g
                  int32_t *iters /* [rows] or NULL */, int mem, void *stream);
 
 /*
+ * Planner.plan_screw's loop (mplib/planner.py:526-671) for many goals in one
+ * device call: row i moves user link `link` from the state q_start[i] towards
+ * the pose goal[i] along the screw between them and returns the joint-space
+ * waypoints (the path plan_screw hands to TOPP-RA; the time parametrisation is
+ * not part of this call).  fp64, no fused multiply-add.
+ *
+ * Start.  T = goal * link_pose(q_start)^-1, the link pose with getLinkPose's
+ * quaternion round trip.  Exponential coordinates as pose2exp_coordinate
+ * (planner.py:575-605), tr the trace of T's rotation:
+ *   |tr - 3| <= 1e-8 + 3e-5 (np.isclose): omega = 0, theta = 1 -- a rotation
+ *     below about 5.5e-3 rad is dropped, the move is a pure translation;
+ *   |tr + 1| <= 1e-8 + 1e-5: the row ends at once with MPG_SCREW_ROT_PI and one
+ *     waypoint (plan_screw returns "screw plan failed." there);
+ *   else theta = acos((tr - 1) / 2), omega = skew part / (2 sin theta).
+ * v = (I / theta - [omega] / 2 + (1 / theta - 1 / (2 tan(theta / 2))) [omega]^2) p
+ * and twist = (v, omega) * theta.
+ *
+ * Step.  J: the WORLD Jacobian of the link's parent joint (getLinkJacobian,
+ * local = false) over the joints above the link that have a dof slot; every
+ * other slot's column is zero and the slot keeps its start value.
+ *   dq = J^T (J J^T)^-1 twist (Cholesky, no damping); dq *= qpos_step / |dq|;
+ *   dtw = J dq; if |dtw| > |twist|, both are scaled by |twist| / |dtw| and the
+ *   step is the last one; q += dq (a continuous joint adds the angle, it is
+ *   not wrapped); twist -= dtw.
+ * Row end, the first of (in this order, after the update):
+ *   a non-positive (or NaN) Cholesky pivot      MPG_SCREW_SINGULAR, before the update
+ *   |dtw| < 1e-4                                MPG_SCREW_STALLED, the state is not stored
+ *   a dof slot with finite limits has q < lo - 1e-3 or q > hi + 1e-3 (every
+ *     slot of the row, those outside the chain too; no 2 pi wrap: plan_screw's
+ *     own test, planner.py:639-647; a joint the snapshot holds as a constant,
+ *     such as a gripper finger outside the move group, has no slot and is
+ *     not tested)                               MPG_SCREW_LIMIT, the state is not stored
+ *   the step was the last one                   stored, MPG_SCREW_REACHED
+ *   max_waypoints states are stored             MPG_SCREW_TRUNCATED
+ * The reference's loop has no bound; this one stores a waypoint or ends the
+ * row in every pass, so it ends for any input (NaNs satisfy no test and end at
+ * the cap or at a NaN pivot).
+ *
+ * Collisions.  The path does not depend on them (plan_screw only aborts on a
+ * collision).  After all rows are integrated one mpg_collide_batch pass runs on
+ * the same stream over the padded [rows * max_waypoints, dof] path, movable
+ * objects at their current poses.  MPG_SCREW_COLLISION_FREE: no waypoint
+ * 1 .. n_waypoints - 1 has a non-zero flag; waypoint 0, the start state, is
+ * not checked, as in plan_screw.  first_hit: the first such waypoint, or -1.
+ * A row is plan_screw's "Success" when status & MPG_SCREW_VALID ==
+ * MPG_SCREW_VALID.
+ *
+ * Deviation: numpy's pinv is an SVD with a 1e-15 cut-off, this call solves
+ * the normal equations; the two differ only where J is rank deficient or
+ * nearly so.  A link with fewer than six joints with a dof slot above it is
+ * therefore MPG_E_UNSUPPORTED, as are dof > 32 and more than 15 joints above
+ * the link.  MPG_E_INVALID: a free-frame link, a link index out of range,
+ * qpos_step not > 0, max_waypoints outside [2, 4096], rows * max_waypoints >
+ * 2^31, a NULL buffer with rows > 0.
+ *
+ * path [rows * max_waypoints * dof]: the waypoints of row i from i *
+ * max_waypoints * dof; the slots past n_waypoints[i] repeat the last stored
+ * waypoint.  mem: MPG_MEM_HOST buffers are staged and the call synchronises
+ * (poses and joint values checked: finite, quaternion norm within 1e-6);
+ * MPG_MEM_DEVICE: goal, q_start and the outputs are device memory, everything
+ * is enqueued on `stream`, nothing synchronises.
+ */
+#define MPG_SCREW_REACHED 1
+#define MPG_SCREW_COLLISION_FREE 2
+#define MPG_SCREW_VALID 3
+#define MPG_SCREW_STALLED 4
+#define MPG_SCREW_LIMIT 8
+#define MPG_SCREW_TRUNCATED 16
+#define MPG_SCREW_SINGULAR 32
+#define MPG_SCREW_ROT_PI 64
+
+typedef struct mpg_screw_options {
+  double qpos_step;      /* 0.1; > 0, else MPG_E_INVALID */
+  int32_t max_waypoints; /* 64; 2 .. 4096 */
+} mpg_screw_options;
+
+int mpg_screw_batch(mpg_world *world, int32_t link, const double *goal /* [rows*7] (p, wxyz) */,
+                    const double *q_start /* [rows*dof] */, int64_t rows,
+                    const mpg_screw_options *opt /* NULL = defaults */, double *path /* [rows*max_waypoints*dof] */,
+                    int32_t *n_waypoints /* [rows] */, uint8_t *status /* [rows] */,
+                    int32_t *first_hit /* [rows] or NULL */, int mem, void *stream);
+
+/*
  * Diagnostics (host only, no device): the FCL 0.7.0 BVHModel<OBBRSS> tree the
  * snapshot builds for a BVH mesh (BVHModel::endModel -> buildTree:
  * BVFitter<OBBRSS>::fit, SPLIT_METHOD_MEAN; OBB half), whose OBB tests gate

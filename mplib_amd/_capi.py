@@ -76,6 +76,21 @@ MPG_IK_SINGULAR = 16
 MPG_IK_VALID = 15
 
 
+class ScrewOptions(ctypes.Structure):
+    """mpg_screw_options (include/mpgpu.h); the defaults are the reference's qpos_step and 64 waypoints."""
+    _fields_ = [("qpos_step", ctypes.c_double), ("max_waypoints", ctypes.c_int32)]
+
+
+MPG_SCREW_REACHED = 1
+MPG_SCREW_COLLISION_FREE = 2
+MPG_SCREW_VALID = 3
+MPG_SCREW_STALLED = 4
+MPG_SCREW_LIMIT = 8
+MPG_SCREW_TRUNCATED = 16
+MPG_SCREW_SINGULAR = 32
+MPG_SCREW_ROT_PI = 64
+
+
 class WorldInfo(ctypes.Structure):
     _fields_ = [("n_pairs", ctypes.c_int32), ("mask_words", ctypes.c_int32), ("dof", ctypes.c_int32),
                 ("n_links", ctypes.c_int32), ("device", ctypes.c_int32), ("block_size", ctypes.c_int32),
@@ -146,6 +161,9 @@ SIGNATURES = {
     "mpg_ik_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(IkOptions), ctypes.c_void_p,
                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "mpg_screw_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                       ctypes.POINTER(ScrewOptions), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "mpg_profile_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "mpg_profile_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
                                         ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_int]),

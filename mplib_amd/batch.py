@@ -281,6 +281,53 @@ class DeviceWorld:
                                      hp(status), hp(err), hp(iters), C.MPG_MEM_HOST, P(stream or 0)), "mpg_ik_batch")
         return q, status, err, iters
 
+    def screw_batch(self, link: int, goal_poses, start_qpos, *, qpos_step: float = 0.1, max_waypoints: int = 64,
+                    first_hit: bool = True, out=None, stream: Optional[int] = None):
+        """Planner.plan_screw's loop for every (goal pose, start state) row of
+        world link ``link`` in one call (mpg_screw_batch): the joint-space
+        waypoints of the straight-line screw motion, then one ``collide()``
+        pass over them.
+        Host path (numpy ``goal_poses`` (7,) / [n, 7]; ``start_qpos`` (dof,)
+        for every row, or [n, dof]): returns (path [n, max_waypoints, dof],
+        n_waypoints [n] i32, status [n] u8 of ``_capi.MPG_SCREW_*`` bits,
+        first_hit [n] i32 or None).  The slots of ``path`` past a row's count
+        repeat its last waypoint.
+        Device path (tensors with data_ptr(); ``goal_poses`` [n, 7],
+        ``start_qpos`` [n, dof]): ``out`` = (path, n_waypoints, status,
+        first_hit or None) preallocated tensors, filled on ``stream`` without
+        synchronising and returned."""
+        o = C.ScrewOptions(float(qpos_step), int(max_waypoints))
+        P = ctypes.c_void_p
+        if hasattr(goal_poses, "data_ptr"):
+            n = goal_poses.numel() // 7
+            if out is None:
+                raise ValueError("device path needs out=(path, n_waypoints, status, first_hit) preallocated")
+            if start_qpos.numel() != n * self.dof:
+                raise ValueError(f"start_qpos must be [{n}, {self.dof}]")
+            path, count, status, hit = out
+            ptr = lambda t: P(t.data_ptr() if t is not None else 0)  # noqa: E731
+            C.check(C.lib().mpg_screw_batch(self._h, int(link), ptr(goal_poses), ptr(start_qpos), n, ctypes.byref(o),
+                                            ptr(path), ptr(count), ptr(status), ptr(hit), C.MPG_MEM_DEVICE,
+                                            P(stream or 0)), "mpg_screw_batch")
+            return out
+        g = np.ascontiguousarray(np.asarray(goal_poses, dtype=np.float64)).reshape(-1, 7)
+        n = g.shape[0]
+        qs = np.asarray(start_qpos, dtype=np.float64)
+        if qs.ndim == 1 and qs.size == self.dof:
+            qs = np.broadcast_to(qs, (n, self.dof))
+        if qs.shape != (n, self.dof):
+            raise ValueError(f"start_qpos must be ({self.dof},) or [{n}, {self.dof}]")
+        qs = np.ascontiguousarray(qs)
+        mw = max(int(max_waypoints), 0)
+        path = np.zeros((n, mw, self.dof))
+        count = np.zeros(n, np.int32)
+        status = np.zeros(n, np.uint8)
+        hit = np.full(n, -1, np.int32) if first_hit else None
+        hp = lambda a: P(a.ctypes.data if a is not None else 0)  # noqa: E731
+        C.check(C.lib().mpg_screw_batch(self._h, int(link), hp(g), hp(qs), n, ctypes.byref(o), hp(path), hp(count),
+                                        hp(status), hp(hit), C.MPG_MEM_HOST, P(stream or 0)), "mpg_screw_batch")
+        return path, count, status, hit
+
 
 def device_sincos(x, device: int = 0):
     xa = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))

@@ -808,6 +808,10 @@ class PlanningWorld {
   void ik_batch(int link, const double* goal_pose, int64_t n_goals, int64_t rows_per_goal, const double* q_init,
                 const double* q_start, const mpg_ik_options& opt, double* q_out, uint8_t* status, double* err,
                 int32_t* iters, int mem, void* stream);
+  // Planner.plan_screw's loop batched (mpg_screw_batch); link as ik_link_index gives it
+  void plan_screw_batch(int link, const double* goal_pose, const double* q_start, int64_t rows,
+                        const mpg_screw_options& opt, double* path, int32_t* n_waypoints, uint8_t* status,
+                        int32_t* first_hit, int mem, void* stream);
   // batched OMPL motion validation over the planner's state space
   // (src/ompl_planner.cpp:248-293): SO2 dofs and the space's maximum extent
   struct MotionSpace {

@@ -1233,6 +1233,68 @@ PYBIND11_MODULE(pymp, m_all) {
            "Enqueue ik_batch on device buffers (float64 goal poses [n_goals, 7], q_init [rows, dim] or 0, q_start "
            "[dim] or 0 -> float64 q [rows, dim], uint8 status [rows], optional float64 err [rows, 6], int32 iters "
            "[rows]; rows = n_goals * rows_per_goal).  link: a world link index (ik_link_index).  No synchronisation.")
+      .def("plan_screw_batch",
+           [](PW& w, py::object link, py::array_t<double, py::array::c_style | py::array::forcecast> goal_poses,
+              py::array_t<double, py::array::c_style | py::array::forcecast> start_qpos, double qpos_step,
+              int max_waypoints) {
+             const int dim = w.state_dim();
+             const int li = py::isinstance<py::str>(link) ? w.ik_link_index(link.cast<std::string>()) : link.cast<int>();
+             if (!((goal_poses.ndim() == 1 && goal_poses.shape(0) == 7) ||
+                   (goal_poses.ndim() == 2 && goal_poses.shape(1) == 7)))
+               throw std::invalid_argument("goal_poses must be (7,) or [n, 7] float64 (p, wxyz)");
+             const int64_t n = goal_poses.ndim() == 1 ? 1 : goal_poses.shape(0);
+             const bool one = start_qpos.ndim() == 1 && start_qpos.shape(0) == dim;
+             if (!one && !(start_qpos.ndim() == 2 && start_qpos.shape(0) == n && start_qpos.shape(1) == dim))
+               throw std::invalid_argument("start_qpos must be (" + std::to_string(dim) + ",) or [n, " +
+                                           std::to_string(dim) + "] float64");
+             // refused before the outputs are sized by it
+             if (max_waypoints < 2 || max_waypoints > 4096)
+               throw std::invalid_argument("max_waypoints outside [2, 4096]");
+             std::vector<double> qs;
+             if (one) {
+               qs.resize((size_t)n * dim);
+               for (int64_t i = 0; i < n; ++i) std::copy(start_qpos.data(), start_qpos.data() + dim, qs.begin() + i * dim);
+             }
+             mpg_screw_options o{qpos_step, max_waypoints};
+             py::array_t<double> path({(ssize_t)n, (ssize_t)max_waypoints, (ssize_t)dim});
+             py::array_t<int32_t> count((ssize_t)n), hit((ssize_t)n);
+             py::array_t<uint8_t> status((ssize_t)n);
+             const double* gp = goal_poses.data();
+             const double* sp = one ? qs.data() : start_qpos.data();
+             double* po = path.mutable_data();
+             int32_t *co = count.mutable_data(), *ho = hit.mutable_data();
+             uint8_t* so = status.mutable_data();
+             {
+               py::gil_scoped_release rel;
+               w.plan_screw_batch(li, gp, sp, n, o, po, co, so, ho, MPG_MEM_HOST, nullptr);
+             }
+             return py::make_tuple(path, count, status, hit);
+           },
+           py::arg("link"), py::arg("goal_poses"), py::arg("start_qpos"), py::kw_only(), py::arg("qpos_step") = 0.1,
+           py::arg("max_waypoints") = 64,
+           "Planner.plan_screw's loop for n (goal pose, start state) rows of one link in one device call "
+           "(include/mpgpu.h mpg_screw_batch): the joint-space waypoints of the straight-line screw motion, then one "
+           "collide() pass over them.  link: a planned articulation's user link name, or a world link index.  "
+           "start_qpos: (dim,) for every row, or [n, dim].  Returns (path [n, max_waypoints, dim], n_waypoints [n] "
+           "int32, status [n] uint8 of MPG_SCREW_* bits, first_hit [n] int32: the first colliding waypoint or -1); "
+           "the slots of path past a row's count repeat its last waypoint; a row is plan_screw's Success when "
+           "status & 3 == 3.")
+      .def("plan_screw_batch_device",
+           [](PW& w, int link, uintptr_t goal_poses, uintptr_t start_qpos, int64_t rows, uintptr_t path,
+              uintptr_t n_waypoints, uintptr_t status, uintptr_t first_hit, uintptr_t stream, double qpos_step,
+              int max_waypoints) {
+             mpg_screw_options o{qpos_step, max_waypoints};
+             w.plan_screw_batch(link, reinterpret_cast<const double*>(goal_poses),
+                                reinterpret_cast<const double*>(start_qpos), rows, o, reinterpret_cast<double*>(path),
+                                reinterpret_cast<int32_t*>(n_waypoints), reinterpret_cast<uint8_t*>(status),
+                                reinterpret_cast<int32_t*>(first_hit), MPG_MEM_DEVICE, reinterpret_cast<void*>(stream));
+           },
+           py::arg("link"), py::arg("goal_poses_ptr"), py::arg("start_qpos_ptr"), py::arg("rows"), py::arg("path_ptr"),
+           py::arg("n_waypoints_ptr"), py::arg("status_ptr"), py::arg("first_hit_ptr") = 0, py::arg("stream") = 0,
+           py::arg("qpos_step") = 0.1, py::arg("max_waypoints") = 64,
+           "Enqueue plan_screw_batch on device buffers (float64 goal poses [rows, 7], start states [rows, dim] -> "
+           "float64 path [rows, max_waypoints, dim], int32 n_waypoints [rows], uint8 status [rows], optional int32 "
+           "first_hit [rows]).  link: a world link index (ik_link_index).  No synchronisation.")
       .def("fk_link_pose",
            [](PW& w, py::array_t<double, py::array::c_style | py::array::forcecast> state, int link) {
              const int dim = w.state_dim();

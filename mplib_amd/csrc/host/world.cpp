@@ -762,6 +762,14 @@ void PlanningWorld::ik_batch(int link, const double* goal_pose, int64_t n_goals,
                             err, iters, mem, stream),
                "mpg_ik_batch");
 }
+void PlanningWorld::plan_screw_batch(int link, const double* goal_pose, const double* q_start, int64_t rows,
+                                     const mpg_screw_options& opt, double* path, int32_t* n_waypoints,
+                                     uint8_t* status, int32_t* first_hit, int mem, void* stream) {
+  ensure_snapshot(CollisionRequest());
+  check_status(mpg_screw_batch(world_->get(), link, goal_pose, q_start, rows, &opt, path, n_waypoints, status, first_hit,
+                               mem, stream),
+               "mpg_screw_batch");
+}
 void PlanningWorld::collide_batch(const double* q, int64_t n, uint8_t* flags, uint32_t* masks) {
   ensure_snapshot(CollisionRequest());
   check_status(mpg_collide_batch(world_->get(), q, n, flags, masks, MPG_MEM_HOST, nullptr), "mpg_collide_batch");

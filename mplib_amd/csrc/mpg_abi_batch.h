@@ -711,6 +711,118 @@ int mpg_ik_batch(mpg_world* w, int32_t link, const double* goal_pose, int64_t n_
   return MPG_OK;
 }
 
+// device buffers: every row integrated by screw_kernel, one collide pass over
+// the padded path, its flags folded into status / first_hit
+static int launch_screw(mpg_world* w, const ScrewView& sv, const double* goal, const double* q_start, long long rows,
+                        double* path, int32_t* n_waypoints, uint8_t* status, int32_t* first_hit, hipStream_t s) {
+  const long long cfgs = rows * sv.max_waypoints;
+  StreamPin pin(w, s);
+  mpg_world::ScrewWork* K = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(w->ws_mu);
+    K = &w->screw_ws[s];
+  }
+  if (K->flags.get() && K->flags.cap() < (size_t)cfgs) HIP_TRY(hipStreamSynchronize(s));  // queued work may still read it
+  HIP_TRY(K->flags.reserve((size_t)cfgs));
+  // one wave per block, a lane per row
+  const size_t cl = (size_t)std::max(sv.iv.cl, 1);
+  const size_t lds = sizeof(double) * (kIkSlot * 64 + IKT_DOUBLES) * cl + sizeof(int) * IKT_INTS * cl;
+  hipLaunchKernelGGL(screw_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), lds, s, w->dw, sv, goal, q_start,
+                     rows, path, n_waypoints, status);
+  HIP_TRY(hipGetLastError());
+  const int rc = mpg_collide_batch(w, path, cfgs, K->flags.get(), nullptr, MPG_MEM_DEVICE, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(screw_fold_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, K->flags.get(),
+                     n_waypoints, rows, sv.max_waypoints, status, first_hit);
+  HIP_TRY(hipGetLastError());
+  return MPG_OK;
+}
+
+int mpg_screw_batch(mpg_world* w, int32_t link, const double* goal, const double* q_start, int64_t rows,
+                    const mpg_screw_options* opt, double* path, int32_t* n_waypoints, uint8_t* status,
+                    int32_t* first_hit, int mem, void* stream) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  if (rows < 0) return set_error(MPG_E_INVALID, "rows < 0");
+  if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
+  const auto& T = w->ik;
+  if (link < 0 || link >= w->dw.n_links) return set_error(MPG_E_INVALID, "link index out of range");
+  if (link >= w->dw.n_links - w->dw.n_free) return set_error(MPG_E_INVALID, "link is a free frame: no joint moves it");
+  mpg_screw_options o{0.1, 64};
+  if (opt) o = *opt;
+  if (!(o.qpos_step > 0) || !std::isfinite(o.qpos_step)) return set_error(MPG_E_INVALID, "qpos_step must be > 0");
+  if (o.max_waypoints < 2 || o.max_waypoints > 4096) return set_error(MPG_E_INVALID, "max_waypoints outside [2, 4096]");
+  if (rows > ((int64_t)1 << 31) / o.max_waypoints)
+    return set_error(MPG_E_INVALID, "rows * max_waypoints exceeds 2^31");
+  const int dof = w->dw.dof;
+  if (dof > kIkDof) return set_error(MPG_E_UNSUPPORTED, "mpg_screw_batch supports dof <= 32");
+  if (T.chain_len[link] > kIkChain)
+    return set_error(MPG_E_UNSUPPORTED, "mpg_screw_batch supports at most 15 joints above the link");
+  ScrewView sv{};
+  IkView& iv = sv.iv;
+  iv.link = link;
+  iv.cs = T.chain_start[link];
+  iv.cl = T.chain_len[link];
+  sv.qpos_step = o.qpos_step;
+  sv.max_waypoints = o.max_waypoints;
+  for (int d = 0; d < dof; ++d) {
+    iv.kind[d] = T.kind[d];
+    iv.bounded[d] = std::isfinite(T.lo[d]) && std::isfinite(T.hi[d]);
+    iv.lo[d] = T.lo[d];
+    iv.hi[d] = T.hi[d];
+    sv.offchain[d] = 1;
+  }
+  int moving = 0;
+  for (int k = 0; k < iv.cl; ++k) {
+    const int src = T.joint_q_source[T.chain_joints[iv.cs + k] - 1];
+    iv.move[k] = src >= 0;
+    if (src >= 0 && src < dof) {
+      sv.offchain[src] = 0;
+      ++moving;
+    }
+  }
+  if (moving < 6)
+    return set_error(MPG_E_UNSUPPORTED,
+                     "mpg_screw_batch needs at least six joints with a dof slot above the link (J J^T is singular)");
+  if (rows > 0 && (!goal || !q_start || !path || !n_waypoints || !status))
+    return set_error(MPG_E_INVALID, "goal / q_start / path / n_waypoints / status is NULL");
+  if (mem == MPG_MEM_HOST && rows > 0) {
+    for (int64_t g = 0; g < rows; ++g) {
+      const double* p = goal + 7 * g;
+      if (!finite_all(p, 7)) return set_error(MPG_E_INVALID, "non-finite goal pose");
+      const double nq = std::sqrt(p[3] * p[3] + p[4] * p[4] + p[5] * p[5] + p[6] * p[6]);
+      if (!(std::fabs(nq - 1.0) <= kFreeQuatTol))
+        return set_error(MPG_E_INVALID, "goal pose quaternion is not of unit norm (within 1e-6)");
+    }
+    if (!finite_all(q_start, (size_t)rows * dof)) return set_error(MPG_E_INVALID, "non-finite q_start");
+  }
+  if (rows == 0) return MPG_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (mem == MPG_MEM_DEVICE) return launch_screw(w, sv, goal, q_start, rows, path, n_waypoints, status, first_hit, s);
+  // host buffers: grow-only device staging kept by the world (one host call at
+  // a time: host_mu; no wait before a buffer is replaced, the call is synchronous)
+  std::lock_guard<std::mutex> lk(w->host_mu);
+  if (!s && w->own_stream) s = w->own_stream.get();
+  auto& S = w->screw_stage;
+  const size_t nq = (size_t)rows * std::max(dof, 1), np = nq * (size_t)o.max_waypoints;
+  if (S.goal.reserve(7 * (size_t)rows) != hipSuccess || S.start.reserve(nq) != hipSuccess ||
+      S.path.reserve(np) != hipSuccess || S.status.reserve((size_t)rows) != hipSuccess ||
+      S.count.reserve((size_t)rows) != hipSuccess || S.first_hit.reserve((size_t)rows) != hipSuccess)
+    return set_error(MPG_E_NOMEM, "screw staging buffers");
+  HIP_TRY(hipMemcpyAsync(S.goal.get(), goal, sizeof(double) * 7 * rows, hipMemcpyHostToDevice, s));
+  if (dof) HIP_TRY(hipMemcpyAsync(S.start.get(), q_start, sizeof(double) * rows * dof, hipMemcpyHostToDevice, s));
+  const int rc = launch_screw(w, sv, S.goal.get(), S.start.get(), rows, S.path.get(), S.count.get(), S.status.get(),
+                              first_hit ? S.first_hit.get() : nullptr, s);
+  if (rc) return rc;
+  if (dof)
+    HIP_TRY(hipMemcpyAsync(path, S.path.get(), sizeof(double) * rows * o.max_waypoints * dof, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(n_waypoints, S.count.get(), sizeof(int32_t) * rows, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(status, S.status.get(), (size_t)rows, hipMemcpyDeviceToHost, s));
+  if (first_hit) HIP_TRY(hipMemcpyAsync(first_hit, S.first_hit.get(), sizeof(int32_t) * rows, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return MPG_OK;
+}
+
 int mpg_debug_collide_pairs(mpg_world* w, int32_t geom_a, int32_t geom_b, int64_t n, const double* Ta,
                             const double* Tb, uint8_t* hit) {
   if (!w || n < 0 || (n > 0 && (!Ta || !Tb || !hit))) return set_error(MPG_E_INVALID, "bad arguments");

@@ -45,6 +45,7 @@
 #include "mpg_math.h"
 #include "mpg_fk.h"
 #include "mpg_ik.h"
+#include "mpg_screw.h"
 #include "mpg_bucket.h"
 #include "mpg_hostpipe.h"
 
@@ -6854,6 +6855,65 @@ __global__ __launch_bounds__(256) void ik_fold_kernel(const uint8_t* __restrict_
   const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= n_rows) return;
   if (flags[row] == 0) status[row] |= MPG_IK_COLLISION_FREE;
+}
+
+// ---------------------------------------------------------------------------
+// Planner.plan_screw's loop (mplib/planner.py:526-671), batched:
+// mpg_screw_batch.  The per-row arithmetic is mpg_screw.h's.
+// ---------------------------------------------------------------------------
+// One lane per row, one wave per block, the whole row in one launch.  A row is
+// at most max_waypoints steps of equal cost, so the grid is ceil(rows / 64)
+// blocks and no lane claims a second row.  Each lane writes its waypoints to
+// path [rows][max_waypoints][dof] as they are accepted and pads the rest.
+// LDS: the lanes' IkLane state, [chain joint][component][lane], then the
+// chain's joint constants (IkJointsTable), filled once per wave.
+__global__ __launch_bounds__(64) void screw_kernel(DevWorld w, ScrewView sv, const double* __restrict__ goal,
+                                                  const double* __restrict__ q_start, long long n_rows, double* path,
+                                                  int32_t* __restrict__ n_waypoints, uint8_t* __restrict__ status) {
+  extern __shared__ double screw_lds[];
+  const int lane = threadIdx.x;
+  const int cl = sv.iv.cl;
+  const IkLane L{screw_lds + lane, 64};
+  double* const td = screw_lds + (size_t)cl * kIkSlot * 64;
+  int* const ti = reinterpret_cast<int*>(td + (size_t)cl * IKT_DOUBLES);
+  for (int k = lane; k < cl; k += 64) {
+    const int j0 = w.chain_joints[sv.iv.cs + k] - 1;
+    ti[IKT_INTS * k + IKT_TYPE] = w.joint_type[j0];
+    ti[IKT_INTS * k + IKT_SRC] = w.joint_q_source[j0];
+    ti[IKT_INTS * k + IKT_MOVE] = sv.iv.move[k];
+    td[IKT_DOUBLES * k + IKT_QCONST] = w.joint_q_const[j0];
+    for (int c = 0; c < 3; ++c) td[IKT_DOUBLES * k + IKT_AXIS + c] = w.joint_axis[3 * j0 + c];
+    for (int c = 0; c < 12; ++c) td[IKT_DOUBLES * k + IKT_PLACE + c] = w.joint_place[12 * j0 + c];
+  }
+  __syncthreads();
+  const long long row = (long long)blockIdx.x * 64 + lane;
+  if (row >= n_rows) return;
+  const IkJointsTable jt{td, ti};
+  int count;
+  const int st = screw_row(w, jt, sv, L, goal + 7 * row, q_start + row * w.dof,
+                           path + row * sv.max_waypoints * w.dof, &count);
+  n_waypoints[row] = count;
+  status[row] = (uint8_t)st;
+}
+
+// folds the collide pass's flags of the padded path into the status bytes:
+// waypoints 1 .. count - 1 (the start state is not checked)
+__global__ __launch_bounds__(256) void screw_fold_kernel(const uint8_t* __restrict__ flags,
+                                                        const int32_t* __restrict__ n_waypoints, long long n_rows,
+                                                        int max_waypoints, uint8_t* __restrict__ status,
+                                                        int32_t* __restrict__ first_hit) {
+  const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n_rows) return;
+  int n = n_waypoints[row];
+  n = n < max_waypoints ? n : max_waypoints;
+  int hit = -1;
+  for (int i = 1; i < n; ++i)
+    if (flags[row * max_waypoints + i] != 0) {
+      hit = i;
+      break;
+    }
+  if (hit < 0) status[row] |= MPG_SCREW_COLLISION_FREE;
+  if (first_hit) first_hit[row] = hit;
 }
 
 // per pair, the configurations whose pair mask has its bit: LDS counters per

@@ -10,9 +10,11 @@ void release_stream_locked(mpg_world* w, hipStream_t s) {
   const auto wi = w->ws.find(s);
   const auto si = w->sides.find(s);
   const auto ki = w->ik_ws.find(s);
-  if (wi == w->ws.end() && si == w->sides.end() && ki == w->ik_ws.end()) return;
+  const auto ci = w->screw_ws.find(s);
+  if (wi == w->ws.end() && si == w->sides.end() && ki == w->ik_ws.end() && ci == w->screw_ws.end()) return;
   hipDeviceSynchronize();
   if (ki != w->ik_ws.end()) w->ik_ws.erase(ki);
+  if (ci != w->screw_ws.end()) w->screw_ws.erase(ci);
   if (wi != w->ws.end()) w->ws.erase(wi);
   if (si != w->sides.end()) {
     w->ws.erase(si->second.side.get());

@@ -85,6 +85,18 @@ struct mpg_world {
     std::vector<double> lo, hi;                  // [dof]
     std::vector<unsigned char> kind, continuous;  // [dof] IKK_*, continuous joint
   } ik;
+  // mpg_screw_batch: per caller stream the collide pass's flags of the padded
+  // path (guarded by ws_mu, released with the stream's workspace); the staging
+  // of host-buffer calls (host_mu)
+  struct ScrewWork {
+    DevBuf<uint8_t> flags;  // [rows * max_waypoints]
+  };
+  std::map<hipStream_t, ScrewWork> screw_ws;
+  struct ScrewStage {
+    DevBuf<double> goal, start, path;
+    DevBuf<uint8_t> status;
+    DevBuf<int32_t> count, first_hit;
+  } screw_stage;
   // free frames: the current poses (host copy; free_dev is the device buffer
   // DevWorld::free_cur points to) and the grow-only staging of host-buffer
   // calls (host_mu)

@@ -189,3 +189,47 @@ def ik(world, link, goal_pose, start_qpos, mask=None, *, n_init_qpos: int = 20, 
         out.append(select_ik(q[g], status[g], start, threshold=threshold, return_closest=return_closest,
                              equiv_mask=equiv, upper=lims[:, 1], distance=distance))
     return out[0] if single else out
+
+
+# ---------------------------------------------------------------------------
+# Planner.plan_screw (planner.py:526-671): the straight-line screw motion to a
+# goal pose, its waypoints integrated and collision-checked by one device call
+# (PlanningWorld.plan_screw_batch, C ABI mpg_screw_batch).  The result is the
+# joint-space path the reference hands to TOPP-RA; the time parametrisation is
+# not part of it.
+# ---------------------------------------------------------------------------
+SCREW_REACHED, SCREW_COLLISION_FREE, SCREW_VALID = 1, 2, 3
+SCREW_STALLED, SCREW_LIMIT, SCREW_TRUNCATED, SCREW_SINGULAR, SCREW_ROT_PI = 4, 8, 16, 32, 64
+_SCREW_REASONS = ((SCREW_STALLED, "STALLED"), (SCREW_LIMIT, "LIMIT"), (SCREW_TRUNCATED, "TRUNCATED"),
+                  (SCREW_SINGULAR, "SINGULAR"), (SCREW_ROT_PI, "ROT_PI"))
+
+
+def screw_reason(status: int, first_hit: int = -1) -> str:
+    """Why a row of plan_screw_batch is not a Success: the names of its end
+    bit and, when a waypoint collides, COLLISION with the waypoint's index."""
+    names = [n for b, n in _SCREW_REASONS if int(status) & b]
+    if not int(status) & SCREW_COLLISION_FREE:
+        names.append("COLLISION" if first_hit < 0 else f"COLLISION at waypoint {int(first_hit)}")
+    return ", ".join(names)
+
+
+def plan_screw(world, link, goal_pose, current_qpos, qpos_step: float = 0.1, *, max_waypoints: int = 64):
+    """Planner.plan_screw over the world's state: ``goal_pose`` (7,) returns
+    {"status": "Success", "path": [count, dof]} or {"status": "screw plan
+    failed", "reason": names of the status bits}; an (n, 7) array returns a
+    list of such dictionaries, all from one device call, every row starting at
+    ``current_qpos`` ((dof,) or [n, dof]).  ``link``: a planned articulation's
+    user link name (or a world link index).  The articulations' qpos is not
+    touched."""
+    goals = np.asarray(goal_pose, np.float64)
+    single = goals.ndim == 1
+    goals = goals.reshape(-1, 7)
+    path, count, status, hit = world.plan_screw_batch(link, goals, np.asarray(current_qpos, np.float64),
+                                                      qpos_step=float(qpos_step), max_waypoints=int(max_waypoints))
+    out = []
+    for i in range(len(goals)):
+        if (int(status[i]) & SCREW_VALID) == SCREW_VALID:
+            out.append({"status": "Success", "path": path[i, :count[i]].copy()})
+        else:
+            out.append({"status": "screw plan failed", "reason": screw_reason(status[i], hit[i])})
+    return out[0] if single else out

@@ -1,0 +1,271 @@
+"""Shared inputs and references of the screw-motion tests (test_screw_host.py,
+test_screw_batch.py).
+
+np_plan_screw is a numpy restatement of planner.py:559-671 (plan_screw without
+its collision abort and without TOPP-RA): the link pose from the CPU oracle's
+FK, J from the host PinocchioModel's compute_full_jacobian / get_link_jacobian(
+HAND, local=False), the step from np.linalg.pinv.
+
+Recipe S: Panda, link panda_hand, n = 256, default_rng(2025): q_start uniform
+in 0.6 x the limits; the goal is the start pose rotated in the world by 0.05 ..
+0.5 rad about a random axis and translated by 0.02 .. 0.15 m in a random
+direction.  Everything is computed once per process and handed out read-only.
+"""
+import ctypes
+import functools
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+
+import ik_cases as K
+import worlds as Wd
+
+HAND = K.HAND
+N_ROWS = 256
+WELL = 1e-2          # "well conditioned": the smallest singular value of J along the path stays above this
+REF_CAP = 4096       # the reference's loop is unbounded; nothing in recipe S comes near this
+REACHED, COLLISION_FREE, VALID, STALLED, LIMIT, TRUNCATED, SINGULAR, ROT_PI = 1, 2, 3, 4, 8, 16, 32, 64
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_ro = K._ro
+
+
+@functools.lru_cache(maxsize=None)
+def limits9():
+    """The limits of the Panda's nine joints, the arm's seven first (plan_screw tests them all)."""
+    return _ro(np.array(K.oracle_world().art.joint_limits()[:9], np.float64))[0]
+
+
+# --- numpy restatement of planner.py:562-605 ---------------------------------
+def quat2mat(q):
+    w, x, y, z = q
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def mat2quat(R):
+    """(w, x, y, z) of a rotation matrix (Shepperd), w >= 0."""
+    R = np.asarray(R, np.float64)
+    t = np.array([R[0, 0] + R[1, 1] + R[2, 2], R[0, 0], R[1, 1], R[2, 2]])
+    i = int(t.argmax())
+    if i == 0:
+        w = np.sqrt(1 + t[0]) / 2
+        q = np.array([w, (R[2, 1] - R[1, 2]) / (4 * w), (R[0, 2] - R[2, 0]) / (4 * w), (R[1, 0] - R[0, 1]) / (4 * w)])
+    else:
+        a, b, c = i - 1, i % 3, (i + 1) % 3
+        s = np.sqrt(1 + R[a, a] - R[b, b] - R[c, c]) / 2
+        q = np.zeros(4)
+        q[1 + a] = s
+        q[1 + b] = (R[b, a] + R[a, b]) / (4 * s)
+        q[1 + c] = (R[c, a] + R[a, c]) / (4 * s)
+        q[0] = (R[c, b] - R[b, c]) / (4 * s)
+    q /= np.linalg.norm(q)
+    return q if q[0] >= 0 else -q
+
+
+def pose7D2mat(pose):
+    mat = np.eye(4)
+    mat[0:3, 3] = pose[:3]
+    mat[0:3, 0:3] = quat2mat(pose[3:])
+    return mat
+
+
+def skew(vec):
+    return np.array([[0, -vec[2], vec[1]], [vec[2], 0, -vec[0]], [-vec[1], vec[0], 0]])
+
+
+def rot2so3(rotation):
+    """(omega, theta, branch): branch 1 = np.isclose(trace, 3), 2 = np.isclose(trace, -1), 0 otherwise."""
+    if np.isclose(rotation.trace(), 3):
+        return np.zeros(3), 1, 1
+    if np.isclose(rotation.trace(), -1):
+        return np.zeros(3), -1e6, 2
+    theta = np.arccos((rotation.trace() - 1) / 2)
+    omega = (1 / 2 / np.sin(theta) * np.array([rotation[2, 1] - rotation[1, 2], rotation[0, 2] - rotation[2, 0],
+                                               rotation[1, 0] - rotation[0, 1]]).T)
+    return omega, theta, 0
+
+
+def pose2exp_coordinate(pose):
+    """planner.py:575-605 with the twist already multiplied by theta: (twist [6] or None, branch)."""
+    omega, theta, branch = rot2so3(pose[:3, :3])
+    if theta < -1e5:
+        return None, branch
+    ss = skew(omega)
+    inv_left_jacobian = np.eye(3) / theta - 0.5 * ss + (1.0 / theta - 0.5 / np.tan(theta / 2)) * ss @ ss
+    v = inv_left_jacobian @ pose[:3, 3]
+    return np.concatenate([v, omega]) * theta, branch
+
+
+# --- numpy restatement of planner.py:607-671 ---------------------------------
+def np_plan_screw(goal7, q0, qpos_step=0.1, solver="pinv", cap=REF_CAP, pin=None, fk=None, lim=None, pad=(0.0, 0.0)):
+    """(status bit, waypoints [count, len(q0)], sigma_min of J over the moving
+    columns along the path, |dq| of every step).  solver: "pinv" as the
+    reference, or "chol" for J^T (J J^T)^-1 by Cholesky (the stated deviation).
+    pin / fk / lim: another model's PinocchioModel, link pose function and
+    limits (default: the Panda)."""
+    pin = K.pin_model() if pin is None else pin
+    fk = (lambda q: K.hand_fk(q)[0][0]) if fk is None else fk
+    lim = limits9() if lim is None else lim
+    nd = len(q0)
+    q = np.concatenate([np.asarray(q0, np.float64), np.asarray(pad, np.float64)])
+    rel = pose7D2mat(np.asarray(goal7, np.float64)) @ np.linalg.inv(pose7D2mat(fk(q[:nd])))
+    tw, branch = pose2exp_coordinate(rel)
+    path = [q[:nd].copy()]
+    sig, steps = np.inf, []
+    if tw is None:
+        return ROT_PI, np.array(path), sig, np.array(steps)
+    tw = tw.reshape(-1, 1)
+    while True:
+        pin.compute_full_jacobian(list(q))
+        J = np.asarray(pin.get_link_jacobian(HAND, False))
+        sig = min(sig, np.linalg.svd(J[:, :nd], compute_uv=False).min())
+        if solver == "pinv":
+            dq = np.linalg.pinv(J) @ tw
+        else:
+            dq = J.T @ np.linalg.solve(J @ J.T, tw)
+        dq *= qpos_step / np.linalg.norm(dq)
+        dtw = J @ dq
+        flag = False
+        if np.linalg.norm(dtw) > np.linalg.norm(tw):
+            ratio = np.linalg.norm(tw) / np.linalg.norm(dtw)
+            dq = dq * ratio
+            dtw = dtw * ratio
+            flag = True
+        q = q + dq.reshape(-1)
+        tw = tw - dtw
+        if np.linalg.norm(dtw) < 1e-4:
+            return STALLED, np.array(path), sig, np.array(steps)
+        if ((q < lim[:len(q), 0] - 1e-3) | (q > lim[:len(q), 1] + 1e-3)).any():
+            return LIMIT, np.array(path), sig, np.array(steps)
+        path.append(q[:nd].copy())
+        steps.append(np.linalg.norm(dq))
+        if flag:
+            return REACHED, np.array(path), sig, np.array(steps)
+        if len(path) >= cap:
+            return TRUNCATED, np.array(path), sig, np.array(steps)
+
+
+def random_unit(rng, n):
+    v = rng.normal(size=(n, 3))
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def axis_angle_mat(axis, angle):
+    ss = skew(axis)
+    return np.eye(3) + np.sin(angle) * ss + (1 - np.cos(angle)) * ss @ ss
+
+
+def moved_pose(pose7, axis, angle, shift):
+    """pose7 rotated in the world by `angle` about `axis` (its position kept) and translated by `shift`."""
+    R = axis_angle_mat(axis, angle) @ quat2mat(pose7[3:])
+    return np.concatenate([pose7[:3] + shift, mat2quat(R)])
+
+
+@functools.lru_cache(maxsize=None)
+def recipe_s(n=N_ROWS, seed=2025):
+    """(q_start [n, 7], goal [n, 7])."""
+    lim = K.limits()
+    rng = np.random.default_rng(seed)
+    q0 = rng.uniform(0.6 * lim[:, 0], 0.6 * lim[:, 1], size=(n, 7))
+    axis = random_unit(rng, n)
+    angle = rng.uniform(0.05, 0.5, size=n)
+    shift = random_unit(rng, n) * rng.uniform(0.02, 0.15, size=(n, 1))
+    start = K.hand_fk(q0)[0]
+    goal = np.stack([moved_pose(start[i], axis[i], angle[i], shift[i]) for i in range(n)])
+    return _ro(q0, goal)
+
+
+@functools.lru_cache(maxsize=None)
+def reference_s(solver="pinv", eps=0.0):
+    """np_plan_screw over recipe S: (status [n], count [n], paths (tuple of
+    [count, 7]), sigma_min [n], steps (tuple)).  eps: the start perturbed by
+    eps * N(0, 1) (the reference's own two-run figure)."""
+    q0, goal = recipe_s()
+    if eps:
+        q0 = q0 + eps * np.random.default_rng(99).normal(size=q0.shape)
+    out = [np_plan_screw(goal[i], q0[i], solver=solver) for i in range(len(q0))]
+    st = np.array([o[0] for o in out], np.uint8)
+    cnt = np.array([len(o[1]) for o in out], np.int32)
+    sig = np.array([o[2] for o in out])
+    _ro(st, cnt, sig, *(o[1] for o in out))
+    return st, cnt, tuple(o[1] for o in out), sig, tuple(o[3] for o in out)
+
+
+def well_rows():
+    return reference_s()[3] >= WELL
+
+
+def compare_paths(status, count, path, rows=None):
+    """Against reference_s: (rows whose status or count differ [bool], max|dq|
+    over the waypoints of the rows where both agree [per row])."""
+    rst, rcnt, rpaths, _, _ = reference_s()
+    rows = np.arange(len(status)) if rows is None else np.asarray(rows)
+    differ = np.zeros(len(rows), bool)
+    dmax = np.zeros(len(rows))
+    for k, r in enumerate(rows):
+        differ[k] = (int(status[k]) & ~COLLISION_FREE) != rst[r] or count[k] != rcnt[r]
+        if not differ[k]:
+            dmax[k] = np.abs(path[k][:rcnt[r]] - rpaths[r]).max()
+    return differ, dmax
+
+
+# --- mpg_screw.h compiled for the host (tests/native/screw_host.cpp) ----------
+_lib = None
+
+
+def host_lib():
+    """Build tests/native/screw_host.cpp into a per-process file and load it."""
+    global _lib
+    if _lib is None:
+        out = os.path.join(tempfile.gettempdir(), "mplib_amd_screw_host_%d_%d.so" % (os.getuid(), os.getpid()))
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", out,
+                               os.path.join(_HERE, "native", "screw_host.cpp")])
+        _lib = ctypes.CDLL(out)
+    return _lib
+
+
+def host_exp(T):
+    """screw_exp_coordinate on [n, 4, 4] transforms: (twist [n, 6], branch [n])."""
+    T = np.asarray(T, np.float64)
+    n = len(T)
+    flat = np.ascontiguousarray(np.concatenate([T[:, :3, :3].reshape(n, 9), T[:, :3, 3]], axis=1))
+    tw = np.zeros((n, 6))
+    br = np.zeros(n, np.int32)
+    P = ctypes.c_void_p
+    host_lib().screw_host_exp(flat.ctypes.data_as(P), ctypes.c_long(n), tw.ctypes.data_as(P), br.ctypes.data_as(P))
+    return tw, br
+
+
+def host_header_rows(goal, q0, qpos_step=0.1, max_waypoints=64, desc=None, link=HAND):
+    """mpg_screw.h's row on the host: (path [n, max_waypoints, dof], count [n], status [n])."""
+    d = Wd.desc_arrays(K.oracle_world()) if desc is None else desc
+    keep = []
+
+    def arr(a, dt_):
+        a = np.ascontiguousarray(np.asarray(a, dtype=dt_))
+        keep.append(a)
+        return a.ctypes.data_as(ctypes.c_void_p)
+
+    dof = int(d["dof"])
+    src = np.asarray(d["joint_q_source"])
+    lo, hi = np.full(dof, -np.inf), np.full(dof, np.inf)
+    for j, s in enumerate(src):
+        if s >= 0:
+            lo[s], hi[s] = d["joint_lower"][j], d["joint_upper"][j]
+    n = len(q0)
+    path = np.zeros((n, max_waypoints, dof))
+    cnt = np.zeros(n, np.int32)
+    st = np.zeros(n, np.uint8)
+    rc = host_lib().screw_host_rows(
+        len(d["joint_type"]), arr(d["joint_type"], np.int32), arr(d["joint_parent"], np.int32),
+        arr(d["joint_q_source"], np.int32), arr(d["joint_q_const"], np.float64), arr(d["joint_axis"], np.float64),
+        arr(d["joint_placement"], np.float64), dof, len(d["link_parent"]), arr(d["link_parent"], np.int32),
+        arr(d["link_placement"], np.float64), int(link), arr(lo, np.float64), arr(hi, np.float64),
+        arr(goal, np.float64), arr(q0, np.float64), ctypes.c_long(n), ctypes.c_double(qpos_step), int(max_waypoints),
+        path.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p), st.ctypes.data_as(ctypes.c_void_p))
+    assert rc == 0
+    return path, cnt, st
