@@ -133,6 +133,7 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
   }
   BpProgram bpp;
   bp_build(d, obb, bpp);
+  bp_build_support(d, obb, bpp);
   size_t lds = 0;
   const int W = std::max(1, (d->n_pairs + 31) / 32);
   const int block = choose_block(cull_lds_per_thread(d->n_moving, bpp.n_saves, W), &lds);
@@ -664,6 +665,17 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
   const size_t o_bop = bb.add(bpp.oplace.data(), bpp.oplace.size());
   const size_t o_boq = bb.add(bpp.oquat.data(), bpp.oquat.size());
   const size_t o_boc = bb.add(bpp.ocen.data(), bpp.ocen.size());
+  const size_t o_bsh = bb.add(bpp.shtab.data(), bpp.shtab.size());
+  std::vector<int> sched_rec(SR_STRIDE * sched_pair.size(), 0);
+  for (size_t e = 0; e < sched_pair.size() && d->n_pairs > 0; ++e) {
+    const int p = sched_pair[e];
+    int* r = sched_rec.data() + SR_STRIDE * e;
+    r[SR_P] = p;
+    r[SR_A] = d->pair_a[p];
+    r[SR_B] = d->pair_b[p];
+    r[SR_SH] = (bpp.pair_sh[2 * p] + 2) | ((bpp.pair_sh[2 * p + 1] + 2) << 16);
+  }
+  const size_t o_srr = bb.add(sched_rec.data(), sched_rec.size());
   const size_t o_olf = bb.add(oct_leaf.data(), oct_leaf.size());
   const size_t o_mtr = bb.add(mesh_tri.data(), mesh_tri.size());
   const size_t o_mnd = bb.add(mesh_node.data(), mesh_node.size());
@@ -713,6 +725,10 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
   dw.W = W;
   dw.mpr_tol = d->gjk_tolerance;
   dw.bp_margin = bp_margin;
+  // the support-height axes' own fp32 evaluation (two rotations, the cell
+  // ratios, the interpolation: ~15 dependent operations on values within X),
+  // bounded like the rest of the cull's rounding
+  dw.sh_margin = bp_margin + (float)(kFp32CullRel * X);
   dw.small_margin = small_margin;
   dw.n_prism = n_prism;
   dw.prism_bound = to_cptr<double>(base + o_pbd);
@@ -738,6 +754,7 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
 #ifdef MPG_DIAG  // ablation builds only (changes results)
   if (const char* m = std::getenv("MPG_DEBUG_MARGIN")) {
     dw.bp_margin = (float)std::atof(m);
+    dw.sh_margin = dw.bp_margin + (float)(kFp32CullRel * X);
     dw.small_margin = std::atof(m);
   }
 #endif
@@ -822,6 +839,7 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
   dw.sched_start = I(o_ss);
   dw.sched_pair = I(o_sp);
   dw.sched_other = I(o_so);
+  dw.sched_rec = I(o_srr);
   dw.st_start = I(o_sts);
   dw.st_m = I(o_stm);
   dw.st_r = to_cptr<float>(base + o_str);
@@ -854,6 +872,7 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
   bp.oplace = F(o_bop);
   bp.oquat = F(o_boq);
   bp.ocen = F(o_boc);
+  bp.shtab = F(o_bsh);
   dw.oct_leaf = to_cptr<double>(base + o_olf);
   dw.oct_path = to_cptr<uint64_t>(base + o_opa);
   dw.oct_depth = to_cptr<int>(base + o_ode);

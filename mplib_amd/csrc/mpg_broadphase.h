@@ -84,6 +84,7 @@ struct BpView {
   cptr<float> oplace;    // [n_moving*12]
   cptr<float> oquat;     // [n_moving*4] rotation of oplace as a quaternion (x, y, z, w)
   cptr<float> ocen;      // [n_moving*3] the object's OBB centre in its joint frame (oplace * local centre)
+  cptr<float> shtab;     // [n_tables*kShFloats] support-height tables of the convex hulls (bp_support_height)
 };
 
 // motion kinds of the fp32 FK: a fixed (or constant) joint, a revolute or
@@ -428,6 +429,117 @@ inline uint32_t fsphere_obb_keep2(const float* c, float r, P rec, float margin) 
 #endif
 
 // ---------------------------------------------------------------------------
+// Support-height axes: a second separating test for the pairs the OBB SAT
+// kept.  Per convex hull a table of its support height about the OBB centre c,
+// h(d) = max_v (v - c) . d, at the corners of a kShK x kShK grid on each of the
+// 6 cube faces of directions (the face parametrisation of hull_cell: the
+// largest component m, the other two as ratios u / |m|, v / |m| in [-1, 1]).
+// h is convex and positively homogeneous, so on a face it is convex in (u, v)
+// and the bilinear interpolant of a cell's corner values is nowhere below it
+// (DESIGN.md "Broad phase"): the value returned is an upper bound of h(d).
+// ---------------------------------------------------------------------------
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MPG_SCHED_FENCE __builtin_amdgcn_sched_barrier(0)
+#else
+#define MPG_SCHED_FENCE (void)0
+#endif
+constexpr int kShK = 8;
+constexpr int kShN = kShK + 1;
+constexpr int kShFloats = 6 * kShN * kShN;
+enum { SH_NONE = -1, SH_SKIP = -2 };
+// what the SAT stage reads per schedule entry, four adjacent ints: the pair,
+// its objects and its sides' tables as (ta + 2) | (tb + 2) << 16 (low half 0:
+// SH_SKIP, the pair takes no support-axis test)
+enum { SR_P = 0, SR_A = 1, SR_B = 2, SR_SH = 3, SR_STRIDE = 4 };
+
+template <class P>
+MPG_INLINE float bp_support_height(P tab, float x, float y, float z) {
+  MPG_FP32_CONTRACT
+  const float ax = fabsf(x), ay = fabsf(y), az = fabsf(z);
+  int f;
+  float m, u, v;
+  if (ax >= ay && ax >= az) {
+    f = 0; m = x; u = y; v = z;
+  } else if (ay >= az) {
+    f = 1; m = y; u = z; v = x;
+  } else {
+    f = 2; m = z; u = x; v = y;
+  }
+  const float am = fabsf(m);
+#if defined(__HIP_DEVICE_COMPILE__)
+  const float inv = __builtin_amdgcn_rcpf(am);
+#else
+  const float inv = 1.0f / am;
+#endif
+  // fractional cell coordinates in [0, kShK]; a NaN (zero direction) clamps to 0
+  const float hk = 0.5f * kShK;
+  const float fu = fminf(fmaxf((u * inv + 1.0f) * hk, 0.f), (float)kShK);
+  const float fv = fminf(fmaxf((v * inv + 1.0f) * hk, 0.f), (float)kShK);
+  int iu = (int)fu, iv = (int)fv;
+  iu = iu > kShK - 1 ? kShK - 1 : iu;
+  iv = iv > kShK - 1 ? kShK - 1 : iv;
+  const float tu = fu - (float)iu, tv = fv - (float)iv;  // in [0, 1]
+  const P c = tab + ((2 * f + (m < 0.f ? 1 : 0)) * kShN + iu) * kShN + iv;
+  const float h00 = c[0], h01 = c[1], h10 = c[kShN], h11 = c[kShN + 1];
+  const float a = h00 + tv * (h01 - h00), b = h10 + tv * (h11 - h10);
+  return (a + tu * (b - a)) * am;
+}
+
+// The support-height axes of a pair the OBB SAT kept (ta, tb: the sides'
+// tables or SH_NONE; at least one table): along an axis w the shapes are
+// apart by at least w.(cB - cA) - hA(RA^T w) - hB(-RB^T w), so the pair is
+// dropped when that exceeds margin |w|.  Axes: the centre-to-centre direction,
+// then +-A's and +-B's box axes (|w| = 1).  Of +w and -w only the one with
+// w.(cB - cA) >= 0 can separate (heights and extents are >= 0), so each box
+// axis costs one lookup; the shape whose axis it is has its OBB extent as
+// height, and a partner without a table would repeat the SAT's axis.  No
+// early exit: the lookups of a side are independent and their loads overlap,
+// two lookups at a time (four in flight cost the cull kernel its fourth wave
+// per SIMD: 130 VGPRs).
+// margin = the cull margin + the pad of this evaluation.
+template <class P>
+MPG_INLINE bool bp_support_separated(const FObb& A, const FObb& B, int ta, int tb, P tab, float margin) {
+  MPG_FP32_CONTRACT
+  const float d[3] = {B.c[0] - A.c[0], B.c[1] - A.c[1], B.c[2] - A.c[2]};
+  float Rm[3][3], t[3], s[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) Rm[i][j] = A.R[i] * B.R[j] + A.R[3 + i] * B.R[3 + j] + A.R[6 + i] * B.R[6 + j];
+    t[i] = d[0] * A.R[i] + d[1] * A.R[3 + i] + d[2] * A.R[6 + i];
+    s[i] = d[0] * B.R[i] + d[1] * B.R[3 + i] + d[2] * B.R[6 + i];
+  }
+  const float dd = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+  float ha = A.e[0] * fabsf(t[0]) + A.e[1] * fabsf(t[1]) + A.e[2] * fabsf(t[2]);
+  float hb = B.e[0] * fabsf(s[0]) + B.e[1] * fabsf(s[1]) + B.e[2] * fabsf(s[2]);
+  bool sep = false;
+  if (ta >= 0) {  // A's table: the centre direction and B's box axes, in A's frame
+    const P tA = tab + (size_t)ta * kShFloats;
+    ha = bp_support_height(tA, t[0], t[1], t[2]);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      if (j == 1) MPG_SCHED_FENCE;
+      const float sg = s[j] < 0.f ? -1.f : 1.f;
+      const float h = bp_support_height(tA, sg * Rm[0][j], sg * Rm[1][j], sg * Rm[2][j]);
+      sep |= fabsf(s[j]) - h - B.e[j] > margin;
+    }
+  }
+  if (tb >= 0) {  // B's table: minus the centre direction and minus A's box axes, in B's frame
+    const P tB = tab + (size_t)tb * kShFloats;
+    hb = bp_support_height(tB, -s[0], -s[1], -s[2]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      if (i == 1) MPG_SCHED_FENCE;
+      const float sg = t[i] < 0.f ? 1.f : -1.f;
+      const float h = bp_support_height(tB, sg * Rm[i][0], sg * Rm[i][1], sg * Rm[i][2]);
+      sep |= fabsf(t[i]) - A.e[i] - h > margin;
+    }
+  }
+  sep |= dd - ha - hb > margin * sqrtf(dd);
+  return sep;
+}
+
+// ---------------------------------------------------------------------------
 // host: build the program from a world descriptor + the per-geometry local
 // OBB records (centre, half extents, bounding radius about that centre)
 // ---------------------------------------------------------------------------
@@ -435,6 +547,8 @@ struct BpProgram {
   int n_saves = 0;
   std::vector<int> jsrc, jsave, link_start, link_order, obj_start, obj_order, jkind, jobj_start, jobj_order;
   std::vector<float> jaxis, jplace, lplace, moff, mobj, sobj, oplace, oquat, ocen;
+  std::vector<float> shtab;  // support-height tables (bp_build_support)
+  std::vector<int> pair_sh;   // [n_pairs*2] the pair's tables (a side, b side), SH_NONE or SH_SKIP
 };
 
 // row-major 3x4 product in fp64 (host program folding)
@@ -608,6 +722,56 @@ inline void bp_build(const mpg_world_desc* d, const std::vector<double>& obb, Bp
   }
 }
 
+// One hull's support-height table: for face 2 f + s (f: the axis of the largest
+// component, s: its sign) and grid corner (i, j) the height along (+-1, u_i,
+// v_j), fp64 over every vertex about the centre c, rounded up (widen; a
+// negative height -- c outside the hull -- becomes its absolute value, still
+// an upper bound)
+inline void bp_support_table(const double* V, int nv, const double* c, float* tab) {
+  for (int f = 0; f < 3; ++f)
+    for (int sgn = 0; sgn < 2; ++sgn)
+      for (int i = 0; i < kShN; ++i)
+        for (int j = 0; j < kShN; ++j) {
+          double dir[3];
+          dir[f] = sgn ? -1.0 : 1.0;
+          dir[(f + 1) % 3] = -1.0 + 2.0 * i / kShK;
+          dir[(f + 2) % 3] = -1.0 + 2.0 * j / kShK;
+          double h = -INFINITY;
+          for (int k = 0; k < nv; ++k)
+            h = std::max(h, (V[3 * k] - c[0]) * dir[0] + (V[3 * k + 1] - c[1]) * dir[1] + (V[3 * k + 2] - c[2]) * dir[2]);
+          tab[((2 * f + sgn) * kShN + i) * kShN + j] = widen(h);
+        }
+}
+
+// tables of every convex hull an object uses, and per pair its sides' tables:
+// SH_NONE for the shapes whose OBB height is used (boxes: exact), SH_SKIP for
+// pairs without any table or with a BVH mesh or an octree
+inline void bp_build_support(const mpg_world_desc* d, const std::vector<double>& obb, BpProgram& P) {
+  std::vector<int> gtab(std::max(d->n_geoms, 1), SH_NONE);
+  auto table_of = [&](int g) {
+    const int t = d->geom_type[g];
+    if (t == MPG_GEOM_MESH || t == MPG_GEOM_OCTREE) return (int)SH_SKIP;
+    if (t != MPG_GEOM_CONVEX || d->geom_vertex_count[g] <= 0) return (int)SH_NONE;
+    if (gtab[g] < 0) {
+      gtab[g] = (int)(P.shtab.size() / kShFloats);
+      P.shtab.resize(P.shtab.size() + kShFloats);
+      bp_support_table(d->vertices + 3 * (size_t)d->geom_vertex_start[g], d->geom_vertex_count[g], obb.data() + 7 * g,
+                       P.shtab.data() + (size_t)gtab[g] * kShFloats);
+    }
+    return gtab[g];
+  };
+  auto geom_of = [&](int id) { return id < d->n_moving ? d->moving_geom[id] : d->static_geom[id - d->n_moving]; };
+  P.pair_sh.assign(2 * (size_t)std::max(d->n_pairs, 1), SH_SKIP);
+  for (int p = 0; p < d->n_pairs; ++p) {
+    if (d->pair_allowed && d->pair_allowed[p]) continue;
+    const int ta = table_of(geom_of(d->pair_a[p])), tb = table_of(geom_of(d->pair_b[p]));
+    if (ta == SH_SKIP || tb == SH_SKIP || (ta < 0 && tb < 0)) continue;
+    P.pair_sh[2 * p] = ta;
+    P.pair_sh[2 * p + 1] = tb;
+  }
+  if (P.shtab.empty()) P.shtab.assign(kShFloats, 0.f);
+}
+
 inline BpView bp_view(const mpg_world_desc* d, const BpProgram& P) {
   BpView b{};
   b.nj = d->n_joints;
@@ -637,6 +801,7 @@ inline BpView bp_view(const mpg_world_desc* d, const BpProgram& P) {
   b.oplace = to_cptr<float>(P.oplace.data());
   b.oquat = to_cptr<float>(P.oquat.data());
   b.ocen = to_cptr<float>(P.ocen.data());
+  b.shtab = to_cptr<float>(P.shtab.data());
   return b;
 }
 

@@ -26,6 +26,7 @@ struct DevWorld {
   int nj, dof, n_links, n_geoms, n_moving, n_static, n_pairs, W;
   double mpr_tol;
   float bp_margin;      // phase-A culling margin (metres), kBpMargin or the libccd false-hit reach
+  float sh_margin;      // bp_margin + the pad of the support-height axes' fp32 evaluation
   double small_margin;  // the latency path's bounding-sphere margin, same rule
   int debug_mode;  // diagnostics only: 1 = broad-phase records only, 2 = no SAT stage, 3 = no MPR (latency path: no narrow test), 5 / 6 = no mesh-mesh / mesh-shape walks, 7 = latency path: FK + sphere test only
   unsigned long long* stats;  // diagnostics only (MPG_STATS=1), else NULL
@@ -100,6 +101,7 @@ struct DevWorld {
   cptr<int> sched_start;  // [n_moving+1]
   cptr<int> sched_pair;
   cptr<int> sched_other;
+  cptr<int> sched_rec;    // [entries * SR_STRIDE] (mpg_broadphase.h)
   cptr<int> st_start;     // [2 * (n_static + 1)]
   cptr<int> st_m;         // [entries]
   cptr<float> st_r;       // [entries]

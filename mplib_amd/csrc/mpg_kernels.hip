@@ -1073,23 +1073,67 @@ __device__ __forceinline__ FObb bp_obb(const DevWorld& w, const float* __restric
   return o;
 }
 
+// The support-height axes (mpg_broadphase.h bp_support_separated) on cnt SAT
+// survivors, one (schedule entry, lane) per lane: the pairs they do not
+// separate either are the candidates.
+template <int BLOCK>
+__device__ __forceinline__ void support_drain(const DevWorld& w, const float* __restrict__ cen, const float* __restrict__ rq,
+                                           long long cap, long long cfg0, uint32_t* survw, uint32_t e, uint32_t cnt,
+                                           int wbase, uint32_t lane) {
+  if (lane < cnt) {
+    const cptr<int> r = w.sched_rec + SR_STRIDE * (int)(e >> 6);
+    const int p = r[SR_P], sh = r[SR_SH], t = wbase + (int)(e & 63u);
+    const FObb A = bp_obb<BLOCK>(w, cen, rq, cap, r[SR_A], t, cfg0 + t);
+    const FObb B = bp_obb<BLOCK>(w, cen, rq, cap, r[SR_B], t, cfg0 + t);
+    if (!bp_support_separated(A, B, (sh & 0xffff) - 2, (sh >> 16) - 2, w.bp.shtab, w.sh_margin))
+      atomicOr(&survw[(p >> 5) * BLOCK + t], 1u << (p & 31));
+  }
+}
+
 template <int BLOCK>
 __device__ __forceinline__ void sat_drain(const DevWorld& w, const float* __restrict__ cen, const float* __restrict__ rq,
                                           long long cap, long long cfg0, uint32_t* survw, const uint32_t* queue,
-                                          uint32_t head, uint32_t cnt, int wbase, uint32_t lane) {
+                                          uint32_t head, uint32_t cnt, int wbase, uint32_t lane, uint32_t& pend,
+                                          uint32_t& npend) {
   __builtin_amdgcn_wave_barrier();
+  uint32_t e = 0u;
+  bool keep = false;
   if (lane < cnt) {
-    const uint32_t e = queue[(head + lane) & (kQueue - 1)];  // (schedule entry, lane)
-    const int p = w.sched_pair[(int)(e >> 6)], t = wbase + (int)(e & 63u);
-    const FObb A = bp_obb<BLOCK>(w, cen, rq, cap, w.pair_a[p], t, cfg0 + t);
-    const FObb B = bp_obb<BLOCK>(w, cen, rq, cap, w.pair_b[p], t, cfg0 + t);
-    if (!fobb_separated(A, B, w.bp_margin)) atomicOr(&survw[(p >> 5) * BLOCK + t], 1u << (p & 31));
+    e = queue[(head + lane) & (kQueue - 1)];  // (schedule entry, lane)
+    const cptr<int> r = w.sched_rec + SR_STRIDE * (int)(e >> 6);
+    const int p = r[SR_P], sh = r[SR_SH], t = wbase + (int)(e & 63u);
+    const FObb A = bp_obb<BLOCK>(w, cen, rq, cap, r[SR_A], t, cfg0 + t);
+    const FObb B = bp_obb<BLOCK>(w, cen, rq, cap, r[SR_B], t, cfg0 + t);
+    if (!fobb_separated(A, B, w.bp_margin)) {
+      if ((sh & 0xffff) == SH_SKIP + 2) atomicOr(&survw[(p >> 5) * BLOCK + t], 1u << (p & 31));
+      else keep = true;
+    }
+  }
+  // SAT survivors with a support-height table wait in `pend` (one entry per
+  // lane, lanes [0, npend)) until 64 of them fill a wave: the survivors move
+  // to the lanes after the pending ones (a forward lane permute, no LDS
+  // storage; the other lanes take the remaining targets so that the targets
+  // are a permutation), wrapping to lane 0 once a full wave has been tested
+  const unsigned long long bal = __ballot(keep);
+  const uint32_t ns = (uint32_t)__popcll(bal);
+  if (ns) {
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+    const uint32_t dst = keep ? npend + rank : npend + ns + (lane - rank);
+    const uint32_t recv = (uint32_t)__builtin_amdgcn_ds_permute((int)((dst & 63u) << 2), (int)e);
+    if (npend + ns >= 64u) {
+      support_drain<BLOCK>(w, cen, rq, cap, cfg0, survw, lane >= npend ? recv : pend, 64, wbase, lane);
+      pend = recv;
+      npend = npend + ns - 64u;
+    } else {
+      if (lane >= npend && lane < npend + ns) pend = recv;
+      npend += ns;
+    }
   }
   __builtin_amdgcn_wave_barrier();
 }
 
 template <int BLOCK, bool FROM_POSES>
-__global__ __launch_bounds__(BLOCK) void cull_kernel(DevWorld w, const double* __restrict__ in, long long n,
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) void cull_kernel(DevWorld w, const double* __restrict__ in, long long n,
                                                     uint8_t* __restrict__ flags, uint32_t* __restrict__ masks,
                                                     uint32_t* __restrict__ surv, float* __restrict__ rq,
                                                     double* __restrict__ sc, long long cap,
@@ -1194,6 +1238,7 @@ __global__ __launch_bounds__(BLOCK) void cull_kernel(DevWorld w, const double* _
   }
 
   uint32_t head = 0, tail = 0;  // wave-uniform queue cursors
+  uint32_t pend = 0u, npend = 0u;  // SAT survivors waiting for the support-height axes (sat_drain)
   uint32_t dbg_keep = 0u;       // diagnostics (11): the bounding tests' bits, kept alive
   // queue the entries [eb, eb + 32) some lane kept (kb: this lane's bits);
   // drain 64 queued (pair, lane) entries through the SAT at a time
@@ -1234,7 +1279,7 @@ __global__ __launch_bounds__(BLOCK) void cull_kernel(DevWorld w, const double* _
       }
       tail += total;
       while (tail - head >= 64) {
-        sat_drain<BLOCK>(w, cen, rq, cap, cfg0, survw, queue, head, 64, wbase, lane);
+        sat_drain<BLOCK>(w, cen, rq, cap, cfg0, survw, queue, head, 64, wbase, lane, pend, npend);
         head += 64;
       }
       return;
@@ -1257,7 +1302,7 @@ __global__ __launch_bounds__(BLOCK) void cull_kernel(DevWorld w, const double* _
       }
       tail += (uint32_t)__popcll(bal);
       if (tail - head >= 64) {
-        sat_drain<BLOCK>(w, cen, rq, cap, cfg0, survw, queue, head, 64, wbase, lane);
+        sat_drain<BLOCK>(w, cen, rq, cap, cfg0, survw, queue, head, 64, wbase, lane, pend, npend);
         head += 64;
       }
     }
@@ -1315,7 +1360,9 @@ __global__ __launch_bounds__(BLOCK) void cull_kernel(DevWorld w, const double* _
       push(eb, kb);
     }
   }
-  if (tail != head) sat_drain<BLOCK>(w, cen, rq, cap, cfg0, survw, queue, head, tail - head, wbase, lane);
+  if (tail != head) sat_drain<BLOCK>(w, cen, rq, cap, cfg0, survw, queue, head, tail - head, wbase, lane, pend, npend);
+  if (npend) support_drain<BLOCK>(w, cen, rq, cap, cfg0, survw, pend, npend, wbase, lane);
+  __builtin_amdgcn_wave_barrier();
   if (forced)
     for (int k = 0; k < w.W; ++k) survw[k * BLOCK + tid] = (uint32_t)w.all_mask[k];
   if (w.dbg(8) || w.dbg(11)) {  // ablation: bounding tests + SAT only (11: without the queue and SAT)
