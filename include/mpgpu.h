@@ -791,6 +791,19 @@ int mpg_debug_sincos(const double *x, int64_t n, double *s, double *c, int devic
 int mpg_latency_server_stats(mpg_world *world, int64_t *served, int64_t *starts, int64_t *fallbacks,
                              int32_t *state);
 
+/*
+ * The lookup grids of the joint-value cull: how many
+ * moving objects have one, the cells of all grids together, whether the words
+ * have been built yet (the first bulk launch with joint-value input does
+ * that; world creation and the latency path do not) and the cell edge in
+ * metres.  For the first cap gridded objects: the moving object, its number
+ * of static partners, and the grid's box as (lo x y z, hi x y z), the region
+ * inside which a centre is looked up.  Any output pointer may be NULL.  No
+ * reference counterpart (diagnostics).
+ */
+int mpg_cull_grid_info(const mpg_world *world, int32_t *objects, int64_t *cells, int32_t *built, double *cell_edge,
+                       int32_t cap, int32_t *object, int32_t *partners, double *box);
+
 /* Synchronise the world's device (used after MPG_MEM_DEVICE calls). */
 int mpg_synchronize(int device);
 

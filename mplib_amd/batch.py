@@ -132,6 +132,23 @@ class DeviceWorld:
         """Host batches of at most n configurations take the one-launch latency path (0 disables)."""
         C.check(C.lib().mpg_set_small_batch_max(self._h, int(n)), "mpg_set_small_batch_max")
 
+    def cull_grid_info(self) -> dict:
+        """The cull's lookup grids (mpg_cull_grid_info): ``objects`` (moving
+        object ids), ``partners`` per object, ``box`` [objects, 6] (lo, hi),
+        ``cells``, ``cell_edge`` and ``built`` (the first bulk call builds them)."""
+        n, cells, built = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int32(0)
+        edge = ctypes.c_double(0.0)
+        L = C.lib()
+        C.check(L.mpg_cull_grid_info(self._h, ctypes.byref(n), ctypes.byref(cells), ctypes.byref(built),
+                                     ctypes.byref(edge), 0, None, None, None), "mpg_cull_grid_info")
+        obj = np.zeros(n.value, np.int32)
+        part = np.zeros(n.value, np.int32)
+        box = np.zeros((n.value, 6))
+        C.check(L.mpg_cull_grid_info(self._h, None, None, None, None, n.value, obj.ctypes.data_as(ctypes.c_void_p),
+                                     part.ctypes.data_as(ctypes.c_void_p), box.ctypes.data_as(ctypes.c_void_p)),
+                "mpg_cull_grid_info")
+        return dict(objects=obj, partners=part, box=box, cells=cells.value, cell_edge=edge.value, built=bool(built.value))
+
     def release_stream(self, stream: int):
         """Drop the workspace / side stream kept for a caller stream (call before destroying it)."""
         C.check(C.lib().mpg_release_stream(self._h, ctypes.c_void_p(int(stream))), "mpg_release_stream")

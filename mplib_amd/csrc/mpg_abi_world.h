@@ -98,6 +98,22 @@ int mpg_latency_server_stats(mpg_world* w, int64_t* served, int64_t* starts, int
   return MPG_OK;
 }
 
+int mpg_cull_grid_info(const mpg_world* w, int32_t* objects, int64_t* cells, int32_t* built, double* cell_edge,
+                       int32_t cap, int32_t* object, int32_t* partners, double* box) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  const mpg_world::GridInfo& g = w->grid_info;
+  if (objects) *objects = (int32_t)g.object.size();
+  if (cells) *cells = g.cells;
+  if (built) *built = w->grid_ready.load(std::memory_order_acquire) ? 1 : 0;
+  if (cell_edge) *cell_edge = g.h;
+  for (int32_t i = 0; i < cap && i < (int32_t)g.object.size(); ++i) {
+    if (object) object[i] = g.object[i];
+    if (partners) partners[i] = g.partners[i];
+    if (box) std::copy(g.box.begin() + 6 * i, g.box.begin() + 6 * i + 6, box + 6 * i);
+  }
+  return MPG_OK;
+}
+
 int mpg_synchronize(int device) {
   HIP_TRY(hipSetDevice(device));
   HIP_TRY(hipDeviceSynchronize());
@@ -511,6 +527,7 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
   // margin from that ball can never be a candidate: its schedule entry is
   // kept only for the link-pose input, whose poses are not kinematic.
   std::vector<std::array<double, 4>> ball(std::max(d->n_moving, 1));  // centre, radius (object radius included)
+  std::vector<double> ball_rc(std::max(d->n_moving, 1), 0.0);          // the same without it: the centre's reach
   for (int m = 0; m < d->n_moving; ++m) {
     const int l = d->moving_link[m];
     const double* g = geom_rec.data() + G_STRIDE * d->moving_geom[m];
@@ -534,6 +551,7 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
       R += std::sqrt(sq3(d->joint_placement + 12 * j + 9)) + travel[j];
     }
     ball[m] = {p1[0], p1[1], p1[2], R * (1.0 + 1e-9) + 1e-9};
+    ball_rc[m] = (R - g[G_RADIUS]) * (1.0 + 1e-9) + 1e-9;
   }
   auto never_near = [&](int m, int sid) {  // exact fp64 distance, reach ball vs the static OBB
     const double* sr = static_rec.data() + (size_t)S_STRIDE * sid;
@@ -588,6 +606,79 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
         }
     }
     st_start[g * (ns + 1) + ns] = (int)sched_pair.size();
+  }
+  // Lookup grids of the joint-value cull (mpg_broadphase.h bp_grid_*): a
+  // link-borne object with kGridMinPartners..kGridMaxPartners group-0 static partners is a
+  // candidate, its box the cube around its reach ball's centre (the centre's
+  // reach, without the object's radius, plus the fp32 centre error);
+  // bp_grid_choose keeps those that fit the cell budget.  Their group-0
+  // entries are repeated object-major after the schedule above, then those of
+  // the other objects static-major (gst_start); the link-pose input keeps
+  // st_start.  A world where no object has a grid adds nothing, and a world
+  // with free frames has none: its joint-value rows go through link poses
+  // (launch_collide_free), so the joint-value cull never runs for it.
+  BpGridPlan gplan;
+  std::vector<int> gst_start, grid_i;
+  std::vector<float> grid_f;
+  {
+    const double slack = kFp32CullRel * X + 1e-6;
+    for (int m = 0; m < d->n_moving && n_free == 0; ++m) {
+      BpGridObj o;
+      o.m = m;
+      o.r = (double)bpp.mobj[BM_STRIDE * m + BM_R];
+      for (int k = 0; k < 3; ++k) {
+        o.lo[k] = ball[m][k] - (ball_rc[m] + slack);
+        o.hi[k] = ball[m][k] + (ball_rc[m] + slack);
+      }
+      for (int sid = 0; sid < ns; ++sid)
+        for (int p = 0; p < d->n_pairs; ++p) {
+          if (allowed[p]) continue;
+          const int a = d->pair_a[p], b = d->pair_b[p];
+          if (std::min(a, b) != m || std::max(a, b) != d->n_moving + sid || never_near(m, sid)) continue;
+          o.sid.push_back(sid);
+          o.pair.push_back(p);
+        }
+      if (bp_grid_candidate(o.sid.size())) gplan.obj.push_back(std::move(o));
+    }
+    bp_grid_choose(gplan, X, (double)bp_margin);
+  }
+  if (!gplan.obj.empty()) {
+    std::vector<char> gridded(d->n_moving, 0);
+    std::vector<int> E;
+    for (const BpGridObj& o : gplan.obj) {
+      gridded[o.m] = 1;
+      E.push_back((int)sched_pair.size());
+      for (size_t k = 0; k < o.sid.size(); ++k) {
+        sched_pair.push_back(o.pair[k]);
+        sched_other.push_back(d->n_moving + o.sid[k]);
+        st_m.push_back(o.m);
+        st_r.push_back(bpp.mobj[BM_STRIDE * o.m + BM_R]);
+      }
+    }
+    E.push_back((int)sched_pair.size());
+    bp_grid_records(gplan, E, grid_f, grid_i);
+    gst_start.assign(ns + 1, 0);
+    for (int sid = 0; sid < ns; ++sid) {
+      gst_start[sid] = (int)sched_pair.size();
+      for (int m = 0; m < d->n_moving; ++m)
+        for (int p = 0; p < d->n_pairs && !gridded[m]; ++p) {
+          if (allowed[p]) continue;
+          const int a = d->pair_a[p], b = d->pair_b[p];
+          if (std::min(a, b) != m || std::max(a, b) != d->n_moving + sid || never_near(m, sid)) continue;
+          sched_pair.push_back(p);
+          sched_other.push_back(d->n_moving + sid);
+          st_m.push_back(m);
+          st_r.push_back(bpp.mobj[BM_STRIDE * m + BM_R]);
+        }
+    }
+    gst_start[ns] = (int)sched_pair.size();
+    gplan.sobb.assign((size_t)15 * ns, 0.0);
+    for (int sid = 0; sid < ns; ++sid) {
+      const float* r = bpp.sobj.data() + BS_STRIDE * sid;
+      double* S = gplan.sobb.data() + 15 * (size_t)sid;
+      for (int k = 0; k < 3; ++k) S[k] = r[BS_C + k], S[12 + k] = r[BS_E + k];
+      for (int k = 0; k < 9; ++k) S[3 + k] = r[BS_R + k];
+    }
   }
   if (sched_pair.empty()) {
     sched_pair.push_back(0);
@@ -698,6 +789,10 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
   for (int m = 0; m < d->n_moving; ++m)
     if (d->moving_link[m] >= d->n_links - n_free) free_obj[d->moving_link[m] - (d->n_links - n_free)] = m;
   const size_t o_fob = n_free ? bb.add(free_obj.data(), free_obj.size()) : 0;
+  const bool has_grid = !gplan.obj.empty();
+  const size_t o_ggf = has_grid ? bb.add(grid_f.data(), grid_f.size()) : 0;
+  const size_t o_ggi = has_grid ? bb.add(grid_i.data(), grid_i.size()) : 0;
+  const size_t o_gst = has_grid ? bb.add(gst_start.data(), gst_start.size()) : 0;
 
   std::unique_ptr<mpg_world> w(new mpg_world());  // every failure below releases what was built
   w->device = device;
@@ -843,6 +938,19 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
   dw.st_start = I(o_sts);
   dw.st_m = I(o_stm);
   dw.st_r = to_cptr<float>(base + o_str);
+  dw.n_grid = has_grid ? (int)(grid_i.size() / GI_STRIDE) : 0;
+  dw.grid_f = to_cptr<float>(base + o_ggf);
+  dw.grid_i = I(o_ggi);
+  dw.gst_start = I(o_gst);
+  for (const BpGridObj& o : gplan.obj) {
+    w->grid_info.object.push_back(o.m);
+    w->grid_info.partners.push_back((int)o.sid.size());
+    for (int k = 0; k < 3; ++k) w->grid_info.box.push_back((double)o.o[k]);
+    for (int k = 0; k < 3; ++k) w->grid_info.box.push_back((double)o.o[k] + o.n[k] * gplan.h);
+  }
+  w->grid_info.cells = has_grid ? gplan.cells : 0;
+  w->grid_info.h = has_grid ? gplan.h : 0.0;
+  w->grid_plan = std::move(gplan);
   auto F = [&](size_t o) { return to_cptr<float>(base + o); };
   BpView& bp = dw.bp;
   bp.nj = d->n_joints;

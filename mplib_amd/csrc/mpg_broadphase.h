@@ -805,4 +805,191 @@ inline BpView bp_view(const mpg_world_desc* d, const BpProgram& P) {
   return b;
 }
 
+// ---------------------------------------------------------------------------
+// Lookup grids for the moving-static bounding tests of the joint-value input.
+// Whether a moving object's bounding sphere comes within the cull margin of a
+// static OBB depends on the sphere's centre alone, and the statics never move:
+// per gridded object a uniform grid over the box its centre can reach holds
+// one word per cell, bit k set unless static partner k is provably farther
+// than radius + margin + pad from every point of the padded cell (fp64, a
+// lower bound of the very distance fsphere_obb_separated evaluates).  The
+// cull then loads one word per object instead of testing every partner; a
+// centre outside the box (or NaN) takes every partner, so nothing rests on the
+// reach bound.  DESIGN.md §5 has the argument for the pads.
+// ---------------------------------------------------------------------------
+constexpr int kGridMaxPartners = 32;          // bits of a cell word
+// fewer partners than this stay in the loop: a gathered load, its index
+// arithmetic and the looser keeps cost more than a handful of sphere tests
+// (cfg4, four statics per object: 1.1 % slower with grids)
+constexpr int kGridMinPartners = 6;
+constexpr long long kGridBudget = 1ll << 19;  // cells of all grids together: 2 MiB, half an XCD's L2
+constexpr double kGridMinH = 0.02;            // cell edge floor (metres): a tiny world gains nothing below it
+constexpr double kGridMaxH = 0.08;            // above it the lookup keeps too much: the largest box goes back to the loop
+constexpr int kGridBlock = 8;                 // the builder tests blocks of kGridBlock^3 cells first
+constexpr int kGridGroup = 4;                 // objects whose words the cull loads together (records padded to it)
+// per gridded object: floats (origin, 1 / h, the dimensions as floats) and
+// ints (object, nx, ny, first cell, first schedule entry, partners, their bits)
+enum { GF_O = 0, GF_INVH = 3, GF_N = 4, GF_STRIDE = 8 };
+enum { GI_M = 0, GI_NX = 1, GI_NY = 2, GI_CELL0 = 3, GI_E = 4, GI_NP = 5, GI_FULL = 6, GI_STRIDE = 8 };
+
+// the cell of centre c, or -1 outside the grid (NaN compares false); what
+// the cull kernel runs per lane, and the host tests replay
+template <class PF, class PI>
+MPG_INLINE int bp_grid_cell(PF gf, PI gi, const float* c) {
+  const float inv = gf[GF_INVH];
+  const float fx = (c[0] - gf[GF_O]) * inv, fy = (c[1] - gf[GF_O + 1]) * inv, fz = (c[2] - gf[GF_O + 2]) * inv;
+  const bool in = fx >= 0.f && fx < gf[GF_N] && fy >= 0.f && fy < gf[GF_N + 1] && fz >= 0.f && fz < gf[GF_N + 2];
+  const int ix = in ? (int)fx : 0, iy = in ? (int)fy : 0, iz = in ? (int)fz : 0;
+  return in ? gi[GI_CELL0] + (iz * gi[GI_NY] + iy) * gi[GI_NX] + ix : -1;
+}
+
+struct BpGridObj {
+  int m = 0;                    // moving object
+  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // box of the centre's reach
+  double r = 0.0;               // bounding radius, as the sphere test takes it
+  std::vector<int> sid, pair;   // partner k: static sid[k], pair pair[k] (schedule entry E + k)
+  int n[3] = {1, 1, 1};
+  float o[3] = {0.f, 0.f, 0.f};
+  long long cell0 = 0;
+};
+struct BpGridPlan {
+  std::vector<BpGridObj> obj;
+  std::vector<double> sobb;  // per static: OBB centre, axes (row-major, column k = axis k), extents, as the fp32 record holds them
+  double h = 0.0;            // cell edge: 1 / inv_h exactly
+  float inv_h = 0.f;
+  double thr_pad = 0.0;      // cull margin + pad, added to the object's radius
+  double cell_pad = 0.0;     // a cell is tested widened by this on every side (fp32 index rounding)
+  long long cells = 0;
+};
+
+inline bool bp_grid_candidate(size_t partners) { return partners >= (size_t)kGridMinPartners && partners <= (size_t)kGridMaxPartners; }
+
+// The layout for cell edge h: the stored 1 / h and its exact reciprocal, each
+// grid's origin (the box's corner as a float), dimensions and first cell.
+// Returns the cells of all grids together, which is what the budget bounds; a
+// grid counts as budget + 1 cells at most, so the sum cannot overflow (such a
+// layout is never used: its total is over the budget).
+inline long long bp_grid_layout(BpGridPlan& G, double h, long long budget) {
+  G.inv_h = (float)(1.0 / h);
+  G.h = 1.0 / (double)G.inv_h;
+  G.cells = 0;
+  for (BpGridObj& o : G.obj) {
+    o.cell0 = G.cells;
+    long long c = 1;
+    for (int k = 0; k < 3; ++k) {
+      o.o[k] = (float)o.lo[k];
+      o.n[k] = (int)std::min(1048576.0, std::max(1.0, std::ceil((o.hi[k] - (double)o.o[k]) / G.h)));
+      c = std::min(c * o.n[k], budget + 1);
+    }
+    G.cells += c;
+  }
+  return G.cells;
+}
+
+// Which of the candidates keep a grid, and the shared cell edge: the smallest
+// edge from kGridMinH up (steps of 1/16, none above kGridMaxH) whose layout
+// fits the budget; while there is none the candidate with the largest box
+// leaves (the first of equals).  Depends on its inputs alone.
+inline void bp_grid_choose(BpGridPlan& G, double coord_bound, double margin, long long budget = kGridBudget) {
+  auto vol = [](const BpGridObj& o) { return (o.hi[0] - o.lo[0]) * (o.hi[1] - o.lo[1]) * (o.hi[2] - o.lo[2]); };
+  for (bool fits = false; !fits && !G.obj.empty();) {
+    for (double h = kGridMinH; h <= kGridMaxH && !fits; h *= 1.0625) fits = bp_grid_layout(G, h, budget) <= budget;
+    if (fits) break;
+    size_t big = 0;
+    for (size_t i = 1; i < G.obj.size(); ++i)
+      if (vol(G.obj[i]) > vol(G.obj[big])) big = i;
+    G.obj.erase(G.obj.begin() + big);
+  }
+  if (G.obj.empty()) bp_grid_layout(G, kGridMinH, budget);
+  int nmax = 1;
+  for (const BpGridObj& o : G.obj) nmax = std::max(nmax, std::max(o.n[0], std::max(o.n[1], o.n[2])));
+  // the fp32 evaluation of the sphere test and the fp32 centre (kFp32CullRel
+  // of the coordinate bound, as the cull margin itself); the index (c - o) *
+  // inv_h carries two roundings of a value below nmax: 2^-22 nmax cells
+  G.thr_pad = margin + kFp32CullRel * coord_bound + 1e-9;
+  G.cell_pad = G.h * nmax * 3e-7 + kFp32CullRel * coord_bound;
+}
+
+// lower bound of the sphere test's distance sqrt(sum_k max(|t_k| - E_k, 0)^2)
+// over the axis-aligned box (centre q, half sizes a): the box's extent along
+// each OBB axis taken off |t_k|, or the distance at q minus the half diagonal
+inline double bp_grid_gap(const double* q, const double* a, const double* S) {
+  double g2 = 0.0, d2 = 0.0;
+  for (int k = 0; k < 3; ++k) {
+    double t = 0.0, w = 0.0;
+    for (int i = 0; i < 3; ++i) {
+      t += (q[i] - S[i]) * S[3 + 3 * i + k];
+      w += a[i] * std::fabs(S[3 + 3 * i + k]);
+    }
+    const double g = std::max(std::fabs(t) - w - S[12 + k], 0.0), ex = std::max(std::fabs(t) - S[12 + k], 0.0);
+    g2 += g * g;
+    d2 += ex * ex;
+  }
+  // (the rounded axes are orthonormal to 1e-7: the Lipschitz bound takes 1e-6 of slack)
+  return std::max(std::sqrt(g2), std::sqrt(d2) - std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]) * (1.0 + 1e-6));
+}
+
+// the words of every grid, coarse to fine: blocks of kGridBlock^3 cells far
+// from every partner stay zero, the others test their cells against the
+// partners near the block
+inline void bp_grid_fill(const BpGridPlan& G, std::vector<uint32_t>& words) {
+  words.assign((size_t)std::max(G.cells, 1ll), 0u);
+  for (const BpGridObj& o : G.obj) {
+    const int np = (int)o.sid.size();
+    const double thr = o.r + G.thr_pad;
+    int near[kGridMaxPartners];
+    for (int bz = 0; bz < o.n[2]; bz += kGridBlock)
+      for (int by = 0; by < o.n[1]; by += kGridBlock)
+        for (int bx = 0; bx < o.n[0]; bx += kGridBlock) {
+          const int b0[3] = {bx, by, bz};
+          int b1[3];
+          double q[3], a[3];
+          for (int k = 0; k < 3; ++k) {
+            b1[k] = std::min(b0[k] + kGridBlock, o.n[k]);
+            q[k] = (double)o.o[k] + 0.5 * (b0[k] + b1[k]) * G.h;
+            a[k] = 0.5 * (b1[k] - b0[k]) * G.h + G.cell_pad;
+          }
+          int nn = 0;
+          for (int k = 0; k < np; ++k)
+            if (!(bp_grid_gap(q, a, G.sobb.data() + 15 * (size_t)o.sid[k]) > thr)) near[nn++] = k;
+          if (nn == 0) continue;
+          const double ac[3] = {0.5 * G.h + G.cell_pad, 0.5 * G.h + G.cell_pad, 0.5 * G.h + G.cell_pad};
+          for (int iz = b0[2]; iz < b1[2]; ++iz)
+            for (int iy = b0[1]; iy < b1[1]; ++iy)
+              for (int ix = b0[0]; ix < b1[0]; ++ix) {
+                const double qc[3] = {(double)o.o[0] + (ix + 0.5) * G.h, (double)o.o[1] + (iy + 0.5) * G.h,
+                                      (double)o.o[2] + (iz + 0.5) * G.h};
+                uint32_t wd = 0u;
+                for (int j = 0; j < nn; ++j)
+                  if (!(bp_grid_gap(qc, ac, G.sobb.data() + 15 * (size_t)o.sid[near[j]]) > thr)) wd |= 1u << near[j];
+                words[(size_t)(o.cell0 + ((long long)iz * o.n[1] + iy) * o.n[0] + ix)] = wd;
+              }
+        }
+  }
+}
+
+// the records the cull reads, padded to a multiple of kGridGroup with empty
+// ones (no cells: every centre is outside, no partners: no bits); E[i] = the
+// first schedule entry of object i's partners
+inline void bp_grid_records(const BpGridPlan& G, const std::vector<int>& E, std::vector<float>& gf, std::vector<int>& gi) {
+  const size_t n = (G.obj.size() + kGridGroup - 1) / kGridGroup * kGridGroup;
+  gf.assign(n * GF_STRIDE, 0.f);
+  gi.assign(n * GI_STRIDE, 0);
+  for (size_t i = 0; i < G.obj.size(); ++i) {
+    const BpGridObj& o = G.obj[i];
+    float* f = gf.data() + GF_STRIDE * i;
+    int* r = gi.data() + GI_STRIDE * i;
+    for (int k = 0; k < 3; ++k) f[GF_O + k] = o.o[k], f[GF_N + k] = (float)o.n[k];
+    f[GF_INVH] = G.inv_h;
+    r[GI_M] = o.m;
+    r[GI_NX] = o.n[0];
+    r[GI_NY] = o.n[1];
+    r[GI_CELL0] = (int)o.cell0;
+    r[GI_E] = E[i];
+    r[GI_NP] = (int)o.sid.size();
+    r[GI_FULL] = (int)(o.sid.size() >= 32 ? ~0u : (1u << o.sid.size()) - 1u);
+  }
+  for (size_t i = G.obj.size(); i < n; ++i) gi[GI_STRIDE * i + GI_E] = E.empty() ? 0 : E.back();
+}
+
 }  // namespace mpg

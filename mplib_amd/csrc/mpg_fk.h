@@ -105,7 +105,18 @@ struct DevWorld {
   cptr<int> st_start;     // [2 * (n_static + 1)]
   cptr<int> st_m;         // [entries]
   cptr<float> st_r;       // [entries]
-  int n_prism;              // prismatic move-group joints with a value bound (a configuration beyond it: every pair)
+  // lookup grids of the joint-value cull (mpg_broadphase.h bp_grid_*): the
+  // group-0 entries of gridded object i are again entries [E_i, E_i + np_i)
+  // after all the above, object-major and contiguous over the objects (bit k
+  // of its cell word = entry E_i + k), and those of the other objects again
+  // static-major after them, by gst_start as by st_start.  The words
+  // themselves are a kernel argument (mpg_world::grid_words, built by the
+  // first bulk launch); without them the kernel walks group 0 of st_start.
+  int n_grid;             // records, a multiple of kGridGroup; 0 = no object has a grid
+  cptr<float> grid_f;     // [n_grid * GF_STRIDE]
+  cptr<int> grid_i;       // [n_grid * GI_STRIDE]
+  cptr<int> gst_start;    // [n_static + 1]
+  int n_prism;             // prismatic move-group joints with a value bound (a configuration beyond it: every pair)
   cptr<double> prism_bound; // [nj] |q| bound of such a joint, 0 = none
   double pose_bound;        // link-pose input: |position| bound of every link (beyond it: every pair)
   cptr<int> all_mask;       // [W] bits of every non-allowed pair

@@ -1137,7 +1137,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) v
                                                     uint8_t* __restrict__ flags, uint32_t* __restrict__ masks,
                                                     uint32_t* __restrict__ surv, float* __restrict__ rq,
                                                     double* __restrict__ sc, long long cap,
-                                                    uint32_t* __restrict__ cnt, int n_tiles) {
+                                                    uint32_t* __restrict__ cnt, int n_tiles,
+                                                    const uint32_t* __restrict__ grid) {
   extern __shared__ __attribute__((aligned(16))) float lds_f[];
   float* cen = lds_f;                                                    // [n_moving][3][BLOCK]
   float* save = cen + (size_t)w.n_moving * 3 * BLOCK;  // [n_saves - kRegSaves][12][BLOCK]
@@ -1313,13 +1314,52 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) v
   // never comes near the static) only for link-pose input, which does not
   // assume the kinematics
   const int ns = w.n_static;
+  // joint-value input with the lookup grids built (mpg_broadphase.h
+  // bp_grid_*): a gridded object's centre picks one cell word, the kept bits
+  // of all its group-0 partners (a centre outside its grid takes them all);
+  // kGridGroup objects' loads are issued together, and the words are shifted
+  // into blocks of 32 consecutive schedule entries for push.  The objects
+  // without a grid keep the loop below, over their own entries (gst_start).
+  const bool use_grid = !FROM_POSES && grid != nullptr && w.n_grid > 0 && !w.dbg(12) && !w.dbg(15);  // 15: diagnostics, lookups off
+  if (use_grid) {
+    int eb = w.grid_i[GI_E], fill = 0;
+    unsigned long long acc = 0ull;
+    for (int g0 = 0; g0 < w.n_grid; g0 += kGridGroup) {
+      uint32_t wd[kGridGroup];
+#pragma unroll
+      for (int j = 0; j < kGridGroup; ++j) {
+        const cptr<float> gf = w.grid_f + GF_STRIDE * (g0 + j);
+        const cptr<int> gi = w.grid_i + GI_STRIDE * (g0 + j);
+        const float* rm = cen + (size_t)gi[GI_M] * 3 * BLOCK + tid;
+        const float cm[3] = {rm[0], rm[BLOCK], rm[2 * BLOCK]};
+        const int cell = bp_grid_cell(gf, gi, cm);
+        const uint32_t x = grid[cell < 0 ? 0 : cell];
+        wd[j] = cell < 0 ? (uint32_t)gi[GI_FULL] : x;
+      }
+      static_assert(kGridGroup == 4, "the selection below names four words");
+#pragma unroll 1
+      for (int j = 0; j < kGridGroup; ++j) {
+        const uint32_t x = j == 0 ? wd[0] : j == 1 ? wd[1] : j == 2 ? wd[2] : wd[3];
+        acc |= (unsigned long long)x << fill;
+        fill += w.grid_i[GI_STRIDE * (g0 + j) + GI_NP];
+        const bool last = g0 + j + 1 == w.n_grid;
+        while (fill >= 32 || (last && fill > 0)) {
+          push(eb, (uint32_t)acc);
+          acc >>= 32;
+          eb += 32;
+          fill = max(fill - 32, 0);
+        }
+      }
+    }
+  }
   for (int g = 0; g < (FROM_POSES ? 2 : 1) && !w.dbg(12); ++g) {  // 12: diagnostics, without these tests
-    const int E0 = w.st_start[g * (ns + 1)], E1 = w.st_start[g * (ns + 1) + ns];
+    const cptr<int> sts = use_grid ? w.gst_start : w.st_start + g * (ns + 1);
+    const int E0 = sts[0], E1 = sts[ns];
     if (E0 == E1) continue;
     int eb = E0;
     uint32_t kb = 0u;
     for (int sid = 0; sid < ns; ++sid) {
-      const int e0 = w.st_start[g * (ns + 1) + sid], e1 = w.st_start[g * (ns + 1) + sid + 1];
+      const int e0 = sts[sid], e1 = sts[sid + 1];
       if (e0 == e1) continue;
       const cptr<float> rec = w.bp.sobj + BS_STRIDE * sid;
       float sr[BS_STRIDE];

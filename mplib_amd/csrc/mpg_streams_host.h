@@ -131,11 +131,42 @@ struct ContactOut {
   double *depth, *normal, *pos;  // [n*P], [n*P*3], [n*P*3]
 };
 
+// The words of the cull's lookup grids (NULL: the world has none).  The first
+// bulk launch with joint-value input builds them from the plan world creation
+// left and uploads them, so creation and the latency path pay nothing; later
+// calls only read the flag.
+inline int grid_words_for(mpg_world* w, const uint32_t** out) {
+  *out = nullptr;
+  if (w->dw.n_grid == 0) return MPG_OK;
+  if (!w->grid_ready.load(std::memory_order_acquire)) {
+    std::lock_guard<std::mutex> lk(w->grid_mu);
+    if (!w->grid_ready.load(std::memory_order_relaxed)) {
+      const auto t0 = std::chrono::steady_clock::now();
+      std::vector<uint32_t> words;
+      bp_grid_fill(w->grid_plan, words);
+      HIP_TRY(w->grid_words.reserve(words.size()));
+      HIP_TRY(hipMemcpy(w->grid_words.get(), words.data(), sizeof(uint32_t) * words.size(), hipMemcpyHostToDevice));
+      w->grid_plan = BpGridPlan();
+      w->grid_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      if (std::getenv("MPG_STATS"))
+        std::fprintf(stderr, "[mpg] lookup grids: %zu cells built in %.1f ms\n", words.size(), w->grid_build_ms);
+      w->grid_ready.store(true, std::memory_order_release);
+    }
+  }
+  *out = w->grid_words.get();
+  return MPG_OK;
+}
+
 template <bool FROM_POSES>
 int launch_collide(mpg_world* w, const double* in, long long n, uint8_t* flags, uint32_t* masks, hipStream_t stream,
                    const ContactOut* co = nullptr) {
   if (n == 0) return MPG_OK;
   StreamPin pin(w, stream);
+  const uint32_t* gwords = nullptr;
+  if (!FROM_POSES) {
+    const int grc = grid_words_for(w, &gwords);
+    if (grc) return grc;
+  }
   const long long chunk = std::min<long long>(n, w->max_chunk);
   mpg_world::Workspace* owner = nullptr;
   int rc = get_workspace(w, stream, chunk, &owner);
@@ -168,15 +199,15 @@ int launch_collide(mpg_world* w, const double* in, long long n, uint8_t* flags, 
     switch (w->block) {
       case 256:
         hipLaunchKernelGGL((cull_kernel<256, FROM_POSES>), dim3(grid), dim3(256), w->lds_bytes, stream, w->dw, qin,
-                           m, fl, mk, surv, rq, sc, cap, cnt, n_tiles);
+                           m, fl, mk, surv, rq, sc, cap, cnt, n_tiles, gwords);
         break;
       case 128:
         hipLaunchKernelGGL((cull_kernel<128, FROM_POSES>), dim3(grid), dim3(128), w->lds_bytes, stream, w->dw, qin,
-                           m, fl, mk, surv, rq, sc, cap, cnt, n_tiles);
+                           m, fl, mk, surv, rq, sc, cap, cnt, n_tiles, gwords);
         break;
       default:
         hipLaunchKernelGGL((cull_kernel<64, FROM_POSES>), dim3(grid), dim3(64), w->lds_bytes, stream, w->dw, qin, m,
-                           fl, mk, surv, rq, sc, cap, cnt, n_tiles);
+                           fl, mk, surv, rq, sc, cap, cnt, n_tiles, gwords);
         break;
     }
     HIP_TRY(hipGetLastError());

@@ -30,6 +30,20 @@ struct mpg_world {
   DevBuf<int> big_busy;
   DevBuf<unsigned long long> stats;
   DevBuf<double> free_dev;
+  // the cull's lookup grids (dw.n_grid > 0): the plan world creation left, the
+  // words the first bulk launch builds from it (grid_words_for; grid_mu, not
+  // host_mu, which some callers of launch_collide hold) and how long that took
+  BpGridPlan grid_plan;
+  DevBuf<uint32_t> grid_words;
+  std::mutex grid_mu;
+  std::atomic<bool> grid_ready{false};
+  double grid_build_ms = 0.0;
+  struct GridInfo {  // what mpg_cull_grid_info reports (kept when the plan is dropped)
+    std::vector<int> object, partners;
+    std::vector<double> box;  // [objects][6]: the grid's corners, origin and origin + n * h
+    long long cells = 0;
+    double h = 0.0;
+  } grid_info;
   int block = 128;
   size_t lds_bytes = 0;
   // staging for MPG_MEM_HOST

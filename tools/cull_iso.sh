@@ -6,7 +6,8 @@
 #   0 full, 1 FK + records, 2 no SAT (sphere survivors kept), 8 bounding
 #   tests + SAT, 9 all but sincos, 11 bounding tests only (no queue / SAT),
 #   12 full without the static-partner bounding tests, 13 FK without the
-#   rq stores, 14 launch + output zeroing only
+#   rq stores, 14 launch + output zeroing only, 15 full with the lookup grids
+#   off (the moving-static sphere tests of every object, as before the grids)
 # usage: bash tools/cull_iso.sh <out dir> [bench args]
 set -o pipefail
 OUT=${1:-gpurun_out/cull_iso}; shift
