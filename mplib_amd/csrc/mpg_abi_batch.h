@@ -26,43 +26,34 @@ int mpg_collide_batch(mpg_world* w, const double* q, int64_t n, uint8_t* flags, 
   return collide_common<false>(w, q, n, flags, pair_mask, mem, stream);
 }
 
+// the worlds of a multi-world call: none NULL or listed twice, all built from world 0's descriptor
+static int check_worlds(mpg_world* const* worlds, int32_t n_worlds) {
+  for (int k = 0; k < n_worlds; ++k) {
+    const mpg_world *wk = worlds[k], *w0 = worlds[0];
+    if (!wk) return set_error(MPG_E_INVALID, "world " + std::to_string(k) + " is NULL");
+    if (wk->dw.dof != w0->dw.dof || wk->dw.n_pairs != w0->dw.n_pairs || wk->dw.W != w0->dw.W ||
+        wk->dw.n_links != w0->dw.n_links || wk->blob_bytes != w0->blob_bytes || wk->snapshot_hash != w0->snapshot_hash)
+      return set_error(MPG_E_INVALID, "world " + std::to_string(k) + " was not built from world 0's descriptor");
+    for (int j = 0; j < k; ++j)
+      if (worlds[j] == wk) return set_error(MPG_E_INVALID, "a world is listed twice");
+  }
+  return MPG_OK;
+}
+
 int mpg_collide_batch_multi(mpg_world* const* worlds, int32_t n_worlds, const double* q, int64_t n, uint8_t* flags,
                             uint32_t* pair_mask) {
   if (n_worlds <= 0 || !worlds) return set_error(MPG_E_INVALID, "no worlds");
   if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
   if (n > 0 && (!q || !flags)) return set_error(MPG_E_INVALID, "q / flags is NULL");
-  mpg_world_info i0{};
-  for (int k = 0; k < n_worlds; ++k) {
-    mpg_world_info ik{};
-    if (!worlds[k]) return set_error(MPG_E_INVALID, "world " + std::to_string(k) + " is NULL");
-    mpg_world_get_info(worlds[k], &ik);
-    if (k == 0) {
-      i0 = ik;
-    } else if (ik.dof != i0.dof || ik.n_pairs != i0.n_pairs || ik.mask_words != i0.mask_words ||
-               ik.n_links != i0.n_links || ik.snapshot_bytes != i0.snapshot_bytes ||
-               worlds[k]->snapshot_hash != worlds[0]->snapshot_hash) {
-      return set_error(MPG_E_INVALID, "world " + std::to_string(k) + " was not built from world 0's descriptor");
-    }
-    for (int j = 0; j < k; ++j)
-      if (worlds[j] == worlds[k]) return set_error(MPG_E_INVALID, "a world is listed twice");
-  }
-  std::vector<int> rc(n_worlds, MPG_OK);
-  std::vector<std::string> err(n_worlds);
-  auto run = [&](int k) {
+  if (const int rc = check_worlds(worlds, n_worlds)) return rc;
+  const size_t dof = worlds[0]->dw.dof, W = worlds[0]->dw.W;
+  return run_shards(n_worlds, [&](int k) -> int {
     int64_t start = 0, count = 0;
     mpg_shard_range(n, k, n_worlds, &start, &count);
-    if (count == 0) return;
-    rc[k] = mpg_collide_batch(worlds[k], q + (size_t)start * i0.dof, count, flags + start,
-                              pair_mask ? pair_mask + (size_t)start * i0.mask_words : nullptr, MPG_MEM_HOST, nullptr);
-    if (rc[k]) err[k] = g_last_error;  // the worker thread's error text
-  };
-  std::vector<std::thread> th;
-  for (int k = 1; k < n_worlds; ++k) th.emplace_back(run, k);
-  run(0);
-  for (auto& t : th) t.join();
-  for (int k = 0; k < n_worlds; ++k)
-    if (rc[k]) return set_error(rc[k], "world " + std::to_string(k) + ": " + err[k]);
-  return MPG_OK;
+    if (count == 0) return MPG_OK;
+    return mpg_collide_batch(worlds[k], q + start * dof, count, flags + start,
+                             pair_mask ? pair_mask + start * W : nullptr, MPG_MEM_HOST, nullptr);
+  });
 }
 
 int mpg_shard_range(int64_t n, int32_t k, int32_t n_parts, int64_t* start, int64_t* count) {
@@ -81,19 +72,11 @@ int mpg_collide_batch_multi_device(mpg_world* const* worlds, int32_t n_worlds, c
   if (n_worlds <= 0 || !worlds) return set_error(MPG_E_INVALID, "no worlds");
   if (!counts || !q || !flags) return set_error(MPG_E_INVALID, "counts / q / flags array is NULL");
   if (gather_masks && !pair_mask) return set_error(MPG_E_INVALID, "gather_masks needs pair_mask");
-  for (int k = 0; k < n_worlds; ++k) {
-    if (!worlds[k]) return set_error(MPG_E_INVALID, "world " + std::to_string(k) + " is NULL");
-    if (counts[k] < 0) return set_error(MPG_E_INVALID, "counts[" + std::to_string(k) + "] < 0");
-    for (int j = 0; j < k; ++j)
-      if (worlds[j] == worlds[k]) return set_error(MPG_E_INVALID, "a world is listed twice");
-  }
+  if (const int rc = check_worlds(worlds, n_worlds)) return rc;
   const mpg_world* w0 = worlds[0];
   for (int k = 0; k < n_worlds; ++k) {
-    const mpg_world* wk = worlds[k];
-    if (wk->dw.dof != w0->dw.dof || wk->dw.n_pairs != w0->dw.n_pairs || wk->dw.W != w0->dw.W ||
-        wk->blob_bytes != w0->blob_bytes || wk->snapshot_hash != w0->snapshot_hash)
-      return set_error(MPG_E_INVALID, "world " + std::to_string(k) + " was not built from world 0's descriptor");
-    if (counts[k] > 0 && ((!q[k] && wk->dw.dof > 0) || !flags[k]))
+    if (counts[k] < 0) return set_error(MPG_E_INVALID, "counts[" + std::to_string(k) + "] < 0");
+    if (counts[k] > 0 && ((!q[k] && w0->dw.dof > 0) || !flags[k]))
       return set_error(MPG_E_INVALID, "shard " + std::to_string(k) + ": q / flags is NULL");
     if (counts[k] > 0 && gather_masks && !pair_mask[k])
       return set_error(MPG_E_INVALID, "shard " + std::to_string(k) + ": gather_masks needs its pair_mask");
@@ -115,22 +98,16 @@ int mpg_collide_batch_multi_device(mpg_world* const* worlds, int32_t n_worlds, c
       (void)hipGetLastError();
     }
   }
-  std::vector<int> rc(n_worlds, MPG_OK);
-  std::vector<std::string> err(n_worlds);
-  auto run = [&](int k) {
+  const int rc = run_shards(n_worlds, [&](int k) -> int {
     mpg_world* w = worlds[k];
     hipStream_t s = streams ? static_cast<hipStream_t>(streams[k]) : nullptr;
     uint32_t* mk = pair_mask ? pair_mask[k] : nullptr;
-    auto fail = [&](int code, const std::string& m) {
-      rc[k] = code;
-      err[k] = m;
-    };
-    if (hipSetDevice(w->device) != hipSuccess) return fail(MPG_E_HIP, "hipSetDevice failed");
+    if (hipSetDevice(w->device) != hipSuccess) return set_error(MPG_E_HIP, "hipSetDevice failed");
     if (counts[k] > 0) {
       const int r = mpg_collide_batch(w, q[k], counts[k], flags[k], mk, MPG_MEM_DEVICE, s);
-      if (r) return fail(r, g_last_error);
+      if (r) return r;
     }
-    if (!gather) return;
+    if (!gather) return MPG_OK;
     hipError_t e = hipSuccess;
     if (counts[k] > 0 && gather_flags)
       e = hipMemcpyPeerAsync(gather_flags + off[k], w0->device, flags[k], w->device, (size_t)counts[k], s);
@@ -141,14 +118,10 @@ int mpg_collide_batch_multi_device(mpg_world* const* worlds, int32_t n_worlds, c
       if (!w->gather_ev) e = w->gather_ev.create(hipEventDisableTiming);
       if (e == hipSuccess) e = hipEventRecord(w->gather_ev.get(), s);
     }
-    if (e != hipSuccess) return fail(MPG_E_HIP, std::string("gather: ") + hipGetErrorString(e));
-  };
-  std::vector<std::thread> th;
-  for (int k = 1; k < n_worlds; ++k) th.emplace_back(run, k);
-  run(0);
-  for (auto& t : th) t.join();
-  for (int k = 0; k < n_worlds; ++k)
-    if (rc[k]) return set_error(rc[k], "world " + std::to_string(k) + ": " + err[k]);
+    if (e != hipSuccess) return set_error(MPG_E_HIP, std::string("gather: ") + hipGetErrorString(e));
+    return MPG_OK;
+  });
+  if (rc) return rc;
   if (gather) {  // streams[0] orders after every shard's copies
     HIP_TRY(hipSetDevice(w0->device));
     hipStream_t s0 = streams ? static_cast<hipStream_t>(streams[0]) : nullptr;
@@ -171,8 +144,7 @@ int mpg_world_set_free_poses(mpg_world* w, const double* pose7) {
   if (!w) return set_error(MPG_E_INVALID, "world is NULL");
   if (w->dw.n_free == 0) return set_error(MPG_E_INVALID, "the world has no free frames");
   if (!pose7) return set_error(MPG_E_INVALID, "pose7 is NULL");
-  const int rc = check_free_poses(pose7, (size_t)w->dw.n_free);
-  if (rc) return rc;
+  if (const int rc = check_poses(pose7, (size_t)w->dw.n_free, "free pose")) return rc;
   HIP_TRY(hipSetDevice(w->device));
   // calls in flight read the buffer: wait for them, then overwrite it in place
   std::lock_guard<std::mutex> lk(w->host_mu);
@@ -204,7 +176,7 @@ int mpg_check_motion_batch_free(mpg_world* w, const double* q_from, const double
   if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
   if (n > 0 && (!q_from || !q_to || !valid)) return set_error(MPG_E_INVALID, "from/to/valid is NULL");
   if (!(longest_valid_segment > 0.0)) return set_error(MPG_E_INVALID, "longest_valid_segment must be > 0");
-  if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
+  if (const int mrc = bad_mem(mem)) return mrc;
   if (const int frc = check_free_args(w, free_pose, free_rows, n)) return frc;
   if (w->dw.dof > 32) return set_error(MPG_E_UNSUPPORTED, "motion validation supports dof <= 32");
   if (n == 0) return MPG_OK;
@@ -212,7 +184,7 @@ int mpg_check_motion_batch_free(mpg_world* w, const double* q_from, const double
   if (per_edge && n > (int64_t)INT32_MAX)
     return set_error(MPG_E_UNSUPPORTED, "per-edge free poses support at most 2^31 - 1 edges");
   if (free_pose && mem == MPG_MEM_HOST)
-    if (const int frc = check_free_poses(free_pose, (size_t)free_rows * w->dw.n_free)) return frc;
+    if (const int frc = check_poses(free_pose, (size_t)free_rows * w->dw.n_free, "free pose")) return frc;
   HIP_TRY(hipSetDevice(w->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   std::lock_guard<std::mutex> lk(w->motion_mu);
@@ -239,11 +211,8 @@ int mpg_check_motion_batch_free(mpg_world* w, const double* q_from, const double
     HIP_TRY(hipMemcpyAsync(d_edges + (size_t)n * dof, q_to, eb, hipMemcpyHostToDevice, s));
     from = d_edges;
     to = d_edges + (size_t)n * dof;
-    if (free_pose) {
-      if ((rc = grow(M.fp, frow * (size_t)free_rows))) return rc;
-      HIP_TRY(hipMemcpyAsync(M.fp.get(), free_pose, sizeof(double) * frow * (size_t)free_rows, hipMemcpyHostToDevice, s));
-      fp = M.fp.get();
-    }
+    HostStage st{s, "motion", &M.last};
+    if (free_pose && !(fp = st.in(M.fp, free_pose, frow * (size_t)free_rows))) return st.rc;
   }
   const unsigned grid = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(motion_count_kernel, dim3(grid), dim3(256), 0, s, from, to, (long long)n, dof, so2_mask,
@@ -330,7 +299,7 @@ int mpg_distance_batch_free(mpg_world* w, const double* q, const double* free_po
   if (n_self_pairs < 0 || n_self_pairs > w->dw.n_pairs) return set_error(MPG_E_INVALID, "bad n_self_pairs");
   if (n > 0 && ((!q && w->dw.dof > 0) || !d_self || !p_self || !d_others || !p_others))
     return set_error(MPG_E_INVALID, "NULL buffer");
-  if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
+  if (const int mrc = bad_mem(mem)) return mrc;
   if (const int frc = check_free_args(w, free_pose, free_rows, n)) return frc;
   const int32_t flags = req->flags;
   if (flags & ~(MPG_DISTANCE_SIGNED | MPG_DISTANCE_NEAREST_POINTS | MPG_DISTANCE_GJK_INDEP))
@@ -351,7 +320,7 @@ int mpg_distance_batch_free(mpg_world* w, const double* q, const double* free_po
                    (flags & MPG_DISTANCE_NEAREST_POINTS ? MPG_DIST_NP : 0) | (indep ? MPG_DIST_INDEP : 0);
   if (n == 0) return MPG_OK;
   if (free_pose && mem == MPG_MEM_HOST)
-    if (const int frc = check_free_poses(free_pose, (size_t)free_rows * w->dw.n_free)) return frc;
+    if (const int frc = check_poses(free_pose, (size_t)free_rows * w->dw.n_free, "free pose")) return frc;
   HIP_TRY(hipSetDevice(w->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   std::lock_guard<std::mutex> lk(w->dist_mu);
@@ -368,12 +337,12 @@ int mpg_distance_batch_free(mpg_world* w, const double* q, const double* free_po
   double *ds = d_self, *dd = d_others, *qs = pts_self, *qo = pts_others;
   int32_t *ps = p_self, *po = p_others;
   const size_t out_bytes = (2 * sizeof(double) + 2 * sizeof(int32_t) + (mode ? 12 * sizeof(double) : 0)) * n;
+  HostStage st{s, "distance", &D.last};  // host buffers: their device twins, replaced as scratch_grow does
   if (mem == MPG_MEM_HOST) {
-    if ((rc = grow(D.q, (size_t)std::max(w->dw.dof, 1) * n))) return rc;
-    if ((rc = grow(D.out, out_bytes))) return rc;
-    if (w->dw.dof) HIP_TRY(hipMemcpyAsync(D.q.get(), q, sizeof(double) * w->dw.dof * n, hipMemcpyHostToDevice, s));
-    qin = D.q.get();
-    ds = reinterpret_cast<double*>(D.out.get());
+    st.out(D.q, (size_t)std::max(w->dw.dof, 1) * n);
+    ds = reinterpret_cast<double*>(st.out(D.out, out_bytes));
+    qin = st.in(D.q, q, (size_t)w->dw.dof * n);
+    if (st.rc) return st.rc;
     dd = ds + n;
     qs = dd + n;
     qo = qs + (mode ? 6 * n : 0);
@@ -389,14 +358,8 @@ int mpg_distance_batch_free(mpg_world* w, const double* q, const double* free_po
     if ((rc = grow(D.links, (size_t)7 * w->dw.n_links * n))) return rc;
     const size_t frow = (size_t)w->dw.n_free * 7;
     const double* fp = free_pose;  // device memory: read where the caller keeps it
-    if (free_pose && mem == MPG_MEM_HOST) {
-      if ((rc = grow(D.fp, frow * (size_t)free_rows))) return rc;
-      HIP_TRY(hipMemcpyAsync(D.fp.get(), free_pose, sizeof(double) * frow * (size_t)free_rows, hipMemcpyHostToDevice, s));
-      fp = D.fp.get();
-    }
-    hipLaunchKernelGGL(fk_free_kernel<false>, dim3(grid), dim3(128), 0, s, w->dw, qin, (long long)n, D.links.get(), fp,
-                       free_rows > 1 ? (long long)frow : 0ll, (const int32_t*)nullptr);
-    HIP_TRY(hipGetLastError());
+    if (free_pose && mem == MPG_MEM_HOST && !(fp = st.in(D.fp, free_pose, frow * (size_t)free_rows))) return st.rc;
+    if ((rc = launch_fk(w, qin, n, D.links.get(), s, fp, free_rows > 1 ? (long long)frow : 0ll))) return rc;
     hipLaunchKernelGGL((pose_kernel<true>), dim3(grid), dim3(128), 0, s, w->dw, D.links.get(), (long long)n, d_poses,
                        d_save64);
   } else {
@@ -436,13 +399,13 @@ int mpg_distance_batch_free(mpg_world* w, const double* q, const double* free_po
   }
   HIP_TRY(hipEventRecord(D.last.get(), s));
   if (mem == MPG_MEM_HOST) {
-    HIP_TRY(hipMemcpyAsync(d_self, ds, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(d_others, dd, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(p_self, ps, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(p_others, po, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-    if (mode && pts_self) HIP_TRY(hipMemcpyAsync(pts_self, qs, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, s));
-    if (mode && pts_others) HIP_TRY(hipMemcpyAsync(pts_others, qo, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    st.back(d_self, ds, n);
+    st.back(d_others, dd, n);
+    st.back(p_self, ps, n);
+    st.back(p_others, po, n);
+    if (mode && pts_self) st.back(pts_self, qs, 6 * n);
+    if (mode && pts_others) st.back(pts_others, qo, 6 * n);
+    if (st.finish()) return st.rc;
     for (int64_t i = 0; i < n; ++i) {
       if (p_self[i] == MPG_DISTANCE_FCL_THROWS)
         return set_error(MPG_E_FAILED, "configuration " + std::to_string(i) +
@@ -475,7 +438,7 @@ int mpg_collide_contacts_free(mpg_world* w, const double* input, const double* f
   const size_t row = poses ? (size_t)w->dw.n_links * 7 : (size_t)w->dw.dof;
   if (n > 0 && ((!input && row > 0) || !flags || !pair_mask || !depth || !normal || !pos))
     return set_error(MPG_E_INVALID, "NULL buffer");
-  if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
+  if (const int mrc = bad_mem(mem)) return mrc;
   if (w->any_gjk)
     return set_error(MPG_E_UNSUPPORTED, "contacts with gjk_solver MPG_GJK_INDEP (FCL's EPA) are not implemented");
   if (w->has_octree2)
@@ -483,65 +446,39 @@ int mpg_collide_contacts_free(mpg_world* w, const double* input, const double* f
   if (w->octree_first)  // contact_kernel reports the (shape, octree) order PlanningWorld uses
     return set_error(MPG_E_UNSUPPORTED, "contacts for a pair whose first object is an OcTree are not implemented");
   if (n == 0) return MPG_OK;
-  // host-memory link-pose rows: the free frames' columns are checked as every host-memory free pose is
-  if (poses && mem == MPG_MEM_HOST && w->dw.n_free)
-    for (int64_t i = 0; i < n; ++i) {
-      const int rc = check_free_poses(input + ((size_t)i * w->dw.n_links + (w->dw.n_links - w->dw.n_free)) * 7,
-                                      (size_t)w->dw.n_free);
-      if (rc) return rc;
-    }
+  if (poses && mem == MPG_MEM_HOST)
+    if (const int crc = check_free_columns(w, input, n)) return crc;
   if (free_pose && mem == MPG_MEM_HOST)
-    if (const int frc = check_free_poses(free_pose, (size_t)free_rows * w->dw.n_free)) return frc;
+    if (const int frc = check_poses(free_pose, (size_t)free_rows * w->dw.n_free, "free pose")) return frc;
   HIP_TRY(hipSetDevice(w->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t P = (size_t)w->dw.n_pairs, W = (size_t)w->dw.W;
   const size_t frow = (size_t)w->dw.n_free * 7;
   const long long fstride = free_rows > 1 ? (long long)frow : 0ll;
-  if (mem == MPG_MEM_DEVICE) {
-    ContactOut co{depth, normal, pos};
-    if (free_pose) return launch_collide_free(w, input, free_pose, fstride, n, flags, pair_mask, s, &co);
-    return poses ? launch_collide<true>(w, input, n, flags, pair_mask, s, &co)
-                 : launch_collide_q(w, input, n, flags, pair_mask, s, &co);
-  }
-  // host buffers: grow-only device staging kept by the world (one host call
-  // at a time: host_mu), no allocation per call
+  auto run = [&](const double* in, const double* fp, uint8_t* fl, uint32_t* mk, const ContactOut& co) {  // device buffers
+    if (fp) return launch_collide_free(w, in, fp, fstride, n, fl, mk, s, &co);
+    return poses ? launch_collide<true>(w, in, n, fl, mk, s, &co) : launch_collide_q(w, in, n, fl, mk, s, &co);
+  };
+  if (mem == MPG_MEM_DEVICE) return run(input, free_pose, flags, pair_mask, ContactOut{depth, normal, pos});
   std::lock_guard<std::mutex> lk(w->host_mu);
   if (!s && w->own_stream) s = w->own_stream.get();
   auto& C = w->contact;
-  int rc = MPG_OK;
-  do {
-    // (no wait before a staging buffer is replaced: this call is synchronous under host_mu)
-    if (C.in.reserve(std::max<size_t>(1, row * n)) != hipSuccess || C.out.reserve(7 * P * n) != hipSuccess ||
-        C.fl.reserve(n) != hipSuccess || C.mk.reserve(W * n) != hipSuccess ||
-        (free_pose && C.fp.reserve(frow * (size_t)free_rows) != hipSuccess)) {
-      rc = set_error(MPG_E_NOMEM, "contact staging buffers");
-      break;
-    }
-    double *d_in = C.in.get(), *d_out = C.out.get(), *d_fp = C.fp.get();
-    uint8_t* d_fl = C.fl.get();
-    uint32_t* d_mk = C.mk.get();
-    if (free_pose && hipMemcpyAsync(d_fp, free_pose, sizeof(double) * frow * (size_t)free_rows,
-                                    hipMemcpyHostToDevice, s) != hipSuccess) {
-      rc = set_error(MPG_E_HIP, "copy free poses");
-      break;
-    }
-    if (row && hipMemcpyAsync(d_in, input, sizeof(double) * row * n, hipMemcpyHostToDevice, s) != hipSuccess) {
-      rc = set_error(MPG_E_HIP, "copy input");
-      break;
-    }
-    ContactOut co{d_out, d_out + P * n, d_out + 4 * P * n};
-    if (free_pose) rc = launch_collide_free(w, d_in, d_fp, fstride, n, d_fl, d_mk, s, &co);
-    else rc = poses ? launch_collide<true>(w, d_in, n, d_fl, d_mk, s, &co) : launch_collide_q(w, d_in, n, d_fl, d_mk, s, &co);
-    if (rc) break;
-    if (hipMemcpyAsync(flags, d_fl, n, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(pair_mask, d_mk, sizeof(uint32_t) * W * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(depth, co.depth, sizeof(double) * P * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(normal, co.normal, sizeof(double) * 3 * P * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(pos, co.pos, sizeof(double) * 3 * P * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-      rc = set_error(MPG_E_HIP, "copy contact results");
-  } while (false);
-  return rc;
+  HostStage st{s, "contact"};
+  st.out(C.in, std::max<size_t>(1, row * n));
+  double* const d_out = st.out(C.out, 7 * P * n);
+  uint8_t* const d_fl = st.out(C.fl, n);
+  uint32_t* const d_mk = st.out(C.mk, W * n);
+  const double* const d_fp = free_pose ? st.in(C.fp, free_pose, frow * (size_t)free_rows) : nullptr;
+  const double* const d_in = st.in(C.in, input, row * n);
+  if (st.rc) return st.rc;
+  const ContactOut co{d_out, d_out + P * n, d_out + 4 * P * n};
+  if (const int rc = run(d_in, d_fp, d_fl, d_mk, co)) return rc;
+  st.back(flags, d_fl, n);
+  st.back(pair_mask, d_mk, W * n);
+  st.back(depth, co.depth, P * n);
+  st.back(normal, co.normal, 3 * P * n);
+  st.back(pos, co.pos, 3 * P * n);
+  return st.finish();
 }
 
 int mpg_fk_batch(mpg_world* w, const double* q, int64_t n, double* link_pose, int mem, void* stream) {
@@ -551,31 +488,25 @@ int mpg_fk_batch(mpg_world* w, const double* q, int64_t n, double* link_pose, in
   HIP_TRY(hipSetDevice(w->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t nout = (size_t)n * w->dw.n_links * 7;
-  const unsigned grid = (unsigned)((n + 127) / 128);
-  if (mem == MPG_MEM_DEVICE) {
-    if (n && w->dw.n_free)
-      hipLaunchKernelGGL(fk_free_kernel<false>, dim3(grid), dim3(128), 0, s, w->dw, q, (long long)n, link_pose,
-                         (const double*)nullptr, 0ll, (const int32_t*)nullptr);
-    else if (n)
-      hipLaunchKernelGGL(fk_kernel, dim3(grid), dim3(128), 0, s, w->dw, q, (long long)n, link_pose);
-    HIP_TRY(hipGetLastError());
-    return MPG_OK;
-  }
-  if (mem != MPG_MEM_HOST) return set_error(MPG_E_INVALID, "bad mem kind");
+  if (mem == MPG_MEM_DEVICE) return launch_fk(w, q, n, link_pose, s);
+  if (const int mrc = bad_mem(mem)) return mrc;
   std::lock_guard<std::mutex> lk(w->host_mu);
-  int rc = ensure_staging(w, (size_t)n, std::max<size_t>(nout, 1));
-  if (rc) return rc;
-  if (n == 0) return MPG_OK;
-  double *const d_q = w->d_q.get(), *const d_out = w->d_out.get();
-  HIP_TRY(hipMemcpyAsync(d_q, q, sizeof(double) * n * w->dw.dof, hipMemcpyHostToDevice, s));
-  if (w->dw.n_free)
-    hipLaunchKernelGGL(fk_free_kernel<false>, dim3(grid), dim3(128), 0, s, w->dw, d_q, (long long)n, d_out,
-                       (const double*)nullptr, 0ll, (const int32_t*)nullptr);
-  else
-    hipLaunchKernelGGL(fk_kernel, dim3(grid), dim3(128), 0, s, w->dw, d_q, (long long)n, d_out);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(link_pose, d_out, sizeof(double) * nout, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
+  auto& F = w->fk_stage;
+  HostStage st{s, "FK"};
+  st.out(F.q, std::max<size_t>(1, (size_t)n * std::max(w->dw.dof, 1)));
+  double* const d_out = st.out(F.out, std::max<size_t>(nout, 1));
+  if (st.rc || n == 0) return st.rc;
+  const double* const d_q = st.in(F.q, q, (size_t)n * w->dw.dof);
+  if (st.rc) return st.rc;
+  if (const int rc = launch_fk(w, d_q, n, d_out, s)) return rc;
+  st.back(link_pose, d_out, nout);
+  return st.finish();
+}
+
+// what mpg_ik_batch and mpg_screw_batch ask of their link
+static int check_ik_link(const mpg_world* w, int32_t link) {
+  if (link < 0 || link >= w->dw.n_links) return set_error(MPG_E_INVALID, "link index out of range");
+  if (link >= w->dw.n_links - w->dw.n_free) return set_error(MPG_E_INVALID, "link is a free frame: no joint moves it");
   return MPG_OK;
 }
 
@@ -605,8 +536,7 @@ static int launch_ik(mpg_world* w, const IkView& iv, const double* goal, long lo
     q_in = q_out;
   }
   // one wave per block; the grid: the waves the LDS lets be resident, fewer for small batches
-  const size_t cl = (size_t)std::max(iv.cl, 1);
-  const size_t lds = sizeof(double) * (kIkSlot * 64 + IKT_DOUBLES) * cl + sizeof(int) * IKT_INTS * cl;
+  const size_t lds = mpg_args::ik_lds_bytes(iv.cl);
   const long long resident = (long long)w->ik.cus * std::max<long long>(1, std::min<long long>(8, (160 * 1024) / lds));
   long long waves = std::min<long long>((rows + 63) / 64, resident);
   if (max_waves > 0) waves = std::min<long long>(waves, max_waves);
@@ -629,10 +559,9 @@ int mpg_ik_batch(mpg_world* w, int32_t link, const double* goal_pose, int64_t n_
                  uint8_t* status, double* err, int32_t* iters, int mem, void* stream) {
   if (!w) return set_error(MPG_E_INVALID, "world is NULL");
   if (n_goals < 0 || rows_per_goal < 0) return set_error(MPG_E_INVALID, "n_goals / rows_per_goal < 0");
-  if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
+  if (const int mrc = bad_mem(mem)) return mrc;
   const auto& T = w->ik;
-  if (link < 0 || link >= w->dw.n_links) return set_error(MPG_E_INVALID, "link index out of range");
-  if (link >= w->dw.n_links - w->dw.n_free) return set_error(MPG_E_INVALID, "link is a free frame: no joint moves it");
+  if (const int lrc = check_ik_link(w, link)) return lrc;
   if (!q_init && !q_start) return set_error(MPG_E_INVALID, "q_init and q_start are both NULL");
   mpg_ik_options o{1e-5, 1000, 0.1, 1e-12, 1e-3, nullptr, 0, 0};
   if (opt) o = *opt;
@@ -644,9 +573,7 @@ int mpg_ik_batch(mpg_world* w, int32_t link, const double* goal_pose, int64_t n_
   if (n_goals > (int64_t)1 << 40 || rows_per_goal > (int64_t)1 << 20 || n_goals * rows_per_goal > (int64_t)1 << 40)
     return set_error(MPG_E_UNSUPPORTED, "mpg_ik_batch supports at most 2^40 rows");
   IkView iv{};
-  iv.link = link;
-  iv.cs = T.chain_start[link];
-  iv.cl = T.chain_len[link];
+  mpg_args::fill_ik_view(iv, T, link, dof, o.mask);
   iv.max_iter = o.max_iter;
   iv.eps = o.eps;
   iv.dt = o.dt;
@@ -654,29 +581,15 @@ int mpg_ik_batch(mpg_world* w, int32_t link, const double* goal_pose, int64_t n_
   iv.threshold = o.threshold;
   constexpr double kPi = 3.14159265358979323846;
   for (int d = 0; d < dof; ++d) {
-    iv.kind[d] = T.kind[d];
-    iv.bounded[d] = std::isfinite(T.lo[d]) && std::isfinite(T.hi[d]);
-    iv.frozen[d] = o.mask && o.mask[d] ? 1 : 0;
-    iv.lo[d] = T.continuous[d] ? -kPi : T.lo[d];
-    iv.hi[d] = T.continuous[d] ? kPi : T.hi[d];
+    if (T.continuous[d]) iv.lo[d] = -kPi, iv.hi[d] = kPi;  // its sampling range
     if (!q_init && !iv.frozen[d] && !T.continuous[d] && !iv.bounded[d])
       return set_error(MPG_E_INVALID, "dof slot " + std::to_string(d) +
                                           ": a joint with neither finite limits nor a continuous type cannot be sampled");
   }
-  for (int k = 0; k < iv.cl; ++k) {
-    const int src = T.joint_q_source[T.chain_joints[iv.cs + k] - 1];
-    iv.move[k] = src >= 0 && !iv.frozen[src];
-  }
   const int64_t rows = n_goals * rows_per_goal;
   if (rows > 0 && (!goal_pose || !q_out || !status)) return set_error(MPG_E_INVALID, "goal_pose / q_out / status is NULL");
   if (mem == MPG_MEM_HOST && rows > 0) {
-    for (int64_t g = 0; g < n_goals; ++g) {
-      const double* p = goal_pose + 7 * g;
-      if (!finite_all(p, 7)) return set_error(MPG_E_INVALID, "non-finite goal pose");
-      const double nq = std::sqrt(p[3] * p[3] + p[4] * p[4] + p[5] * p[5] + p[6] * p[6]);
-      if (!(std::fabs(nq - 1.0) <= kFreeQuatTol))
-        return set_error(MPG_E_INVALID, "goal pose quaternion is not of unit norm (within 1e-6)");
-    }
+    if (const int prc = check_poses(goal_pose, (size_t)n_goals, "goal pose")) return prc;
     if (q_init && !finite_all(q_init, (size_t)rows * dof)) return set_error(MPG_E_INVALID, "non-finite q_init");
     if (q_start && !finite_all(q_start, (size_t)dof)) return set_error(MPG_E_INVALID, "non-finite q_start");
   }
@@ -686,29 +599,29 @@ int mpg_ik_batch(mpg_world* w, int32_t link, const double* goal_pose, int64_t n_
   if (mem == MPG_MEM_DEVICE)
     return launch_ik(w, iv, goal_pose, n_goals, rows_per_goal, q_init, q_start, o.seed, o.max_waves, q_out, status, err,
                      iters, s);
-  // host buffers: grow-only device staging kept by the world (one host call at
-  // a time: host_mu; no wait before a buffer is replaced, the call is synchronous)
   std::lock_guard<std::mutex> lk(w->host_mu);
   if (!s && w->own_stream) s = w->own_stream.get();
   auto& S = w->ik_stage;
-  const size_t nq = (size_t)rows * std::max(dof, 1);
-  if (S.goal.reserve(7 * (size_t)n_goals) != hipSuccess || S.q.reserve(nq) != hipSuccess ||
-      S.start.reserve(std::max(dof, 1)) != hipSuccess || S.err.reserve(6 * (size_t)rows) != hipSuccess ||
-      S.status.reserve((size_t)rows) != hipSuccess || S.iters.reserve((size_t)rows) != hipSuccess)
-    return set_error(MPG_E_NOMEM, "IK staging buffers");
-  HIP_TRY(hipMemcpyAsync(S.goal.get(), goal_pose, sizeof(double) * 7 * n_goals, hipMemcpyHostToDevice, s));
-  if (q_init && dof) HIP_TRY(hipMemcpyAsync(S.q.get(), q_init, sizeof(double) * rows * dof, hipMemcpyHostToDevice, s));
-  if (q_start && dof) HIP_TRY(hipMemcpyAsync(S.start.get(), q_start, sizeof(double) * dof, hipMemcpyHostToDevice, s));
-  const int rc = launch_ik(w, iv, S.goal.get(), n_goals, rows_per_goal, q_init ? S.q.get() : nullptr,
-                           q_start ? S.start.get() : nullptr, o.seed, o.max_waves, S.q.get(), S.status.get(),
-                           S.err.get(), S.iters.get(), s);
+  const size_t nq = (size_t)rows * dof;
+  HostStage st{s, "IK"};
+  st.out(S.goal, 7 * (size_t)n_goals);
+  double* const d_q = st.out(S.q, (size_t)rows * std::max(dof, 1));
+  st.out(S.start, std::max(dof, 1));
+  double* const d_err = st.out(S.err, 6 * (size_t)rows);
+  uint8_t* const d_status = st.out(S.status, (size_t)rows);
+  int32_t* const d_iters = st.out(S.iters, (size_t)rows);
+  const double* const d_goal = st.in(S.goal, goal_pose, 7 * (size_t)n_goals);
+  if (q_init) st.in(S.q, q_init, nq);
+  const double* const d_start = q_start ? st.in(S.start, q_start, (size_t)dof) : nullptr;
+  if (st.rc) return st.rc;
+  const int rc = launch_ik(w, iv, d_goal, n_goals, rows_per_goal, q_init ? d_q : nullptr, d_start, o.seed, o.max_waves,
+                           d_q, d_status, d_err, d_iters, s);
   if (rc) return rc;
-  if (dof) HIP_TRY(hipMemcpyAsync(q_out, S.q.get(), sizeof(double) * rows * dof, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(status, S.status.get(), (size_t)rows, hipMemcpyDeviceToHost, s));
-  if (err) HIP_TRY(hipMemcpyAsync(err, S.err.get(), sizeof(double) * 6 * rows, hipMemcpyDeviceToHost, s));
-  if (iters) HIP_TRY(hipMemcpyAsync(iters, S.iters.get(), sizeof(int32_t) * rows, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return MPG_OK;
+  st.back(q_out, d_q, nq);
+  st.back(status, d_status, (size_t)rows);
+  if (err) st.back(err, d_err, 6 * (size_t)rows);
+  if (iters) st.back(iters, d_iters, (size_t)rows);
+  return st.finish();
 }
 
 // device buffers: every row integrated by screw_kernel, one collide pass over
@@ -725,10 +638,8 @@ static int launch_screw(mpg_world* w, const ScrewView& sv, const double* goal, c
   if (K->flags.get() && K->flags.cap() < (size_t)cfgs) HIP_TRY(hipStreamSynchronize(s));  // queued work may still read it
   HIP_TRY(K->flags.reserve((size_t)cfgs));
   // one wave per block, a lane per row
-  const size_t cl = (size_t)std::max(sv.iv.cl, 1);
-  const size_t lds = sizeof(double) * (kIkSlot * 64 + IKT_DOUBLES) * cl + sizeof(int) * IKT_INTS * cl;
-  hipLaunchKernelGGL(screw_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), lds, s, w->dw, sv, goal, q_start,
-                     rows, path, n_waypoints, status);
+  hipLaunchKernelGGL(screw_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), mpg_args::ik_lds_bytes(sv.iv.cl), s,
+                     w->dw, sv, goal, q_start, rows, path, n_waypoints, status);
   HIP_TRY(hipGetLastError());
   const int rc = mpg_collide_batch(w, path, cfgs, K->flags.get(), nullptr, MPG_MEM_DEVICE, s);
   if (rc) return rc;
@@ -743,10 +654,9 @@ int mpg_screw_batch(mpg_world* w, int32_t link, const double* goal, const double
                     int32_t* first_hit, int mem, void* stream) {
   if (!w) return set_error(MPG_E_INVALID, "world is NULL");
   if (rows < 0) return set_error(MPG_E_INVALID, "rows < 0");
-  if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
+  if (const int mrc = bad_mem(mem)) return mrc;
   const auto& T = w->ik;
-  if (link < 0 || link >= w->dw.n_links) return set_error(MPG_E_INVALID, "link index out of range");
-  if (link >= w->dw.n_links - w->dw.n_free) return set_error(MPG_E_INVALID, "link is a free frame: no joint moves it");
+  if (const int lrc = check_ik_link(w, link)) return lrc;
   mpg_screw_options o{0.1, 64};
   if (opt) o = *opt;
   if (!(o.qpos_step > 0) || !std::isfinite(o.qpos_step)) return set_error(MPG_E_INVALID, "qpos_step must be > 0");
@@ -758,23 +668,14 @@ int mpg_screw_batch(mpg_world* w, int32_t link, const double* goal, const double
   if (T.chain_len[link] > kIkChain)
     return set_error(MPG_E_UNSUPPORTED, "mpg_screw_batch supports at most 15 joints above the link");
   ScrewView sv{};
-  IkView& iv = sv.iv;
-  iv.link = link;
-  iv.cs = T.chain_start[link];
-  iv.cl = T.chain_len[link];
+  const IkView& iv = sv.iv;
+  mpg_args::fill_ik_view(sv.iv, T, link, dof, nullptr);
   sv.qpos_step = o.qpos_step;
   sv.max_waypoints = o.max_waypoints;
-  for (int d = 0; d < dof; ++d) {
-    iv.kind[d] = T.kind[d];
-    iv.bounded[d] = std::isfinite(T.lo[d]) && std::isfinite(T.hi[d]);
-    iv.lo[d] = T.lo[d];
-    iv.hi[d] = T.hi[d];
-    sv.offchain[d] = 1;
-  }
+  for (int d = 0; d < dof; ++d) sv.offchain[d] = 1;
   int moving = 0;
   for (int k = 0; k < iv.cl; ++k) {
     const int src = T.joint_q_source[T.chain_joints[iv.cs + k] - 1];
-    iv.move[k] = src >= 0;
     if (src >= 0 && src < dof) {
       sv.offchain[src] = 0;
       ++moving;
@@ -786,41 +687,34 @@ int mpg_screw_batch(mpg_world* w, int32_t link, const double* goal, const double
   if (rows > 0 && (!goal || !q_start || !path || !n_waypoints || !status))
     return set_error(MPG_E_INVALID, "goal / q_start / path / n_waypoints / status is NULL");
   if (mem == MPG_MEM_HOST && rows > 0) {
-    for (int64_t g = 0; g < rows; ++g) {
-      const double* p = goal + 7 * g;
-      if (!finite_all(p, 7)) return set_error(MPG_E_INVALID, "non-finite goal pose");
-      const double nq = std::sqrt(p[3] * p[3] + p[4] * p[4] + p[5] * p[5] + p[6] * p[6]);
-      if (!(std::fabs(nq - 1.0) <= kFreeQuatTol))
-        return set_error(MPG_E_INVALID, "goal pose quaternion is not of unit norm (within 1e-6)");
-    }
+    if (const int prc = check_poses(goal, (size_t)rows, "goal pose")) return prc;
     if (!finite_all(q_start, (size_t)rows * dof)) return set_error(MPG_E_INVALID, "non-finite q_start");
   }
   if (rows == 0) return MPG_OK;
   HIP_TRY(hipSetDevice(w->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (mem == MPG_MEM_DEVICE) return launch_screw(w, sv, goal, q_start, rows, path, n_waypoints, status, first_hit, s);
-  // host buffers: grow-only device staging kept by the world (one host call at
-  // a time: host_mu; no wait before a buffer is replaced, the call is synchronous)
   std::lock_guard<std::mutex> lk(w->host_mu);
   if (!s && w->own_stream) s = w->own_stream.get();
   auto& S = w->screw_stage;
-  const size_t nq = (size_t)rows * std::max(dof, 1), np = nq * (size_t)o.max_waypoints;
-  if (S.goal.reserve(7 * (size_t)rows) != hipSuccess || S.start.reserve(nq) != hipSuccess ||
-      S.path.reserve(np) != hipSuccess || S.status.reserve((size_t)rows) != hipSuccess ||
-      S.count.reserve((size_t)rows) != hipSuccess || S.first_hit.reserve((size_t)rows) != hipSuccess)
-    return set_error(MPG_E_NOMEM, "screw staging buffers");
-  HIP_TRY(hipMemcpyAsync(S.goal.get(), goal, sizeof(double) * 7 * rows, hipMemcpyHostToDevice, s));
-  if (dof) HIP_TRY(hipMemcpyAsync(S.start.get(), q_start, sizeof(double) * rows * dof, hipMemcpyHostToDevice, s));
-  const int rc = launch_screw(w, sv, S.goal.get(), S.start.get(), rows, S.path.get(), S.count.get(), S.status.get(),
-                              first_hit ? S.first_hit.get() : nullptr, s);
+  const size_t nq = (size_t)rows * dof, cap_q = (size_t)rows * std::max(dof, 1);
+  HostStage st{s, "screw"};
+  st.out(S.goal, 7 * (size_t)rows);
+  st.out(S.start, cap_q);
+  double* const d_path = st.out(S.path, cap_q * (size_t)o.max_waypoints);
+  uint8_t* const d_status = st.out(S.status, (size_t)rows);
+  int32_t* const d_count = st.out(S.count, (size_t)rows);
+  int32_t* const d_hit = st.out(S.first_hit, (size_t)rows);
+  const double* const d_goal = st.in(S.goal, goal, 7 * (size_t)rows);
+  const double* const d_start = st.in(S.start, q_start, nq);
+  if (st.rc) return st.rc;
+  const int rc = launch_screw(w, sv, d_goal, d_start, rows, d_path, d_count, d_status, first_hit ? d_hit : nullptr, s);
   if (rc) return rc;
-  if (dof)
-    HIP_TRY(hipMemcpyAsync(path, S.path.get(), sizeof(double) * rows * o.max_waypoints * dof, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(n_waypoints, S.count.get(), sizeof(int32_t) * rows, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(status, S.status.get(), (size_t)rows, hipMemcpyDeviceToHost, s));
-  if (first_hit) HIP_TRY(hipMemcpyAsync(first_hit, S.first_hit.get(), sizeof(int32_t) * rows, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return MPG_OK;
+  st.back(path, d_path, nq * (size_t)o.max_waypoints);
+  st.back(n_waypoints, d_count, (size_t)rows);
+  st.back(status, d_status, (size_t)rows);
+  if (first_hit) st.back(first_hit, d_hit, (size_t)rows);
+  return st.finish();
 }
 
 int mpg_debug_collide_pairs(mpg_world* w, int32_t geom_a, int32_t geom_b, int64_t n, const double* Ta,
@@ -871,12 +765,7 @@ int mpg_sample_uniform(const double* lower, const double* upper, int32_t dof, in
     return set_error(MPG_E_INVALID, "bad arguments");
   if (n == 0 || dof == 0) return MPG_OK;
   SampleRange r{};
-  for (int k = 0; k < dof; ++k) {
-    if (!(std::isfinite(lower[k]) && std::isfinite(upper[k]) && lower[k] <= upper[k]))
-      return set_error(MPG_E_INVALID, "sampling range must be finite with lower <= upper");
-    r.lo[k] = lower[k];
-    r.hi[k] = upper[k];
-  }
+  if (const char* why = mpg_args::fill_sample_range(r, lower, upper, dof)) return set_error(MPG_E_INVALID, why);
   HIP_TRY(hipSetDevice(device));
   DevBuf<double> d;
   HIP_TRY(d.reserve((size_t)n * dof));
@@ -899,12 +788,7 @@ int mpg_collide_count(mpg_world* w, const double* lower, const double* upper, in
   for (int p = 0; p < P; ++p) counts[p] = 0;
   if (n == 0 || P == 0) return MPG_OK;
   SampleRange r{};
-  for (int k = 0; k < dof; ++k) {
-    if (!(std::isfinite(lower[k]) && std::isfinite(upper[k]) && lower[k] <= upper[k]))
-      return set_error(MPG_E_INVALID, "sampling range must be finite with lower <= upper");
-    r.lo[k] = lower[k];
-    r.hi[k] = upper[k];
-  }
+  if (const char* why = mpg_args::fill_sample_range(r, lower, upper, dof)) return set_error(MPG_E_INVALID, why);
   HIP_TRY(hipSetDevice(w->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const long long chunk = std::min<long long>(n, w->max_chunk);

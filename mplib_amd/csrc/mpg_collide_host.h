@@ -443,7 +443,23 @@ int collide_host_pipelined(mpg_world* w, const double* q, int64_t n, uint8_t* fl
 
 int collide_free(mpg_world* w, const double* q, const double* free_pose, int64_t free_rows, int64_t n, uint8_t* flags,
                  uint32_t* pair_mask, int mem, void* stream);
-int check_free_poses(const double* p7, size_t count);
+// mpg_args_host.h's reasons as the entry points report them
+int bad_mem(int mem) { return mpg_args::mem_ok(mem) ? MPG_OK : set_error(MPG_E_INVALID, "bad mem kind"); }
+int pose_fault(mpg_args::PoseFault f, const char* what) {
+  return f ? set_error(MPG_E_INVALID, mpg_args::pose_message(f, what)) : MPG_OK;
+}
+// host-memory poses ("free pose", "goal pose"): finite values, unit quaternions within kFreeQuatTol
+int check_poses(const double* p7, size_t count, const char* what) {
+  return pose_fault(mpg_args::check_pose7(p7, count, kFreeQuatTol), what);
+}
+// host-memory link-pose rows: the free frames' columns are checked as every host-memory free pose is
+int check_free_columns(const mpg_world* w, const double* rows, int64_t n) {
+  return pose_fault(mpg_args::check_free_columns(rows, n, w->dw.n_links, w->dw.n_free, kFreeQuatTol), "free pose");
+}
+int check_free_args(const mpg_world* w, const double* free_pose, int64_t free_rows, int64_t n) {
+  const char* why = mpg_args::check_free_args(free_pose, free_rows, n, w->dw.n_free);
+  return why ? set_error(MPG_E_INVALID, why) : MPG_OK;
+}
 
 template <bool FROM_POSES>
 int collide_common(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uint32_t* pair_mask, int mem,
@@ -455,17 +471,12 @@ int collide_common(mpg_world* w, const double* q, int64_t n, uint8_t* flags, uin
   const size_t row = FROM_POSES ? (size_t)w->dw.n_links * 7 : (size_t)w->dw.dof;
   // a world without inputs (dof 0) may pass q = NULL
   if (n > 0 && ((!q && row > 0) || !flags)) return set_error(MPG_E_INVALID, "input/flags is NULL");
-  // host-memory link-pose rows: the free frames' columns are checked as every host-memory free pose is
-  if (FROM_POSES && mem == MPG_MEM_HOST && w->dw.n_free)
-    for (int64_t i = 0; i < n; ++i) {
-      const int rc = check_free_poses(q + ((size_t)i * w->dw.n_links + (w->dw.n_links - w->dw.n_free)) * 7,
-                                      (size_t)w->dw.n_free);
-      if (rc) return rc;
-    }
+  if (FROM_POSES && mem == MPG_MEM_HOST)
+    if (const int rc = check_free_columns(w, q, n)) return rc;
   HIP_TRY(hipSetDevice(w->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (mem == MPG_MEM_DEVICE) return launch_collide_overlapped<FROM_POSES>(w, q, n, flags, pair_mask, s);
-  if (mem != MPG_MEM_HOST) return set_error(MPG_E_INVALID, "bad mem kind");
+  if (const int rc = bad_mem(mem)) return rc;
   std::lock_guard<std::mutex> lk(w->host_mu);
   if (!s && w->own_stream) s = w->own_stream.get();
   if (n == 0) return MPG_OK;
@@ -526,32 +537,26 @@ int launch_collide_free(mpg_world* w, const double* q, const double* free_pose, 
   return MPG_OK;
 }
 
+// link-pose rows of n configurations: fk_kernel, or with free frames fk_free_kernel at free_pose (NULL: the
+// current poses; free_stride doubles per row).  (After launch_collide_free, where fk_free_kernel is first
+// used: the order of first uses is the order of the kernels in the code object.)
+int launch_fk(mpg_world* w, const double* q, long long n, double* out, hipStream_t s, const double* free_pose = nullptr,
+              long long free_stride = 0) {
+  const unsigned grid = (unsigned)((n + 127) / 128);
+  if (n && w->dw.n_free)
+    hipLaunchKernelGGL(fk_free_kernel<false>, dim3(grid), dim3(128), 0, s, w->dw, q, n, out, free_pose, free_stride,
+                       (const int32_t*)nullptr);
+  else if (n)
+    hipLaunchKernelGGL(fk_kernel, dim3(grid), dim3(128), 0, s, w->dw, q, n, out);
+  HIP_TRY(hipGetLastError());
+  return MPG_OK;
+}
+
 // joint-value rows on the device, evaluated at the world's current free poses
 int launch_collide_q(mpg_world* w, const double* q, long long n, uint8_t* flags, uint32_t* masks, hipStream_t s,
                      const ContactOut* co = nullptr) {
   if (w->dw.n_free) return launch_collide_free(w, q, nullptr, 0, n, flags, masks, s, co);
   return launch_collide<false>(w, q, n, flags, masks, s, co);
-}
-
-// finite values and unit quaternions (kFreeQuatTol) of host-memory free poses
-int check_free_poses(const double* p7, size_t count) {
-  for (size_t k = 0; k < count; ++k) {
-    const double* p = p7 + 7 * k;
-    if (!finite_all(p, 7)) return set_error(MPG_E_INVALID, "non-finite free pose");
-    const double nq = std::sqrt(p[3] * p[3] + p[4] * p[4] + p[5] * p[5] + p[6] * p[6]);
-    if (!(std::fabs(nq - 1.0) <= kFreeQuatTol))
-      return set_error(MPG_E_INVALID, "free pose quaternion is not of unit norm (within 1e-6)");
-  }
-  return MPG_OK;
-}
-
-// free_pose / free_rows of an entry point that takes the free poses per call
-// (n: its rows -- configurations, or edges)
-int check_free_args(const mpg_world* w, const double* free_pose, int64_t free_rows, int64_t n) {
-  if (free_pose && free_rows != 1 && free_rows != n)
-    return set_error(MPG_E_INVALID, "free_rows must be 1 (shared by the batch) or n (one pose set per row)");
-  if (free_pose && w->dw.n_free == 0) return set_error(MPG_E_INVALID, "the world has no free frames");
-  return MPG_OK;
 }
 
 // host buffers: rows staged to the device in passes of kFreeChunk; batches up
@@ -562,39 +567,29 @@ int collide_free_host(mpg_world* w, const double* q, const double* free_pose, lo
   const size_t dof = (size_t)w->dw.dof, frow = (size_t)w->dw.n_free * 7, lrow = (size_t)w->dw.n_links * 7;
   const size_t W = (size_t)w->dw.W;
   const long long chunk = std::min<long long>(n, kFreeChunk);
-  // no wait before a staging buffer is replaced: these calls are synchronous under host_mu
-  HIP_TRY(F.q.reserve(std::max<size_t>(1, dof * chunk)));
-  HIP_TRY(F.fp.reserve(frow * (free_rows > 1 ? chunk : 1)));
-  HIP_TRY(F.links.reserve(lrow * chunk));
+  HostStage st{s, "free-frame collide"};
+  st.out(F.q, std::max<size_t>(1, dof * chunk));
+  st.out(F.fp, frow * (free_rows > 1 ? chunk : 1));
+  double* const d_links = st.out(F.links, lrow * chunk);
   // the latency kernel reads all n rows at once: only a batch that one pass
   // assembles (small_batch_max may be set above kFreeChunk)
   const bool small = n <= w->small_max && n <= chunk;
-  if (!small) {
-    HIP_TRY(F.fl.reserve((size_t)chunk));
-    HIP_TRY(F.mk.reserve(W * chunk));
-  }
-  double *const d_q = F.q.get(), *const d_fp = F.fp.get(), *const d_links = F.links.get();
-  uint8_t* const d_fl = F.fl.get();
-  uint32_t* const d_mk = F.mk.get();
-  if (free_pose && free_rows == 1)
-    HIP_TRY(hipMemcpyAsync(d_fp, free_pose, sizeof(double) * frow, hipMemcpyHostToDevice, s));
-  int rc;
+  uint8_t* const d_fl = small ? nullptr : st.out(F.fl, (size_t)chunk);
+  uint32_t* const d_mk = small ? nullptr : st.out(F.mk, W * chunk);
+  const double* d_fp = free_pose && free_rows == 1 ? st.in(F.fp, free_pose, frow) : nullptr;
   for (long long off = 0; off < n; off += chunk) {
     const long long m = std::min<long long>(chunk, n - off);
-    if (dof) HIP_TRY(hipMemcpyAsync(d_q, q + (size_t)off * dof, sizeof(double) * dof * m, hipMemcpyHostToDevice, s));
-    if (free_pose && free_rows > 1)
-      HIP_TRY(hipMemcpyAsync(d_fp, free_pose + (size_t)off * frow, sizeof(double) * frow * m, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(fk_free_kernel<false>, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, w->dw, d_q, m,
-                       d_links, free_pose ? d_fp : nullptr, free_rows > 1 ? (long long)frow : 0ll,
-                       (const int32_t*)nullptr);
-    HIP_TRY(hipGetLastError());
+    const double* d_q = st.in(F.q, q + off * dof, dof * m);
+    if (free_pose && free_rows > 1) d_fp = st.in(F.fp, free_pose + off * frow, frow * m);
+    if (st.rc) return st.rc;
+    int rc = launch_fk(w, d_q, m, d_links, s, d_fp, free_rows > 1 ? (long long)frow : 0ll);
+    if (rc) return rc;
     if (small) return collide_small<true>(w, nullptr, n, flags, pair_mask, s, d_links);
     rc = launch_collide<true>(w, d_links, m, d_fl, pair_mask ? d_mk : nullptr, s);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(flags + off, d_fl, (size_t)m, hipMemcpyDeviceToHost, s));
-    if (pair_mask)
-      HIP_TRY(hipMemcpyAsync(pair_mask + (size_t)off * W, d_mk, sizeof(uint32_t) * W * m, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    st.back(flags + off, d_fl, (size_t)m);
+    if (pair_mask) st.back(pair_mask + off * W, d_mk, W * m);
+    if (st.finish()) return st.rc;
   }
   return MPG_OK;
 }
@@ -604,21 +599,37 @@ int collide_free(mpg_world* w, const double* q, const double* free_pose, int64_t
   if (!w) return set_error(MPG_E_INVALID, "world is NULL");
   if (n < 0) return set_error(MPG_E_INVALID, "n < 0");
   if (n > 0 && ((!q && w->dw.dof > 0) || !flags)) return set_error(MPG_E_INVALID, "input/flags is NULL");
-  if (mem != MPG_MEM_HOST && mem != MPG_MEM_DEVICE) return set_error(MPG_E_INVALID, "bad mem kind");
-  if (free_pose && free_rows != 1 && free_rows != n)
-    return set_error(MPG_E_INVALID, "free_rows must be 1 (shared by the batch) or n (one pose set per configuration)");
-  if (free_pose && w->dw.n_free == 0) return set_error(MPG_E_INVALID, "the world has no free frames");
+  if (const int rc = bad_mem(mem)) return rc;
+  if (const int rc = check_free_args(w, free_pose, free_rows, n)) return rc;
   if (w->dw.n_free == 0) return collide_common<false>(w, q, n, flags, pair_mask, mem, stream);
   HIP_TRY(hipSetDevice(w->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const long long fstride = free_rows > 1 ? (long long)w->dw.n_free * 7 : 0ll;
   if (mem == MPG_MEM_DEVICE) return launch_collide_free(w, q, free_pose, fstride, n, flags, pair_mask, s);
-  if (free_pose) {
-    const int rc = check_free_poses(free_pose, (size_t)free_rows * w->dw.n_free);
-    if (rc) return rc;
-  }
+  if (free_pose)
+    if (const int rc = check_poses(free_pose, (size_t)free_rows * w->dw.n_free, "free pose")) return rc;
   std::lock_guard<std::mutex> lk(w->host_mu);
   if (!s && w->own_stream) s = w->own_stream.get();
   if (n == 0) return MPG_OK;
   return collide_free_host(w, q, free_pose, free_rows, n, flags, pair_mask, s);
+}
+
+// The shards of a multi-world call, a thread per world (shard 0 on the
+// caller's): shard(k) returns its code with the error text set on its thread;
+// the first failure is reported as "world k: ...".
+template <class F>
+int run_shards(int n_worlds, F&& shard) {
+  std::vector<int> rc(n_worlds, MPG_OK);
+  std::vector<std::string> err(n_worlds);
+  auto run = [&](int k) {
+    rc[k] = shard(k);
+    if (rc[k]) err[k] = g_last_error;  // the worker thread's error text
+  };
+  std::vector<std::thread> th;
+  for (int k = 1; k < n_worlds; ++k) th.emplace_back(run, k);
+  run(0);
+  for (auto& t : th) t.join();
+  for (int k = 0; k < n_worlds; ++k)
+    if (rc[k]) return set_error(rc[k], "world " + std::to_string(k) + ": " + err[k]);
+  return MPG_OK;
 }

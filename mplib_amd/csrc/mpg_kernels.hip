@@ -48,6 +48,7 @@
 #include "mpg_screw.h"
 #include "mpg_bucket.h"
 #include "mpg_hostpipe.h"
+#include "mpg_args_host.h"
 
 using namespace mpg;
 
@@ -67,12 +68,6 @@ int set_error(int code, const std::string& msg) {
     if (_e != hipSuccess)                                                             \
       return set_error(MPG_E_HIP, std::string(#expr " failed: ") + hipGetErrorString(_e)); \
   } while (0)
-
-// ---------------------------------------------------------------------------
-// device snapshot
-// ---------------------------------------------------------------------------
-
-
 
 // ---------------------------------------------------------------------------
 // FCL GJK objects + libccd MPR

@@ -271,25 +271,43 @@ int launch_collide(mpg_world* w, const double* in, long long n, uint8_t* flags, 
   return MPG_OK;
 }
 
-int ensure_staging(mpg_world* w, size_t ncfg, size_t nout) {
-  // no wait: the calls that use the staging are synchronous under host_mu
-  if (ncfg > w->cap_cfg) {
-    w->d_q.reset();
-    w->d_flags.reset();
-    w->d_masks.reset();
-    w->cap_cfg = 0;
-    HIP_TRY(w->d_q.reserve(std::max<size_t>(1, ncfg * std::max(w->dw.dof, 1))));
-    HIP_TRY(w->d_flags.reserve(std::max<size_t>(1, ncfg)));
-    HIP_TRY(w->d_masks.reserve(std::max<size_t>(1, ncfg * w->dw.W)));
-    w->cap_cfg = ncfg;
+// The staging of one MPG_MEM_HOST call on stream s: grow-only device twins of
+// the caller's arrays.  It keeps the call's first error (a failed reserve is
+// MPG_E_NOMEM, a failed copy or wait MPG_E_HIP) and does nothing after one: a
+// caller checks rc once before it launches and returns finish().  last: the
+// world scratch's event (scratch_begin below), waited for before a buffer is
+// replaced; the stage structs under host_mu pass none (synchronous calls).
+struct HostStage {
+  hipStream_t s;
+  const char* what;  // "IK", "contact", ...: names the call in the error text
+  const Event* last = nullptr;
+  int rc = MPG_OK;
+  void check(hipError_t e, const char* step) {
+    if (!rc && e != hipSuccess)
+      rc = set_error(MPG_E_HIP, std::string(what) + " staging, " + step + ": " + hipGetErrorString(e));
   }
-  if (nout > w->cap_out) {
-    w->cap_out = 0;
-    HIP_TRY(w->d_out.reserve(nout));
-    w->cap_out = nout;
+  template <class T>
+  T* out(DevBuf<T>& buf, size_t count) {  // reserve: the device pointer
+    if (!rc && last && *last && buf.get() && buf.cap() < count)
+      check(hipEventSynchronize(last->get()), "wait for the previous call");  // the old block's last reader
+    if (!rc && buf.reserve(count) != hipSuccess) rc = set_error(MPG_E_NOMEM, std::string(what) + " staging buffers");
+    return rc ? nullptr : buf.get();
   }
-  return MPG_OK;
-}
+  template <class T>
+  T* in(DevBuf<T>& buf, const T* host, size_t count) {  // reserve, queue the copy in: the device pointer
+    T* const d = out(buf, count);
+    if (d && count) check(hipMemcpyAsync(d, host, sizeof(T) * count, hipMemcpyHostToDevice, s), "copy in");
+    return rc ? nullptr : d;
+  }
+  template <class T>
+  void back(T* host, const T* dev, size_t count) {  // queue the copy out
+    if (!rc && count) check(hipMemcpyAsync(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost, s), "copy out");
+  }
+  int finish() {  // the results are in the caller's arrays
+    if (!rc) check(hipStreamSynchronize(s), "synchronize");
+    return rc;
+  }
+};
 
 // World-owned scratch (distance, motion validation) used by calls on any
 // stream: a call's work waits for the previous call's (`last`, whatever its

@@ -46,13 +46,37 @@ struct mpg_world {
   } grid_info;
   int block = 128;
   size_t lds_bytes = 0;
-  // staging for MPG_MEM_HOST
+  // The staging of the MPG_MEM_HOST calls, a struct per family: grow-only
+  // device twins of the caller's arrays, filled and read back through a
+  // HostStage (mpg_streams_host.h).  One rule for all of them: the call holds
+  // host_mu and is synchronous, so a buffer is replaced without a wait.  (The
+  // host-buffer calls of distance and motion validation stage in their scratch
+  // below, under its own mutex and event.)
   std::mutex host_mu;
-  DevBuf<double> d_q, d_out;
-  DevBuf<uint8_t> d_flags;
-  DevBuf<uint32_t> d_masks;
-  size_t cap_cfg = 0;
-  size_t cap_out = 0;
+  struct FkStage {
+    DevBuf<double> q, out;
+  } fk_stage;
+  struct FreeStage {  // collide_batch of a world with free frames
+    DevBuf<double> q, fp, links;
+    DevBuf<uint8_t> fl;
+    DevBuf<uint32_t> mk;
+  } free_stage;
+  struct ContactStage {
+    DevBuf<double> in, out;
+    DevBuf<uint8_t> fl;
+    DevBuf<uint32_t> mk;
+    DevBuf<double> fp;  // host-memory free poses of the call
+  } contact;
+  struct IkStage {
+    DevBuf<double> goal, q, start, err;
+    DevBuf<uint8_t> status;
+    DevBuf<int32_t> iters;
+  } ik_stage;
+  struct ScrewStage {
+    DevBuf<double> goal, start, path;
+    DevBuf<uint8_t> status;
+    DevBuf<int32_t> count, first_hit;
+  } screw_stage;
   // phase A/B workspace, one per stream so concurrent streams never share it
   struct Workspace {
     DevBuf<uint32_t> surv;       // [W * cap] survivor bits, word-major
@@ -81,18 +105,12 @@ struct mpg_world {
   std::map<hipStream_t, Workspace> ws;
   // mpg_ik_batch: per caller stream the row counter ik_clik_kernel's lanes
   // claim rows from and the collide pass's flags (guarded by ws_mu, released
-  // with the stream's workspace); the staging of host-buffer calls (host_mu);
-  // host tables built by mpg_world_create
+  // with the stream's workspace); host tables built by mpg_world_create
   struct IkWork {
     DevBuf<unsigned long long> counter;
     DevBuf<uint8_t> flags;  // [rows]
   };
   std::map<hipStream_t, IkWork> ik_ws;
-  struct IkStage {
-    DevBuf<double> goal, q, start, err;
-    DevBuf<uint8_t> status;
-    DevBuf<int32_t> iters;
-  } ik_stage;
   struct IkTables {
     int cus = 256;
     std::vector<int> chain_start, chain_len, chain_joints, joint_q_source;
@@ -100,26 +118,14 @@ struct mpg_world {
     std::vector<unsigned char> kind, continuous;  // [dof] IKK_*, continuous joint
   } ik;
   // mpg_screw_batch: per caller stream the collide pass's flags of the padded
-  // path (guarded by ws_mu, released with the stream's workspace); the staging
-  // of host-buffer calls (host_mu)
+  // path (guarded by ws_mu, released with the stream's workspace)
   struct ScrewWork {
     DevBuf<uint8_t> flags;  // [rows * max_waypoints]
   };
   std::map<hipStream_t, ScrewWork> screw_ws;
-  struct ScrewStage {
-    DevBuf<double> goal, start, path;
-    DevBuf<uint8_t> status;
-    DevBuf<int32_t> count, first_hit;
-  } screw_stage;
   // free frames: the current poses (host copy; free_dev is the device buffer
-  // DevWorld::free_cur points to) and the grow-only staging of host-buffer
-  // calls (host_mu)
+  // DevWorld::free_cur points to)
   std::vector<double> free_host;
-  struct FreeStage {
-    DevBuf<double> q, fp, links;
-    DevBuf<uint8_t> fl;
-    DevBuf<uint32_t> mk;
-  } free_stage;
   // optional per-stage timing (mpg_profile_enable)
   struct Mark {
     int stage;
@@ -158,13 +164,6 @@ struct mpg_world {
     DevBuf<ccdx::BigPolytope> big;    // kBigPool EPA polytopes (distance_redo_kernel)
     DevBuf<unsigned> list;            // overflowed configurations: [count, ids...]
   } dist;
-  // host-buffer contact calls: grow-only device staging (guarded by host_mu)
-  struct ContactStage {
-    DevBuf<double> in, out;
-    DevBuf<uint8_t> fl;
-    DevBuf<uint32_t> mk;
-    DevBuf<double> fp;  // host-memory free poses of the call
-  } contact;
   std::mutex dist_mu;
   std::mutex prof_mu;
   bool prof = false;

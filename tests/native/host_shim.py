@@ -32,3 +32,17 @@ def walk_lib():
     if _walk is None:
         _walk = _build(os.path.join(_HERE, "walk_cells.cpp"), "mplib_amd_walk_cells")
     return _walk
+
+
+_args = None
+
+
+def args_lib():
+    """tests/native/args_host.cpp: mpg_args_host.h's shared argument checks on the host."""
+    global _args
+    if _args is None:
+        _args = _build(os.path.join(_HERE, "args_host.cpp"), "mplib_amd_args_host")
+        _args.args_check_free_args.restype = ctypes.c_char_p
+        _args.args_fill_sample_range.restype = ctypes.c_char_p
+        _args.args_ik_lds_bytes.restype = ctypes.c_ulong
+    return _args

@@ -26,6 +26,8 @@ pytestmark = pytest.mark.gpu
 KINDS = ("free", "static")
 ROWS = (3, 200, 1500, 5000, 3)  # server / latency path / host pipeline at small_batch_max 1024, then small again
 EDGES = (5, 200, 5)
+HOST_ROWS = (3, 200, 3)  # fk, IK, screw: their host staging grows once, then is reused while larger than needed
+HAND = "panda_hand"
 N_MAX = max(ROWS)
 
 
@@ -163,6 +165,44 @@ def motion(w, kind, n, dev, shared):
     return [v.astype(bool), f, s]
 
 
+def fk_rows(w, q):
+    """mpg_fk_batch on host buffers: [len(q), n_links, 7]."""
+    q = np.ascontiguousarray(q)
+    info = C.WorldInfo()
+    h = ctypes.c_void_p(w.device_handle())
+    C.check(C.lib().mpg_world_get_info(h, ctypes.byref(info)), "mpg_world_get_info")
+    out = np.zeros((len(q), info.n_links, 7))
+    C.check(C.lib().mpg_fk_batch(h, ptr(q), len(q), ptr(out), C.MPG_MEM_HOST, None), "mpg_fk_batch")
+    return out
+
+
+def fk(w, kind, n):
+    """Host buffers, as ik and screw below: what grows is the staging (their
+    device-buffer calls are tested in test_ik_batch.py and test_screw_batch.py)."""
+    return [fk_rows(w, inputs(kind)[0][:n])]
+
+
+@functools.lru_cache(maxsize=None)
+def hand_goals(kind):
+    """[max(HOST_ROWS), 7]: the hand's pose a tenth of the way from row i to row N_MAX - 1 - i."""
+    n = max(HOST_ROWS)
+    q = inputs(kind)[0]
+    w = make(kind)
+    goals = np.ascontiguousarray(fk_rows(w, 0.9 * q[:n] + 0.1 * q[::-1][:n])[:, w.ik_link_index(HAND)])
+    goals.setflags(write=False)
+    return goals
+
+
+def ik(w, kind, n):
+    """One seed per goal, given (nothing is sampled), 5 iterations."""
+    q0 = inputs(kind)[0][:n].reshape(n, 1, -1)
+    return list(w.ik_batch(HAND, hand_goals(kind)[:n], q_init=q0, max_iter=5))
+
+
+def screw(w, kind, n):
+    return list(w.plan_screw_batch(HAND, hand_goals(kind)[:n], inputs(kind)[0][:n], max_waypoints=8))
+
+
 def equal(got, want, msg):
     assert len(got) == len(want), msg
     for k, (g, r) in enumerate(zip(got, want)):
@@ -223,6 +263,43 @@ def test_motion_buffers_grow_in_place(kind):
         ref = grow_and_compare(kind, lambda w, n, dev: motion(w, kind, n, dev, shared), EDGES,
                                f"check_motion_batch ({'shared' if shared else 'per-edge'} poses)")
         assert 0 < int(ref[200][0].sum()) < 200
+
+
+def grow_host(kind, call, what):
+    """`call(world, kind, n)` on the long-lived world at HOST_ROWS, against a fresh world's call of that size."""
+    w = long_lived(kind)
+    ref = {}
+    for n in HOST_ROWS:
+        if n not in ref:
+            fresh = make(kind)
+            ref[n] = call(fresh, kind, n)
+            del fresh
+        equal(call(w, kind, n), ref[n], f"{what}, {kind} world, n = {n}")
+    return ref
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_fk_buffers_grow_in_place(kind):
+    ref = grow_host(kind, fk, "fk_batch")
+    assert np.abs(np.linalg.norm(ref[200][0][..., 3:], axis=-1) - 1.0).max() < 1e-9  # poses, not zeros
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_ik_buffers_grow_in_place(kind):
+    """(q, status, err, iters) of 3, 200 and 3 rows, at most 5 iterations each."""
+    ref = grow_host(kind, ik, "ik_batch")
+    q, status, err, iters = ref[200]
+    assert q.shape == (200, 1, 7) and np.isfinite(q).all()
+    assert (iters <= 5).all() and (iters > 0).any()  # the loop ran
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_screw_buffers_grow_in_place(kind):
+    """(path, n_waypoints, status, first_hit) of 3, 200 and 3 rows with max_waypoints = 8."""
+    ref = grow_host(kind, screw, "plan_screw_batch")
+    path, count, status, hit = ref[200]
+    assert path.shape == (200, 8, 7) and np.isfinite(path).all()
+    assert ((count >= 0) & (count <= 8)).all() and (count > 1).any()  # the loop ran
 
 
 # ---------------------------------------------------------------------------
