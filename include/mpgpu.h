@@ -589,6 +589,22 @@ int mpg_debug_collide_pairs(mpg_world *world, int32_t geom_a, int32_t geom_b, in
                             const double *Tb, uint8_t *hit);
 
 /*
+ * Diagnostics: the narrow-phase task list of the last bulk collide call
+ * (mpg_collide_batch above the latency path's sizes, mpg_collide_contacts,
+ * ...) on `stream`'s workspace, read after synchronising the stream: the
+ * number of tasks, the task size ts of the first level, the number of
+ * task-size levels in use (1 unless the batch holds more candidates than
+ * 4 * narrow blocks * 128: then the tasks shrink towards the end of the list)
+ * and the number of candidates.  Any output may be NULL.  stream NULL after
+ * host-buffer calls: the world's own stream.  The environment variable
+ * MPG_NARROW_BLOCKS (read by mpg_world_create, clamped to [1, the resident
+ * blocks of the narrow kernel]) shrinks the persistent narrow grid, so that
+ * small batches reach several levels.
+ */
+int mpg_debug_task_plan(mpg_world *world, void *stream, int64_t *tasks, int32_t *task_size, int32_t *levels,
+                        int64_t *candidates);
+
+/*
  * Planner.generate_collision_pair (mplib/planner.py:118-163), batched: n
  * configurations of the world's state drawn uniformly in [lower, upper]
  * (dof values each) on the device, evaluated as mpg_collide_batch does, and

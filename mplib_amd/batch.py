@@ -149,6 +149,16 @@ class DeviceWorld:
                 "mpg_cull_grid_info")
         return dict(objects=obj, partners=part, box=box, cells=cells.value, cell_edge=edge.value, built=bool(built.value))
 
+    def task_plan_info(self, stream: Optional[int] = None) -> dict:
+        """The narrow-phase task list of the last bulk collide call on
+        ``stream`` (mpg_debug_task_plan; synchronises the stream): ``tasks``,
+        ``task_size`` (first level), ``levels`` in use and ``candidates``."""
+        t, c = ctypes.c_int64(0), ctypes.c_int64(0)
+        ts, lv = ctypes.c_int32(0), ctypes.c_int32(0)
+        C.check(C.lib().mpg_debug_task_plan(self._h, ctypes.c_void_p(stream or 0), ctypes.byref(t), ctypes.byref(ts),
+                                            ctypes.byref(lv), ctypes.byref(c)), "mpg_debug_task_plan")
+        return dict(tasks=t.value, task_size=ts.value, levels=lv.value, candidates=c.value)
+
     def release_stream(self, stream: int):
         """Drop the workspace / side stream kept for a caller stream (call before destroying it)."""
         C.check(C.lib().mpg_release_stream(self._h, ctypes.c_void_p(int(stream))), "mpg_release_stream")

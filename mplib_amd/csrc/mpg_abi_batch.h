@@ -758,6 +758,30 @@ int mpg_debug_collide_pairs(mpg_world* w, int32_t geom_a, int32_t geom_b, int64_
   return MPG_OK;
 }
 
+int mpg_debug_task_plan(mpg_world* w, void* stream, int64_t* tasks, int32_t* task_size, int32_t* levels,
+                        int64_t* candidates) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  HIP_TRY(hipSetDevice(w->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const uint32_t* tail = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(w->ws_mu);
+    auto it = w->ws.find(s);
+    if (it == w->ws.end() && !s && w->own_stream) it = w->ws.find(s = w->own_stream.get());  // host-buffer calls
+    if (it == w->ws.end() || !it->second.prefix.get())
+      return set_error(MPG_E_INVALID, "the stream has no workspace: no bulk collide call has run on it");
+    tail = it->second.prefix.get() + std::max(w->dw.n_pairs, 0);
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  uint32_t h[kPrefixTail];
+  HIP_TRY(hipMemcpy(h, tail, sizeof(h), hipMemcpyDeviceToHost));
+  if (tasks) *tasks = h[0];
+  if (task_size) *task_size = (int32_t)h[2];
+  if (candidates) *candidates = h[3];
+  if (levels) *levels = (int32_t)bk_plan_load(h + 4).n;
+  return MPG_OK;
+}
+
 int mpg_sample_uniform(const double* lower, const double* upper, int32_t dof, int64_t n, uint64_t seed,
                        int64_t row_offset, double* q, int device) {
   if (dof < 0 || dof > kSampleMaxDof) return set_error(MPG_E_INVALID, "dof out of range [0, 64]");

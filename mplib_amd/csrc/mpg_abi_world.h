@@ -1005,6 +1005,9 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, narrow_kernel<false>, 256, 0) != hipSuccess || per_cu <= 0)
     per_cu = 2;
   w->narrow_blocks = cus * per_cu;
+  // a smaller grid (tests: a few thousand candidates then reach every level of the task plan)
+  if (const char* e = std::getenv("MPG_NARROW_BLOCKS"))
+    w->narrow_blocks = std::max(1, std::min(w->narrow_blocks, std::atoi(e)));
   // mpg_ik_batch's tables: host copies of the chains and, per dof slot, the
   // kind and limits of the joint behind it
   {

@@ -272,7 +272,9 @@ int launch_collide_overlapped(mpg_world* w, const double* in, long long n, uint8
   // one chunk or less runs on the caller's stream alone: its two halves'
   // cull and narrow kernels each fill the chip and are latency-bound, so on a
   // second stream they only time-share the CUs (cfg3, 2^20: single stream
-  // +0.7-1.3 %; cfg4, 4 chunks: overlapped +16 %, profiles/r05a/overlap_ab.txt)
+  // +0.7-1.3 %; cfg4, 4 chunks: overlapped +16 %, profiles/r05a/overlap_ab.txt).
+  // The 2^20 figure predates the tapered task list (mpg_bucket.h, bk_task_plan),
+  // which shortens a half batch's tail too; it has not been measured again.
   if (w->overlap_min <= 0 || n < w->overlap_min || n <= w->max_chunk)
     return launch_collide<FROM_POSES>(w, in, n, flags, masks, s);
   // one side stream and fork/join event pair per caller stream: callers on

@@ -1030,6 +1030,21 @@ __device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi
 #endif
 constexpr int kQueue = 128;  // entries per wave: < 64 pending + <= 64 pushed
 constexpr uint32_t kTask = MPG_TASK;  // narrow phase: candidates of one pair per wave task
+// taper of the task size towards the end of the task list (mpg_bucket.h,
+// bk_task_plan): a level starts where MPG_TAPER_C * target tasks * (the size
+// before it) candidates remain, sizes halve down to MPG_TAPER_MIN.  Measured
+// on cfg3 at 2^20 (profiles/r10a/taper_sweep.txt): tasks below 64 candidates
+// cost more in drained waves than the shorter tail returns (a task lasts
+// about one MPR's dependent chain however few candidates it holds), so the
+// product tapers the last quarter task per wave from 128 to 64 and no further.
+#ifndef MPG_TAPER_C
+#define MPG_TAPER_C 0.25
+#endif
+#ifndef MPG_TAPER_MIN
+#define MPG_TAPER_MIN 64
+#endif
+constexpr double kTaperC = MPG_TAPER_C;
+constexpr uint32_t kTaperMin = MPG_TAPER_MIN;
 
 // inclusive scan of one value per lane across the wave
 __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, uint32_t lane) {
@@ -1582,9 +1597,13 @@ __device__ __forceinline__ uint32_t block_sum1024(uint32_t v, uint32_t* red) {
 // ts = total candidates / target tasks (the narrow grid's resident waves),
 // clamped to [kTaskMin, kTask] and rounded up to a multiple of 8 -- small
 // batches (cfg2's 2^16 self pairs: ~27k candidates) spread over the whole
-// chip instead of a few hundred full waves.  prefix[n_pairs] = task count,
-// prefix[n_pairs + 1] = the narrow phase's task counter, prefix[n_pairs + 2]
-// = ts, prefix[n_pairs + 3] = the candidate count.
+// chip instead of a few hundred full waves.  A batch that hits the upper
+// clamp (more than target tasks * kTask candidates: cfg3's 2^20) gets a plan
+// of several levels, whose tasks shrink towards the end of the list so that
+// the persistent waves finish together (bk_task_plan).  prefix[n_pairs] = task
+// count, prefix[n_pairs + 1] = the narrow phase's task counter,
+// prefix[n_pairs + 2] = ts, prefix[n_pairs + 3] = the candidate count, then
+// the plan's kPlanWords words.
 __global__ __launch_bounds__(1024) void range_scan_kernel(const uint32_t* __restrict__ cnt, int n_tiles, int W,
                                                          uint32_t* __restrict__ part, uint32_t* __restrict__ grp,
                                                          int n_groups, int n_pairs, uint32_t* seg_len,
@@ -1652,40 +1671,44 @@ __global__ __launch_bounds__(1024) void range_scan_kernel(const uint32_t* __rest
   else
     for (int p = tid; p < n_pairs; p += 1024) psum += seg_len[p];
   const uint32_t all = block_sum1024(psum, red);
-  uint32_t ts = target_tasks ? (all + target_tasks - 1) / target_tasks : kTask;
-  ts = ts < kTaskMin ? kTaskMin : (ts > kTask ? kTask : ts);
-  ts = (ts + 7u) & ~7u;
+  const TaskPlan plan = bk_task_plan(all, target_tasks, kTaskMin, kTask, kTaperC, kTaperMin);
   uint32_t cl = 0, ct = 0;  // carries over rounds
   for (int p0 = 0; p0 < n_pairs; p0 += 1024) {
     const int p = p0 + tid;
     const uint32_t len = one ? my_len : (p < n_pairs ? seg_len[p] : 0u);
-    const uint32_t tasks = (len + ts - 1) / ts;
-    const uint32_t il = wave_inclusive_scan(len, lane), it = wave_inclusive_scan(tasks, lane);
-    if (lane == 63) {
-      wl[wv] = il;
-      wt[wv] = it;
-    }
+    const uint32_t il = wave_inclusive_scan(len, lane);
+    if (lane == 63) wl[wv] = il;
     __syncthreads();
-    uint32_t bl = cl, bt = ct;
-    for (uint32_t k = 0; k < wv; ++k) {
-      bl += wl[k];
-      bt += wt[k];
+    uint32_t bl = cl, bt = ct;  // candidates / tasks before this wave's pairs
+#pragma unroll
+    for (uint32_t k = 0; k < 16; ++k) {
+      const uint32_t x = wl[k];
+      bl += k < wv ? x : 0u;
+      cl += x;
+    }
+    const uint32_t start = bl + il - len;  // the pair's global candidate offset: its tasks follow the plan's levels
+    const uint32_t tasks = bk_pair_tasks(start, len, plan);
+    const uint32_t it = wave_inclusive_scan(tasks, lane);
+    if (lane == 63) wt[wv] = it;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < 16; ++k) {
+      const uint32_t x = wt[k];
+      bt += k < wv ? x : 0u;
+      ct += x;
     }
     if (p < n_pairs) {
-      seg_start[p] = bl + il - len;
+      seg_start[p] = start;
       prefix[p] = bt + it - tasks;
-    }
-    for (uint32_t k = 0; k < 16; ++k) {
-      cl += wl[k];
-      ct += wt[k];
     }
     __syncthreads();
   }
   if (threadIdx.x == 0) {
     prefix[n_pairs] = ct;
     prefix[n_pairs + 1] = 0;  // narrow-phase task counter
-    prefix[n_pairs + 2] = ts;
+    prefix[n_pairs + 2] = plan.s[0];
     prefix[n_pairs + 3] = cl;  // candidates in all (diagnostics)
+    bk_plan_store(plan, prefix + n_pairs + 4);
     if (units) atomicAdd(units, (unsigned long long)cl);  // profiling: narrow-phase candidates
   }
 }
@@ -1744,6 +1767,17 @@ __device__ __forceinline__ int task_pair(const uint32_t* __restrict__ prefix, in
   return lo;
 }
 
+// candidates [t0, t1) of task tk of pair p, local to the pair's list.  The
+// plan, the pair's start and its length are read here, per task (wave-uniform
+// scalar loads that hit the scalar cache): narrow_kernel keeps none of them
+// across its MPR loop, where it has no scalar registers to spare.
+__device__ __forceinline__ void task_range(const uint32_t* __restrict__ prefix, const uint32_t* __restrict__ seg_start,
+                                           const uint32_t* __restrict__ seg_len, int n_pairs, int p, uint32_t tk,
+                                           uint32_t& t0, uint32_t& t1) {
+  const TaskPlan plan = bk_plan_load(prefix + n_pairs + 4);
+  bk_task_range(seg_start[p], seg_len[p], tk - prefix[p], plan, &t0, &t1);
+}
+
 // ---------------------------------------------------------------------------
 // Phase B: exact narrow phase.  Each wave takes 64 candidates of ONE pair, so
 // every lane scans the same hull (wave-uniform scalar loads of the vertices)
@@ -1800,6 +1834,7 @@ __global__ __launch_bounds__(256, CLS == CLS_OCTREE ? 2 : 1) void closed_form_ke
   const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
   const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
   const uint32_t total = prefix[w.n_pairs];
+  const TaskPlan plan = bk_plan_load(prefix + w.n_pairs + 4);
   for (uint32_t tk = wave; tk < total; tk += n_waves) {
     int lo = 0, hi = w.n_pairs;
     while (hi - lo > 1) {
@@ -1810,8 +1845,8 @@ __global__ __launch_bounds__(256, CLS == CLS_OCTREE ? 2 : 1) void closed_form_ke
     const int p = lo;
     const int cf = w.pair_cf[p];
     if (cf == CF_NONE || cf_class(cf) != CLS) continue;
-    const uint32_t ts = prefix[w.n_pairs + 2];
-    const uint32_t t0 = (tk - prefix[p]) * ts, t1 = min(seg_len[p], t0 + ts);
+    uint32_t t0, t1;
+    bk_task_range(seg_start[p], seg_len[p], tk - prefix[p], plan, &t0, &t1);
     const int a = w.pair_a[p], b = w.pair_b[p];
     const bool am = a < w.n_moving, bm = b < w.n_moving;
     const int ga = am ? w.moving_geom[a] : w.static_geom[a - w.n_moving];
@@ -3011,7 +3046,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void n
   // (staging the hulls in LDS measured slower: +60 VGPRs, occupancy 4 -> 3)
   const cptr<double> HV = w.hull;
   const uint32_t lane = lane_id();
-  const uint32_t total = prefix[w.n_pairs], ts = prefix[w.n_pairs + 2];
+  const uint32_t total = prefix[w.n_pairs];
   __shared__ float s_stage[4][STG_N][64];
   __shared__ uint32_t s_cfg[4][64];
   float (*stg)[64] = s_stage[threadIdx.x >> 6];
@@ -3034,8 +3069,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void n
       tk = fetch();
       continue;
     }
-    uint32_t next = (tk - prefix[p]) * ts;  // wave-uniform cursor into the pair's candidates
-    uint32_t t1 = min(seg_len[p], next + ts);
+    uint32_t next, t1;  // wave-uniform cursor into the pair's candidates and the task's end
+    task_range(prefix, seg_start, seg_len, w.n_pairs, p, tk, next, t1);
     uint32_t pend = 0xffffffffu;  // a task of another pair, taken early: runs after this one
     bool more = true;             // the queue may still hold tasks
     const uint32_t* __restrict__ cl = cand + seg_start[p];
@@ -3068,8 +3103,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void n
         if (t2 >= total) {
           more = false;
         } else if (task_pair(prefix, w.n_pairs, t2) == p) {  // same pair: continue without draining
-          next = (t2 - prefix[p]) * ts;
-          t1 = min(seg_len[p], next + ts);
+          task_range(prefix, seg_start, seg_len, w.n_pairs, p, t2, next, t1);
         } else {
           pend = t2;
         }
@@ -6573,6 +6607,7 @@ __global__ __launch_bounds__(256) void contact_kernel(DevWorld w, const double* 
   const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
   const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
   const uint32_t total = prefix[w.n_pairs];
+  const TaskPlan plan = bk_plan_load(prefix + w.n_pairs + 4);
   for (uint32_t tk = wave; tk < total; tk += n_waves) {
     int lo = 0, hi = w.n_pairs;
     while (hi - lo > 1) {
@@ -6581,8 +6616,8 @@ __global__ __launch_bounds__(256) void contact_kernel(DevWorld w, const double* 
       else hi = mid;
     }
     const int p = lo;
-    const uint32_t ts = prefix[w.n_pairs + 2];
-    const uint32_t t0 = (tk - prefix[p]) * ts, t1 = min(seg_len[p], t0 + ts);
+    uint32_t t0, t1;
+    bk_task_range(seg_start[p], seg_len[p], tk - prefix[p], plan, &t0, &t1);
     const int a = w.pair_a[p], b = w.pair_b[p];
     for (uint32_t base = t0; base < t1; base += 64) {
       const uint32_t idx = base + lane;

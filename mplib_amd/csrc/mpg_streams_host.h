@@ -83,7 +83,7 @@ int get_workspace(mpg_world* w, hipStream_t s, long long want, mpg_world::Worksp
     HIP_TRY(ws.grp.reserve(bk_grp_words(w->dw.W, want)));
     HIP_TRY(ws.seg_len.reserve(np));
     HIP_TRY(ws.seg_start.reserve(np));
-    HIP_TRY(ws.prefix.reserve(np + 4));
+    HIP_TRY(ws.prefix.reserve(np + kPrefixTail));
     HIP_TRY(ws.cand.reserve((size_t)np * want));
     HIP_TRY(ws.rq.reserve((size_t)4 * std::max(w->dw.n_moving, 1) * want));
     HIP_TRY(ws.sc.reserve((size_t)2 * std::max(w->dw.dof, 1) * want));

@@ -85,7 +85,7 @@ struct mpg_world {
     DevBuf<uint32_t> grp;        // [n_groups][W * 32] group totals -> each group's base inside its pair
     DevBuf<uint32_t> seg_len;    // [n_pairs]
     DevBuf<uint32_t> seg_start;  // [n_pairs]
-    DevBuf<uint32_t> prefix;     // [n_pairs + 4] task prefix, task count, task counter, ts, candidates
+    DevBuf<uint32_t> prefix;     // [n_pairs + kPrefixTail] task prefix, task count, task counter, ts, candidates, task plan
     DevBuf<uint32_t> cand;       // [n_pairs * cap] worst case
     DevBuf<float> rq;            // [n_moving * 4 * cap] phase-A rotations (quaternions) for the SAT stage
     DevBuf<double> sc;           // [cap * dof * 2] exact joint (sin, cos) for phase B
