@@ -801,6 +801,10 @@ class Articulation:
                 g = load_convex_mesh(path, geom.scale) if convex else load_bvh_mesh(path, geom.scale)
             elif geom.kind == "box":
                 g = BoxGeom(geom.size)
+            elif geom.kind == "sphere":  # fcl_model.cpp:240-244
+                g = SphereGeom(geom.radius)
+            elif geom.kind == "cylinder":  # fcl_model.cpp:229-233: Cylinder(radius, length)
+                g = CylinderGeom(geom.radius, geom.length)
             else:
                 raise ValueError(f"oracle: unsupported link geometry {geom.kind}")
             self.objects.append(CollisionObj(link_name, parent, origin.se3(), g))

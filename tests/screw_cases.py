@@ -101,12 +101,13 @@ def pose2exp_coordinate(pose):
 
 
 # --- numpy restatement of planner.py:607-671 ---------------------------------
-def np_plan_screw(goal7, q0, qpos_step=0.1, solver="pinv", cap=REF_CAP, pin=None, fk=None, lim=None, pad=(0.0, 0.0)):
+def np_plan_screw(goal7, q0, qpos_step=0.1, solver="pinv", cap=REF_CAP, pin=None, fk=None, lim=None, pad=(0.0, 0.0),
+                  link=HAND):
     """(status bit, waypoints [count, len(q0)], sigma_min of J over the moving
     columns along the path, |dq| of every step).  solver: "pinv" as the
     reference, or "chol" for J^T (J J^T)^-1 by Cholesky (the stated deviation).
-    pin / fk / lim: another model's PinocchioModel, link pose function and
-    limits (default: the Panda)."""
+    pin / fk / lim / link: another model's PinocchioModel, link pose function,
+    limits and user link index (default: the Panda's hand)."""
     pin = K.pin_model() if pin is None else pin
     fk = (lambda q: K.hand_fk(q)[0][0]) if fk is None else fk
     lim = limits9() if lim is None else lim
@@ -121,7 +122,7 @@ def np_plan_screw(goal7, q0, qpos_step=0.1, solver="pinv", cap=REF_CAP, pin=None
     tw = tw.reshape(-1, 1)
     while True:
         pin.compute_full_jacobian(list(q))
-        J = np.asarray(pin.get_link_jacobian(HAND, False))
+        J = np.asarray(pin.get_link_jacobian(link, False))
         sig = min(sig, np.linalg.svd(J[:, :nd], compute_uv=False).min())
         if solver == "pinv":
             dq = np.linalg.pinv(J) @ tw

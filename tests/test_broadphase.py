@@ -42,8 +42,10 @@ def bp_objects(d, q):
     return out, rq
 
 
-def _check(q):
-    ow = Wd.oracle_world(3)
+def _check(q, ow=None):
+    """(dR, dRq, dp): the largest deviations of the fp32 object poses from the
+    oracle's on the rows q of world ow (default: the Panda box scene)."""
+    ow = Wd.oracle_world(3) if ow is None else ow
     d = Wd.desc_arrays(ow)
     f32, rq = bp_objects(d, q)
     _, objT = ow.fk_batch(q)

@@ -12,6 +12,7 @@ import pytest
 import worlds as Wd
 from mplib_amd import pymp, scenes
 from mplib_amd.batch import DeviceWorld, device_sincos
+from zoo import motion_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -241,31 +242,9 @@ def test_fcl_collide_free_function():
 # ------------------------------------------------------- batched motion validation
 def _motion_reference(q_from, q_to, lvs, ow_):
     """OMPL DiscreteMotionValidator semantics restated in numpy (RealVector
-    subspaces, weights 1) + the CPU oracle for every generated state."""
-    segs, states, owner = [], [], []
-    for e in range(len(q_from)):
-        a, b = q_from[e], q_to[e]
-        d = 0.0
-        for i in range(len(a)):
-            diff = a[i] - b[i]
-            d += 1.0 * float(np.sqrt(diff * diff))
-        m = max(1, int(np.ceil(d / lvs)))
-        segs.append(m)
-        for j in range(1, m + 1):
-            states.append(b.copy() if j == m else a + (b - a) * (j / m))
-            owner.append(e)
-    flags, _ = ow_.collide_batch(np.array(states), nthreads=NTHREADS)
-    valid = np.ones(len(q_from), bool)
-    first = np.full(len(q_from), -1, np.int32)
-    owner = np.array(owner)
-    pos = 0
-    for e, m in enumerate(segs):
-        f = flags[pos:pos + m]
-        if f.any():
-            valid[e] = False
-            first[e] = int(np.argmax(f)) + 1
-        pos += m
-    return valid, first, np.array(segs, np.int32)
+    subspaces, weights 1) + the CPU oracle for every generated state: the
+    shared zoo.motion_reference without SO2 components."""
+    return motion_reference(q_from, q_to, lvs, 0, ow_, nthreads=NTHREADS)
 
 
 def test_check_motion_batch_matches_oracle():
