@@ -780,6 +780,88 @@ int mpg_screw_batch(mpg_world *world, int32_t link, const double *goal /* [rows*
                     int32_t *first_hit /* [rows] or NULL */, int mem, void *stream);
 
 /*
+ * Planner.plan's RRTConnect (src/ompl_planner.cpp over OMPL 1.6.0
+ * RRTConnect::solve) for Q independent (start, goals) rows in one call: the
+ * rows advance in lockstep, one growTree call per row and round, and the states
+ * all their motion validators look at ride in one mpg_collide_batch pass per
+ * round on the same stream (movable objects at their current poses).  fp64, no
+ * fused multiply-add, no library call: a row's result is the same bits as the
+ * host build of mplib_amd/csrc/mpg_rrt.h with the same validity answers.
+ *
+ * State space.  Slot d of a state is an SO2 joint where bit d of so2_mask is
+ * set (bounds and sampling range [-pi, pi], distance and interpolation the
+ * short way round), else a real value within the snapshot's joint limits,
+ * which must be finite.  distance = sum over the slots, interpolate, equal,
+ * validSegmentCount and satisfiesBounds are OMPL's for a compound space of
+ * RealVector(1) / SO2 subspaces with weight 1.  extent = the sum of the
+ * slots' widths (pi for SO2), longestValidSegment = 0.01 extent, maxDistance =
+ * range, or 0.2 extent when range <= 1e-6.
+ *
+ * Rounds.  Iteration k (k = 0, 1, ...) draws a sample, grows the start tree
+ * (k even) or the goal tree (k odd) towards it from the exact nearest node
+ * (first strict minimum, ties to the lowest index), and on ADVANCED / REACHED
+ * grows the other tree towards the added state while that answers ADVANCED.
+ * growTree validates what OMPL's does: checkMotion(near, new) for the start
+ * tree, isValid(new) && checkMotion(new, near) for the goal tree, with the
+ * DiscreteMotionValidator's states.  REACHED while connecting ends the row:
+ * the path is start root .. connection .. goal root with the duplicate
+ * connection state removed.  Every growTree call is one round.
+ *
+ * Stated deviations from OMPL: (1) the sample of iteration k of a row is row k
+ * of mpg_sample_uniform(lo, hi, seed = the row's seed) -- the row's seed is
+ * row_seed[r], or splitmix64(seed + (r + 1) * 0x9E3779B97F4A7C15) without the
+ * array -- so a row depends on nothing but its own inputs and seed; (2) every
+ * goal of the row that is collision-free and within the bounds is a root of
+ * the goal tree before the first iteration, in the given order; (3) an invalid
+ * start ends the row with MPG_PLAN_START_INVALID, it is not resampled.
+ *
+ * status: MPG_PLAN_SOLVED; START_INVALID (bounds or collision); GOAL_INVALID
+ * (no goal survives); ROUNDS_EXHAUSTED (max_rounds rounds without a solution);
+ * NODES_EXHAUSTED (a node did not fit its tree of max_nodes, roots included);
+ * TRUNCATED (with SOLVED: the path has more than max_waypoints states;
+ * n_waypoints is 0).  path [Q * max_waypoints * dof]: the slots past
+ * n_waypoints repeat the last waypoint; a row without a path holds its start
+ * state in every slot.  iterations: the iterations a row started; tree_sizes
+ * [Q * 2]: nodes of the start and the goal tree.
+ *
+ * MPG_E_UNSUPPORTED: dof > 32.  MPG_E_INVALID: G outside [1, 16], max_nodes
+ * outside [2, 65536], max_waypoints outside [2, 4096], max_rounds < 1,
+ * check_every < 1, a non-finite range, an SO2 bit at or above dof, a slot
+ * without finite limits that is not SO2, Q * 2 * max_nodes * dof > 2^31 (the
+ * trees' doubles), Q * the round's states > 2^31, a NULL buffer with Q > 0,
+ * non-finite start / goal values (MPG_MEM_HOST).
+ *
+ * The host decides when to stop, so the call is not a pure enqueue: with
+ * MPG_MEM_DEVICE (start, goal, row_seed and the outputs in device memory) it
+ * synchronises `stream` once per check_every rounds, to read the count of
+ * unfinished rows, and once at the end; it stops when that count is 0 or
+ * after max_rounds rounds.  Results do not depend on check_every.
+ * MPG_MEM_HOST buffers are staged.
+ */
+#define MPG_PLAN_SOLVED 1
+#define MPG_PLAN_START_INVALID 2
+#define MPG_PLAN_GOAL_INVALID 4
+#define MPG_PLAN_ROUNDS_EXHAUSTED 8
+#define MPG_PLAN_NODES_EXHAUSTED 16
+#define MPG_PLAN_TRUNCATED 32
+
+typedef struct mpg_plan_options {
+  double range;          /* 0: 0.2 * extent (OMPL's default) */
+  int32_t max_rounds;    /* 20000; >= 1 */
+  int32_t max_nodes;     /* 2048 per tree; 2 .. 65536 */
+  int32_t max_waypoints; /* 256; 2 .. 4096 */
+  int32_t check_every;   /* 8; >= 1 */
+  uint64_t seed;         /* row seeds when row_seed is NULL */
+  uint32_t so2_mask;     /* bit d: state slot d is an SO2 joint */
+} mpg_plan_options;
+
+int mpg_plan_batch(mpg_world *world, const double *start /* [Q*dof] */, const double *goal /* [Q*G*dof] */, int64_t Q,
+                   int32_t G, const uint64_t *row_seed /* [Q] or NULL */,
+                   const mpg_plan_options *opt /* NULL = defaults */, double *path /* [Q*max_waypoints*dof] */,
+                   int32_t *n_waypoints /* [Q] */, uint8_t *status /* [Q] */, int32_t *iterations /* [Q] or NULL */,
+                   int32_t *tree_sizes /* [Q*2] or NULL */, int mem, void *stream);
+
+/*
  * Diagnostics (host only, no device): the FCL 0.7.0 BVHModel<OBBRSS> tree the
  * snapshot builds for a BVH mesh (BVHModel::endModel -> buildTree:
  * BVFitter<OBBRSS>::fit, SPLIT_METHOD_MEAN; OBB half), whose OBB tests gate

@@ -91,6 +91,21 @@ MPG_SCREW_SINGULAR = 32
 MPG_SCREW_ROT_PI = 64
 
 
+class PlanOptions(ctypes.Structure):
+    """mpg_plan_options (include/mpgpu.h); range 0 is OMPL's default, 0.2 x the space's extent."""
+    _fields_ = [("range", ctypes.c_double), ("max_rounds", ctypes.c_int32), ("max_nodes", ctypes.c_int32),
+                ("max_waypoints", ctypes.c_int32), ("check_every", ctypes.c_int32), ("seed", ctypes.c_uint64),
+                ("so2_mask", ctypes.c_uint32)]
+
+
+MPG_PLAN_SOLVED = 1
+MPG_PLAN_START_INVALID = 2
+MPG_PLAN_GOAL_INVALID = 4
+MPG_PLAN_ROUNDS_EXHAUSTED = 8
+MPG_PLAN_NODES_EXHAUSTED = 16
+MPG_PLAN_TRUNCATED = 32
+
+
 class WorldInfo(ctypes.Structure):
     _fields_ = [("n_pairs", ctypes.c_int32), ("mask_words", ctypes.c_int32), ("dof", ctypes.c_int32),
                 ("n_links", ctypes.c_int32), ("device", ctypes.c_int32), ("block_size", ctypes.c_int32),
@@ -164,6 +179,9 @@ SIGNATURES = {
     "mpg_screw_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.POINTER(ScrewOptions), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "mpg_plan_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                      ctypes.c_void_p, ctypes.POINTER(PlanOptions), ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "mpg_profile_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "mpg_profile_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
                                         ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_int]),

@@ -355,6 +355,73 @@ class DeviceWorld:
                                         hp(status), hp(hit), C.MPG_MEM_HOST, P(stream or 0)), "mpg_screw_batch")
         return path, count, status, hit
 
+    def plan_batch(self, start_qpos, goal_qpos, *, range: float = 0.0, max_rounds: int = 20000, max_nodes: int = 2048,
+                   max_waypoints: int = 256, seed: int = 0, row_seed=None, check_every: int = 8, so2_mask: int = 0,
+                   out=None, stream: Optional[int] = None):
+        """Planner.plan's RRTConnect for every (start state, goal states) row
+        in one call (mpg_plan_batch): the rows advance in lockstep, one
+        growTree per row and round, all their motion states in one
+        ``collide()`` pass per round.  ``so2_mask``: bit d marks state slot d
+        as an SO2 (continuous) joint; the other slots use the descriptor's
+        joint limits.
+        Host path (numpy ``start_qpos`` (dof,) for every row, or [Q, dof];
+        ``goal_qpos`` [Q, dof] or [Q, G, dof]; ``row_seed`` [Q] uint64 or
+        None): returns (path [Q, max_waypoints, dof], n_waypoints [Q] i32,
+        status [Q] u8 of ``_capi.MPG_PLAN_*`` bits, iterations [Q] i32,
+        tree_sizes [Q, 2] i32).  The slots of ``path`` past a row's count
+        repeat its last waypoint.
+        Device path (tensors with data_ptr(); ``start_qpos`` [Q, dof],
+        ``goal_qpos`` [Q, G, dof]): ``out`` = (path, n_waypoints, status,
+        iterations or None, tree_sizes or None) preallocated tensors, filled
+        on ``stream`` and returned.  The host decides when to stop, so the
+        call synchronises ``stream`` once per ``check_every`` rounds and once
+        at the end."""
+        o = C.PlanOptions(float(range), int(max_rounds), int(max_nodes), int(max_waypoints), int(check_every),
+                          int(seed), int(so2_mask))
+        P = ctypes.c_void_p
+        dof = max(self.dof, 1)
+        if hasattr(start_qpos, "data_ptr"):
+            Q = start_qpos.numel() // dof
+            if out is None:
+                raise ValueError("device path needs out=(path, n_waypoints, status, iterations, tree_sizes) preallocated")
+            if Q == 0 or goal_qpos.numel() % (Q * dof):
+                raise ValueError(f"goal_qpos must be [{Q}, G, {self.dof}]")
+            G = goal_qpos.numel() // (Q * dof)
+            path, count, status, iters, sizes = out
+            ptr = lambda t: P(t.data_ptr() if t is not None else 0)  # noqa: E731
+            C.check(C.lib().mpg_plan_batch(self._h, ptr(start_qpos), ptr(goal_qpos), Q, G, ptr(row_seed),
+                                           ctypes.byref(o), ptr(path), ptr(count), ptr(status), ptr(iters), ptr(sizes),
+                                           C.MPG_MEM_DEVICE, P(stream or 0)), "mpg_plan_batch")
+            return out
+        g = np.asarray(goal_qpos, dtype=np.float64)
+        if g.ndim == 2:
+            g = g[:, None, :]
+        if g.ndim != 3 or g.shape[2] != self.dof:
+            raise ValueError(f"goal_qpos must be [Q, {self.dof}] or [Q, G, {self.dof}]")
+        g = np.ascontiguousarray(g)
+        Q, G = g.shape[0], g.shape[1]
+        qs = np.asarray(start_qpos, dtype=np.float64)
+        if qs.ndim == 1 and qs.size == self.dof:
+            qs = np.broadcast_to(qs, (Q, self.dof))
+        if qs.shape != (Q, self.dof):
+            raise ValueError(f"start_qpos must be ({self.dof},) or [{Q}, {self.dof}]")
+        qs = np.ascontiguousarray(qs)
+        rs = None
+        if row_seed is not None:
+            rs = np.ascontiguousarray(np.asarray(row_seed, dtype=np.uint64).reshape(-1))
+            if rs.size != Q:
+                raise ValueError(f"row_seed must hold {Q} values")
+        path = np.zeros((Q, max(int(max_waypoints), 0), self.dof))
+        count = np.zeros(Q, np.int32)
+        status = np.zeros(Q, np.uint8)
+        iters = np.zeros(Q, np.int32)
+        sizes = np.zeros((Q, 2), np.int32)
+        hp = lambda a: P(a.ctypes.data if a is not None else 0)  # noqa: E731
+        C.check(C.lib().mpg_plan_batch(self._h, hp(qs), hp(g), Q, G, hp(rs), ctypes.byref(o), hp(path), hp(count),
+                                       hp(status), hp(iters), hp(sizes), C.MPG_MEM_HOST, P(stream or 0)),
+                "mpg_plan_batch")
+        return path, count, status, iters, sizes
+
 
 def device_sincos(x, device: int = 0):
     xa = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))

@@ -812,6 +812,11 @@ class PlanningWorld {
   void plan_screw_batch(int link, const double* goal_pose, const double* q_start, int64_t rows,
                         const mpg_screw_options& opt, double* path, int32_t* n_waypoints, uint8_t* status,
                         int32_t* first_hit, int mem, void* stream);
+  // Planner.plan's RRTConnect batched (mpg_plan_batch): Q (start, G goals) rows; opt.so2_mask is
+  // filled from motion_space(), the limits are the snapshot's (what OMPLPlanner's state space holds)
+  void plan_batch(const double* start, const double* goal, int64_t Q, int32_t G, const uint64_t* row_seed,
+                  mpg_plan_options opt, double* path, int32_t* n_waypoints, uint8_t* status, int32_t* iterations,
+                  int32_t* tree_sizes, int mem, void* stream);
   // batched OMPL motion validation over the planner's state space
   // (src/ompl_planner.cpp:248-293): SO2 dofs and the space's maximum extent
   struct MotionSpace {

@@ -1295,6 +1295,83 @@ PYBIND11_MODULE(pymp, m_all) {
            "Enqueue plan_screw_batch on device buffers (float64 goal poses [rows, 7], start states [rows, dim] -> "
            "float64 path [rows, max_waypoints, dim], int32 n_waypoints [rows], uint8 status [rows], optional int32 "
            "first_hit [rows]).  link: a world link index (ik_link_index).  No synchronisation.")
+      .def("plan_batch",
+           [](PW& w, py::array_t<double, py::array::c_style | py::array::forcecast> start_qpos,
+              py::array_t<double, py::array::c_style | py::array::forcecast> goal_qpos, double range, int max_rounds,
+              int max_nodes, int max_waypoints, uint64_t seed,
+              std::optional<py::array_t<uint64_t, py::array::c_style | py::array::forcecast>> row_seed,
+              int check_every) {
+             const int dim = w.state_dim();
+             int64_t Q = 0, G = 1;
+             if (goal_qpos.ndim() == 2 && goal_qpos.shape(1) == dim) Q = goal_qpos.shape(0);
+             else if (goal_qpos.ndim() == 3 && goal_qpos.shape(2) == dim) Q = goal_qpos.shape(0), G = goal_qpos.shape(1);
+             else
+               throw std::invalid_argument("goal_qpos must be [Q, " + std::to_string(dim) + "] or [Q, G, " +
+                                           std::to_string(dim) + "] float64");
+             const bool one = start_qpos.ndim() == 1 && start_qpos.shape(0) == dim;
+             if (!one && !(start_qpos.ndim() == 2 && start_qpos.shape(0) == Q && start_qpos.shape(1) == dim))
+               throw std::invalid_argument("start_qpos must be (" + std::to_string(dim) + ",) or [Q, " +
+                                           std::to_string(dim) + "] float64");
+             if (row_seed && (row_seed->ndim() != 1 || row_seed->shape(0) != Q))
+               throw std::invalid_argument("row_seed must hold Q uint64 values");
+             // refused before the outputs are sized by them
+             if (max_waypoints < 2 || max_waypoints > 4096)
+               throw std::invalid_argument("max_waypoints outside [2, 4096]");
+             if (G < 1 || G > 16) throw std::invalid_argument("G outside [1, 16]");
+             std::vector<double> qs;
+             if (one) {
+               qs.resize((size_t)Q * dim);
+               for (int64_t i = 0; i < Q; ++i) std::copy(start_qpos.data(), start_qpos.data() + dim, qs.begin() + i * dim);
+             }
+             mpg_plan_options o{range, max_rounds, max_nodes, max_waypoints, check_every, seed, 0};
+             py::array_t<double> path({(ssize_t)Q, (ssize_t)max_waypoints, (ssize_t)dim});
+             py::array_t<int32_t> count((ssize_t)Q), iters((ssize_t)Q), sizes({(ssize_t)Q, (ssize_t)2});
+             py::array_t<uint8_t> status((ssize_t)Q);
+             const double* sp = one ? qs.data() : start_qpos.data();
+             const double* gp = goal_qpos.data();
+             const uint64_t* rs = row_seed ? row_seed->data() : nullptr;
+             double* po = path.mutable_data();
+             int32_t *co = count.mutable_data(), *io = iters.mutable_data(), *zo = sizes.mutable_data();
+             uint8_t* so = status.mutable_data();
+             {
+               py::gil_scoped_release rel;
+               w.plan_batch(sp, gp, Q, (int32_t)G, rs, o, po, co, so, io, zo, MPG_MEM_HOST, nullptr);
+             }
+             return py::make_tuple(path, count, status, iters, sizes);
+           },
+           py::arg("start_qpos"), py::arg("goal_qpos"), py::kw_only(), py::arg("range") = 0.0,
+           py::arg("max_rounds") = 20000, py::arg("max_nodes") = 2048, py::arg("max_waypoints") = 256,
+           py::arg("seed") = 0, py::arg("row_seed") = py::none(), py::arg("check_every") = 8,
+           "Planner.plan's RRTConnect for Q (start state, goal states) rows in one device call (include/mpgpu.h "
+           "mpg_plan_batch): the rows' searches advance in lockstep, one growTree per row and round, all their motion "
+           "states in one collide() pass per round.  start_qpos: (dim,) for every row, or [Q, dim]; goal_qpos: [Q, dim] "
+           "or [Q, G, dim] (G <= 16 goals per row).  The state space is OMPLPlanner.get_state_space()'s; range 0: 0.2 x "
+           "its extent.  row_seed [Q] uint64: the rows' sampler seeds (default: derived from seed and the row index).  "
+           "Returns (path [Q, max_waypoints, dim], n_waypoints [Q] int32, status [Q] uint8 of MPG_PLAN_* bits, "
+           "iterations [Q] int32, tree_sizes [Q, 2] int32); the slots of path past a row's count repeat its last "
+           "waypoint; a row is solved when status == 1.")
+      .def("plan_batch_device",
+           [](PW& w, uintptr_t start_qpos, uintptr_t goal_qpos, int64_t rows, int goals, uintptr_t path,
+              uintptr_t n_waypoints, uintptr_t status, uintptr_t iterations, uintptr_t tree_sizes, uintptr_t row_seed,
+              uintptr_t stream, double range, int max_rounds, int max_nodes, int max_waypoints, uint64_t seed,
+              int check_every) {
+             mpg_plan_options o{range, max_rounds, max_nodes, max_waypoints, check_every, seed, 0};
+             py::gil_scoped_release rel;
+             w.plan_batch(reinterpret_cast<const double*>(start_qpos), reinterpret_cast<const double*>(goal_qpos), rows,
+                          goals, reinterpret_cast<const uint64_t*>(row_seed), o, reinterpret_cast<double*>(path),
+                          reinterpret_cast<int32_t*>(n_waypoints), reinterpret_cast<uint8_t*>(status),
+                          reinterpret_cast<int32_t*>(iterations), reinterpret_cast<int32_t*>(tree_sizes), MPG_MEM_DEVICE,
+                          reinterpret_cast<void*>(stream));
+           },
+           py::arg("start_qpos_ptr"), py::arg("goal_qpos_ptr"), py::arg("rows"), py::arg("goals"), py::arg("path_ptr"),
+           py::arg("n_waypoints_ptr"), py::arg("status_ptr"), py::arg("iterations_ptr") = 0,
+           py::arg("tree_sizes_ptr") = 0, py::arg("row_seed_ptr") = 0, py::arg("stream") = 0, py::arg("range") = 0.0,
+           py::arg("max_rounds") = 20000, py::arg("max_nodes") = 2048, py::arg("max_waypoints") = 256,
+           py::arg("seed") = 0, py::arg("check_every") = 8,
+           "plan_batch on device buffers (float64 start states [rows, dim], goal states [rows, goals, dim], optional "
+           "uint64 row seeds [rows] -> float64 path [rows, max_waypoints, dim], int32 n_waypoints [rows], uint8 status "
+           "[rows], optional int32 iterations [rows] and tree_sizes [rows, 2]).  Not a pure enqueue: the host decides "
+           "when to stop, so the call synchronises `stream` once per check_every rounds and once at the end.")
       .def("fk_link_pose",
            [](PW& w, py::array_t<double, py::array::c_style | py::array::forcecast> state, int link) {
              const int dim = w.state_dim();

@@ -770,6 +770,15 @@ void PlanningWorld::plan_screw_batch(int link, const double* goal_pose, const do
                                mem, stream),
                "mpg_screw_batch");
 }
+void PlanningWorld::plan_batch(const double* start, const double* goal, int64_t Q, int32_t G, const uint64_t* row_seed,
+                               mpg_plan_options opt, double* path, int32_t* n_waypoints, uint8_t* status,
+                               int32_t* iterations, int32_t* tree_sizes, int mem, void* stream) {
+  ensure_snapshot(CollisionRequest());
+  opt.so2_mask = motion_space().so2_mask;
+  check_status(mpg_plan_batch(world_->get(), start, goal, Q, G, row_seed, &opt, path, n_waypoints, status, iterations,
+                              tree_sizes, mem, stream),
+               "mpg_plan_batch");
+}
 void PlanningWorld::collide_batch(const double* q, int64_t n, uint8_t* flags, uint32_t* masks) {
   ensure_snapshot(CollisionRequest());
   check_status(mpg_collide_batch(world_->get(), q, n, flags, masks, MPG_MEM_HOST, nullptr), "mpg_collide_batch");

@@ -717,6 +717,140 @@ int mpg_screw_batch(mpg_world* w, int32_t link, const double* goal, const double
   return st.finish();
 }
 
+// what launch_plan queues on s: the roots and the first collide pass, then the
+// rounds -- propose, one collide pass over every row's slot block, commit -- as
+// plain launches, then the paths of the rows that connected.  Every
+// check_every rounds the host reads the count of rows that have not ended (one
+// synchronise) and stops at 0.
+static int plan_rounds(mpg_world* w, const RrtView& v, const RrtBufs& b, const double* start, const double* goal,
+                       long long Q, const uint64_t* row_seed, uint64_t seed, int check_every, double* path,
+                       int32_t* n_waypoints, uint8_t* status, int32_t* iterations, int32_t* tree_sizes, hipStream_t s) {
+  const size_t q = (size_t)Q;
+  const long long first = 1 + v.goals, per_round = v.block;
+  HIP_TRY(hipMemsetAsync(b.active, 0, sizeof(int32_t), s));
+  const long long vals = Q * first * v.dof;
+  if (vals > 0) {
+    hipLaunchKernelGGL(rrt_gather_kernel, dim3((unsigned)((vals + 255) / 256)), dim3(256), 0, s, v, Q, start, goal,
+                       b.slots);
+    HIP_TRY(hipGetLastError());
+  }
+  if (const int rc = mpg_collide_batch(w, b.slots, Q * first, b.flags, nullptr, MPG_MEM_DEVICE, s)) return rc;
+  const unsigned row_blocks = (unsigned)((Q + 63) / 64);
+  hipLaunchKernelGGL(rrt_init_kernel, dim3(row_blocks), dim3(64), 0, s, v, Q, start, goal, row_seed, seed, b,
+                     n_waypoints, status);
+  HIP_TRY(hipGetLastError());
+  const long long fill = Q * (per_round + v.max_waypoints) * v.dof;
+  if (fill > 0) {
+    hipLaunchKernelGGL(rrt_fill_kernel, dim3((unsigned)std::min<long long>((fill + 255) / 256, 1 << 20)), dim3(256), 0,
+                       s, v, Q, start, b.slots, path);
+    HIP_TRY(hipGetLastError());
+  }
+  int32_t active = 1;
+  for (int round = 0; round < v.max_rounds && active > 0; ++round) {
+    hipLaunchKernelGGL(rrt_propose_kernel, dim3((unsigned)Q), dim3(256), 0, s, v, b);
+    HIP_TRY(hipGetLastError());
+    if (const int rc = mpg_collide_batch(w, b.slots, Q * per_round, b.flags, nullptr, MPG_MEM_DEVICE, s)) return rc;
+    hipLaunchKernelGGL(rrt_commit_kernel, dim3(row_blocks), dim3(64), 0, s, v, Q, round, b, status);
+    HIP_TRY(hipGetLastError());
+    if ((round + 1) % check_every == 0) {
+      HIP_TRY(hipMemcpyAsync(&active, b.active, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+    }
+  }
+  hipLaunchKernelGGL(rrt_path_kernel, dim3((unsigned)Q), dim3(64), 0, s, v, b, path, n_waypoints, status);
+  HIP_TRY(hipGetLastError());
+  if (iterations) HIP_TRY(hipMemcpyAsync(iterations, b.iter, sizeof(int32_t) * q, hipMemcpyDeviceToDevice, s));
+  if (tree_sizes) HIP_TRY(hipMemcpyAsync(tree_sizes, b.sizes, sizeof(int32_t) * 2 * q, hipMemcpyDeviceToDevice, s));
+  return MPG_OK;
+}
+
+// device buffers: the stream's workspace, the rounds, and one synchronise at
+// the end -- after a failure too -- so the workspace is idle when the call
+// returns and the next call may replace its buffers.
+static int launch_plan(mpg_world* w, const RrtView& v, const double* start, const double* goal, long long Q,
+                       const uint64_t* row_seed, uint64_t seed, int check_every, double* path, int32_t* n_waypoints,
+                       uint8_t* status, int32_t* iterations, int32_t* tree_sizes, hipStream_t s) {
+  StreamPin pin(w, s);
+  mpg_world::PlanWork* K = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(w->ws_mu);
+    K = &w->plan_ws[s];
+  }
+  const size_t dof = (size_t)std::max(v.dof, 1), q = (size_t)Q;
+  const size_t slot_rows = q * (size_t)std::max(1 + v.goals, v.block);
+  HIP_TRY(K->nodes.reserve(q * 2 * v.max_nodes * dof));
+  HIP_TRY(K->parent.reserve(q * 2 * v.max_nodes));
+  HIP_TRY(K->newstate.reserve(q * dof));
+  HIP_TRY(K->slots.reserve(slot_rows * dof));
+  HIP_TRY(K->flags.reserve(slot_rows));
+  HIP_TRY(K->sizes.reserve(2 * q));
+  HIP_TRY(K->phase.reserve(q));
+  HIP_TRY(K->added.reserve(q));
+  HIP_TRY(K->iter.reserve(q));
+  HIP_TRY(K->prop.reserve(RRT_P_INTS * q));
+  HIP_TRY(K->seeds.reserve(q));
+  HIP_TRY(K->active.reserve(1));
+  const RrtBufs b{K->nodes.get(), K->parent.get(), K->sizes.get(), K->phase.get(),  K->added.get(), K->iter.get(),
+                  K->prop.get(),  K->newstate.get(), K->seeds.get(), K->slots.get(), K->flags.get(), K->active.get()};
+  const int rc = plan_rounds(w, v, b, start, goal, Q, row_seed, seed, check_every, path, n_waypoints, status, iterations,
+                             tree_sizes, s);
+  const hipError_t e = hipStreamSynchronize(s);
+  if (rc) return rc;
+  HIP_TRY(e);
+  return MPG_OK;
+}
+
+int mpg_plan_batch(mpg_world* w, const double* start, const double* goal, int64_t Q, int32_t G,
+                   const uint64_t* row_seed, const mpg_plan_options* opt, double* path, int32_t* n_waypoints,
+                   uint8_t* status, int32_t* iterations, int32_t* tree_sizes, int mem, void* stream) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  if (const int mrc = bad_mem(mem)) return mrc;
+  mpg_plan_options o{0.0, 20000, 2048, 256, 8, 0, 0};
+  if (opt) o = *opt;
+  const int dof = w->dw.dof;
+  RrtView v{};
+  bool unsupported = false;
+  const std::string why = mpg_args::fill_rrt_view(v, o, w->ik.lo.data(), w->ik.hi.data(), dof, Q, G, &unsupported);
+  if (!why.empty()) return set_error(unsupported ? MPG_E_UNSUPPORTED : MPG_E_INVALID, why);
+  if (Q > 0 && (!start || !goal || !path || !n_waypoints || !status))
+    return set_error(MPG_E_INVALID, "start / goal / path / n_waypoints / status is NULL");
+  if (mem == MPG_MEM_HOST && Q > 0) {
+    if (!finite_all(start, (size_t)Q * dof)) return set_error(MPG_E_INVALID, "non-finite start");
+    if (!finite_all(goal, (size_t)Q * G * dof)) return set_error(MPG_E_INVALID, "non-finite goal");
+  }
+  if (Q == 0) return MPG_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (mem == MPG_MEM_DEVICE)
+    return launch_plan(w, v, start, goal, Q, row_seed, o.seed, o.check_every, path, n_waypoints, status, iterations,
+                       tree_sizes, s);
+  std::lock_guard<std::mutex> lk(w->host_mu);
+  if (!s && w->own_stream) s = w->own_stream.get();
+  auto& S = w->plan_stage;
+  const size_t q = (size_t)Q, nq = q * dof, cap_q = q * std::max(dof, 1);
+  HostStage st{s, "plan"};
+  st.out(S.start, cap_q);
+  st.out(S.goal, cap_q * (size_t)G);
+  double* const d_path = st.out(S.path, cap_q * (size_t)o.max_waypoints);
+  uint8_t* const d_status = st.out(S.status, q);
+  int32_t* const d_count = st.out(S.count, q);
+  int32_t* const d_iters = st.out(S.iters, q);
+  int32_t* const d_sizes = st.out(S.sizes, 2 * q);
+  const double* const d_start = st.in(S.start, start, nq);
+  const double* const d_goal = st.in(S.goal, goal, nq * (size_t)G);
+  const uint64_t* const d_seed = row_seed ? st.in(S.row_seed, row_seed, q) : nullptr;
+  if (st.rc) return st.rc;
+  const int rc = launch_plan(w, v, d_start, d_goal, Q, d_seed, o.seed, o.check_every, d_path, d_count, d_status,
+                             iterations ? d_iters : nullptr, tree_sizes ? d_sizes : nullptr, s);
+  if (rc) return rc;
+  st.back(path, d_path, nq * (size_t)o.max_waypoints);
+  st.back(n_waypoints, d_count, q);
+  st.back(status, d_status, q);
+  if (iterations) st.back(iterations, d_iters, q);
+  if (tree_sizes) st.back(tree_sizes, d_sizes, 2 * q);
+  return st.finish();
+}
+
 int mpg_debug_collide_pairs(mpg_world* w, int32_t geom_a, int32_t geom_b, int64_t n, const double* Ta,
                             const double* Tb, uint8_t* hit) {
   if (!w || n < 0 || (n > 0 && (!Ta || !Tb || !hit))) return set_error(MPG_E_INVALID, "bad arguments");

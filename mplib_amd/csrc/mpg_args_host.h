@@ -11,6 +11,7 @@
 
 #include "../../include/mpgpu.h"
 #include "mpg_ik.h"
+#include "mpg_rrt.h"
 
 namespace mpg_args __attribute__((visibility("hidden"))) {  // nothing of it among the library's exports
 
@@ -81,6 +82,59 @@ void fill_ik_view(mpg::IkView& iv, const Tables& t, int link, int dof, const uin
     const int src = t.joint_q_source[t.chain_joints[iv.cs + k] - 1];
     iv.move[k] = src >= 0 && !iv.frozen[src];
   }
+}
+
+// mpg_plan_batch: the options against their limits, then the planner's view
+// from the dof slots' limits (lo / hi, as mpg_world::IkTables holds them) and
+// the SO2 bits.  An empty string, or the reason; *unsupported: it is
+// MPG_E_UNSUPPORTED's, not MPG_E_INVALID's.
+inline std::string fill_rrt_view(mpg::RrtView& v, const mpg_plan_options& o, const double* lo, const double* hi, int dof,
+                                 int64_t Q, int32_t G, bool* unsupported) {
+  *unsupported = false;
+  if (dof > mpg::kRrtDof) {
+    *unsupported = true;
+    return "mpg_plan_batch supports dof <= 32";
+  }
+  if (Q < 0) return "Q < 0";
+  if (G < 1 || G > mpg::kRrtGoals) return "G outside [1, 16]";
+  if (o.max_nodes < 2 || o.max_nodes > 65536) return "max_nodes outside [2, 65536]";
+  if (o.max_waypoints < 2 || o.max_waypoints > 4096) return "max_waypoints outside [2, 4096]";
+  if (o.max_rounds < 1) return "max_rounds < 1";
+  if (o.check_every < 1) return "check_every < 1";
+  if (!std::isfinite(o.range)) return "non-finite range";
+  if (dof < 32 && (o.so2_mask >> dof) != 0) return "so2_mask has a bit at or above dof";
+  v = mpg::RrtView{};
+  v.dof = dof;
+  v.goals = G;
+  v.max_rounds = o.max_rounds;
+  v.max_nodes = o.max_nodes;
+  v.max_waypoints = o.max_waypoints;
+  v.so2_mask = o.so2_mask;
+  double extent = 0.0;  // CompoundStateSpace::getMaximumExtent, weights 1
+  for (int d = 0; d < dof; ++d) {
+    if (mpg::rrt_so2(v, d)) {
+      v.lo[d] = -mpg::kRrtPi, v.hi[d] = mpg::kRrtPi;
+      extent += mpg::kRrtPi;
+      continue;
+    }
+    if (!(std::isfinite(lo[d]) && std::isfinite(hi[d]) && lo[d] <= hi[d]))
+      return "dof slot " + std::to_string(d) + ": a joint with neither finite limits nor an SO2 bit cannot be planned";
+    v.lo[d] = lo[d], v.hi[d] = hi[d];
+    extent += hi[d] - lo[d];
+  }
+  if (!(extent > 0.0)) return "the state space has no extent";
+  v.lvs = extent * 0.01;                               // SpaceInformation::setup
+  v.range = o.range > 1e-6 ? o.range : 0.2 * extent;  // SelfConfig::configurePlannerRange
+  const double segs = std::ceil(v.range / v.lvs);
+  if (!(segs < 1e6)) return "range / (0.01 * extent) exceeds 10^6 validator states per motion";
+  v.block = (int)segs + 2;  // goal tree: the new state, then the motion's; one more for a motion an ulp over range
+  const int64_t tree_doubles = (int64_t)2 * o.max_nodes * std::max(dof, 1);
+  if (Q > ((int64_t)1 << 31) / tree_doubles)
+    return "Q * 2 * max_nodes * dof = " + std::to_string(Q) + " * " + std::to_string(tree_doubles) +
+           " exceeds 2^31 doubles of tree storage";
+  if (Q > ((int64_t)1 << 31) / std::max(v.block, 1 + G))
+    return "Q * " + std::to_string(std::max(v.block, 1 + G)) + " states per round exceeds 2^31";
+  return std::string();
 }
 
 // dynamic LDS of ik_clik_kernel and screw_kernel (a wave per block): 64 lanes' slots and the tables of cl joints

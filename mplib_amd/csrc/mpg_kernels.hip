@@ -46,6 +46,7 @@
 #include "mpg_fk.h"
 #include "mpg_ik.h"
 #include "mpg_screw.h"
+#include "mpg_rrt.h"
 #include "mpg_bucket.h"
 #include "mpg_hostpipe.h"
 #include "mpg_args_host.h"
@@ -7031,6 +7032,157 @@ __global__ __launch_bounds__(256) void screw_fold_kernel(const uint8_t* __restri
     }
   if (hit < 0) status[row] |= MPG_SCREW_COLLISION_FREE;
   if (first_hit) first_hit[row] = hit;
+}
+
+// ---------------------------------------------------------------------------
+// Planner.plan's RRTConnect (ompl_planner.cpp over OMPL's RRTConnect::solve),
+// batched: mpg_plan_batch.  The per-row arithmetic is mpg_rrt.h's.  A round is
+// rrt_propose_kernel, one collide pass over every row's slot block,
+// rrt_commit_kernel; the host loops over the rounds (launch_plan).
+// ---------------------------------------------------------------------------
+// a call's workspace as the kernels take it (mpg_world::PlanWork), all per row
+struct RrtBufs {
+  double* nodes;     // [Q][2][max_nodes][dof]
+  int32_t* parent;   // [Q][2][max_nodes]
+  int32_t* sizes;    // [Q][2]
+  int32_t* phase;    // [Q] RRT_EXTEND / RRT_CONNECT / RRT_DONE
+  int32_t* added;    // [Q] the node the iteration's extension added
+  int32_t* iter;     // [Q] iterations started
+  int32_t* prop;     // [Q][RRT_P_INTS] the round's proposal
+  double* newstate;  // [Q][dof] the state it would add
+  uint64_t* seeds;   // [Q]
+  double* slots;     // [Q][block][dof] the states of the round's collide pass ([Q][1 + G][dof] at the start)
+  uint8_t* flags;    // their flags
+  int32_t* active;   // rows that have not ended
+};
+
+// start and goals of every row, packed for the first collide pass
+__global__ __launch_bounds__(256) void rrt_gather_kernel(RrtView v, long long Q, const double* __restrict__ start,
+                                                        const double* __restrict__ goal, double* __restrict__ slots) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long per = (long long)(1 + v.goals) * v.dof;
+  if (i >= Q * per) return;
+  const long long row = i / per, k = i % per;
+  slots[i] = k < v.dof ? start[row * v.dof + k] : goal[row * (long long)v.goals * v.dof + (k - v.dof)];
+}
+
+// a thread per row: the roots, the status of an invalid start / goal set, the
+// machine's first state (rrt_init_row); counts the rows that plan
+__global__ __launch_bounds__(64) void rrt_init_kernel(RrtView v, long long Q, const double* __restrict__ start,
+                                                     const double* __restrict__ goal,
+                                                     const uint64_t* __restrict__ row_seed, uint64_t seed, RrtBufs b,
+                                                     int32_t* __restrict__ n_waypoints, uint8_t* __restrict__ status) {
+  const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= Q) return;
+  const size_t tree = (size_t)2 * v.max_nodes;
+  b.seeds[row] = row_seed ? row_seed[row] : rrt_row_seed(seed, (uint64_t)row);
+  const bool plans = rrt_init_row(v, start + row * v.dof, goal + row * (long long)v.goals * v.dof,
+                                  b.flags + row * (1 + v.goals), b.nodes + row * tree * v.dof, b.parent + row * tree,
+                                  b.sizes + 2 * row, b.phase + row, b.added + row, b.iter + row,
+                                  b.prop + RRT_P_INTS * row, n_waypoints + row, status + row);
+  if (plans) atomicAdd(b.active, 1);
+}
+
+// every row's slot block and path start as copies of its start state, so the
+// collide passes and a row without a path see finite states: a thread per
+// value (grid-stride), after the first collide pass has read the slots
+__global__ __launch_bounds__(256) void rrt_fill_kernel(RrtView v, long long Q, const double* __restrict__ start,
+                                                      double* __restrict__ slots, double* __restrict__ path) {
+  const long long per = (long long)(v.block + v.max_waypoints) * v.dof, tot = Q * per;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (long long)gridDim.x * blockDim.x) {
+    const long long row = i / per, k = i % per;
+    *rrt_fill_start(v, k, slots + row * (long long)v.block * v.dof, path + row * (long long)v.max_waypoints * v.dof) =
+        start[row * v.dof + k % v.dof];
+  }
+}
+
+// A workgroup per row.  Thread 0 draws the sample or takes the connect target;
+// every thread scans a strided share of the tree (node-major, so the
+// workgroup reads contiguous memory) for the first strict minimum of the
+// distance, summed in dimension order as on the host; the reduction orders
+// (distance, index) lexicographically, which is the serial scan's "first
+// strict minimum".  Thread 0 steers, then the threads write the motion's
+// states into the row's slot block (the slots past the count repeat slot 0).
+// Every loop is bounded by max_nodes, dof or the block size.
+__global__ __launch_bounds__(256) void rrt_propose_kernel(RrtView v, RrtBufs b) {
+  __shared__ double s_target[kRrtDof], s_ds[kRrtDof], s_bd[4];
+  __shared__ int s_bi[4], s_meta[4];  // tree, nearest node, segments, states
+  const long long row = blockIdx.x;
+  if (b.phase[row] == RRT_DONE) return;  // the whole workgroup
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  double* const nodes = b.nodes + (size_t)row * 2 * v.max_nodes * v.dof;
+  if (tid == 0)
+    s_meta[0] = rrt_target(v, b.seeds[row], b.phase[row], b.iter + row, b.added[row], nodes, s_target);
+  __syncthreads();
+  const int tree = s_meta[0];
+  const double* const tn = rrt_node(v, nodes, tree, 0);
+  int n = b.sizes[2 * row + tree];
+  n = n < v.max_nodes ? n : v.max_nodes;
+  double bd = INFINITY;
+  int bi = 0x7fffffff;
+  rrt_nearest_scan(v, tn, n, s_target, tid, 256, &bd, &bi);
+  for (int o = 32; o > 0; o >>= 1) {
+    const double od = __shfl_xor(bd, o);
+    const int oi = __shfl_xor(bi, o);
+    if (rrt_nearer(od, oi, bd, bi)) bd = od, bi = oi;
+  }
+  if (lane == 0) s_bd[wv] = bd, s_bi[wv] = bi;
+  __syncthreads();
+  if (tid == 0) {
+    for (int k = 1; k < 4; ++k)
+      if (rrt_nearer(s_bd[k], s_bi[k], bd, bi)) bd = s_bd[k], bi = s_bi[k];
+    if (bi >= n) bi = 0;  // no finite distance: the serial scan's initial answer
+    int32_t* const prop = b.prop + RRT_P_INTS * row;
+    s_meta[1] = bi;
+    s_meta[2] = rrt_steer(v, tree, tn + (size_t)bi * v.dof, bi, s_target, s_ds, prop);
+    s_meta[3] = prop[RRT_P_COUNT];
+    rrt_copy(v.dof, s_ds, b.newstate + row * v.dof);
+  }
+  __syncthreads();
+  const double* const near = tn + (size_t)s_meta[1] * v.dof;
+  const int nd = s_meta[2], count = s_meta[3];
+  double* const slots = b.slots + row * (long long)v.block * v.dof;
+  for (int s = tid; s < v.block; s += 256)
+    rrt_slot_state(v, tree, near, s_ds, nd, s < count ? s : 0, slots + (size_t)s * v.dof);
+}
+
+// a thread per row: growTree's answer from the block's flags, the node, the
+// next state of the machine and the status of a row that ends (rrt_commit);
+// the rows that end leave the count of active rows
+__global__ __launch_bounds__(64) void rrt_commit_kernel(RrtView v, long long Q, int round, RrtBufs b,
+                                                       uint8_t* __restrict__ status) {
+  const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= Q) return;
+  const size_t tree = (size_t)2 * v.max_nodes;
+  const bool ended = rrt_commit(v, round, b.prop + RRT_P_INTS * row, b.newstate + row * v.dof,
+                                b.flags + row * (long long)v.block, b.nodes + row * tree * v.dof, b.parent + row * tree,
+                                b.sizes + 2 * row, b.phase + row, b.added + row, status + row);
+  if (ended) atomicSub(b.active, 1);
+}
+
+// after the last round, a wave per row: lane 0 of a solved row walks the two
+// parent chains into the waypoints' node indices (LDS; at most max_waypoints
+// <= 4096 of them, each walk bounded by max_nodes steps), then the lanes copy
+// the path's slots (rrt_finish_row's steps).  A path longer than
+// max_waypoints sets MPG_PLAN_TRUNCATED and leaves the count 0.
+__global__ __launch_bounds__(64) void rrt_path_kernel(RrtView v, RrtBufs b, double* __restrict__ path,
+                                                     int32_t* __restrict__ n_waypoints, uint8_t* __restrict__ status) {
+  __shared__ int32_t s_idx[4096];
+  __shared__ int s_n;
+  const long long row = blockIdx.x;
+  if (!(status[row] & MPG_PLAN_SOLVED)) return;  // the whole wave
+  const size_t tree = (size_t)2 * v.max_nodes;
+  if (threadIdx.x == 0) {
+    const int32_t* prop = b.prop + RRT_P_INTS * row;
+    s_n = rrt_path_indices(v, b.parent + row * tree, prop[RRT_P_SM], prop[RRT_P_GM], s_idx);
+    if (s_n < 0) status[row] |= MPG_PLAN_TRUNCATED;
+    else n_waypoints[row] = s_n;
+  }
+  __syncthreads();
+  const int n = s_n;
+  if (n < 0) return;
+  double* const out = path + row * (long long)v.max_waypoints * v.dof;
+  for (int p = threadIdx.x; p < v.max_waypoints; p += 64) rrt_path_slot(v, b.nodes + row * tree * v.dof, s_idx, n, p, out);
 }
 
 // per pair, the configurations whose pair mask has its bit: LDS counters per

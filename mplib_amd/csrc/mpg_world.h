@@ -77,6 +77,12 @@ struct mpg_world {
     DevBuf<uint8_t> status;
     DevBuf<int32_t> count, first_hit;
   } screw_stage;
+  struct PlanStage {
+    DevBuf<double> start, goal, path;
+    DevBuf<uint64_t> row_seed;
+    DevBuf<uint8_t> status;
+    DevBuf<int32_t> count, iters, sizes;
+  } plan_stage;
   // phase A/B workspace, one per stream so concurrent streams never share it
   struct Workspace {
     DevBuf<uint32_t> surv;       // [W * cap] survivor bits, word-major
@@ -123,6 +129,17 @@ struct mpg_world {
     DevBuf<uint8_t> flags;  // [rows * max_waypoints]
   };
   std::map<hipStream_t, ScrewWork> screw_ws;
+  // mpg_plan_batch: per caller stream the rows' trees, machines and slot
+  // blocks (RrtBufs in mpg_kernels.hip; guarded by ws_mu, released with the
+  // stream's workspace).  The call ends with a synchronise, so nothing queued
+  // reads a buffer when the next call replaces it.
+  struct PlanWork {
+    DevBuf<double> nodes, newstate, slots;
+    DevBuf<int32_t> parent, sizes, phase, added, iter, prop, active;
+    DevBuf<uint64_t> seeds;
+    DevBuf<uint8_t> flags;
+  };
+  std::map<hipStream_t, PlanWork> plan_ws;
   // free frames: the current poses (host copy; free_dev is the device buffer
   // DevWorld::free_cur points to)
   std::vector<double> free_host;

@@ -233,3 +233,72 @@ def plan_screw(world, link, goal_pose, current_qpos, qpos_step: float = 0.1, *, 
         else:
             out.append({"status": "screw plan failed", "reason": screw_reason(status[i], hit[i])})
     return out[0] if single else out
+
+
+# ---------------------------------------------------------------------------
+# Planner.plan (planner.py:358-524) without its time parametrisation: the
+# RRTConnect searches of many (start, goals) rows in one device call
+# (PlanningWorld.plan_batch, C ABI mpg_plan_batch), and the IK in front of
+# them for goals given as poses.
+# ---------------------------------------------------------------------------
+PLAN_SOLVED, PLAN_START_INVALID, PLAN_GOAL_INVALID = 1, 2, 4
+PLAN_ROUNDS_EXHAUSTED, PLAN_NODES_EXHAUSTED, PLAN_TRUNCATED = 8, 16, 32
+_PLAN_REASONS = ((PLAN_START_INVALID, "START_INVALID"), (PLAN_GOAL_INVALID, "GOAL_INVALID"),
+                 (PLAN_ROUNDS_EXHAUSTED, "ROUNDS_EXHAUSTED"), (PLAN_NODES_EXHAUSTED, "NODES_EXHAUSTED"),
+                 (PLAN_TRUNCATED, "TRUNCATED"))
+
+
+def plan_reason(status: int) -> str:
+    """Why a row of plan_batch is not a Success: the names of its status bits."""
+    return ", ".join(n for b, n in _PLAN_REASONS if int(status) & b)
+
+
+def plan_batch(world, start_qpos, goal_qpos, *, range: float = 0.0, max_rounds: int = 20000, max_nodes: int = 2048,
+               max_waypoints: int = 256, seed: int = 0, row_seed=None, check_every: int = 8):
+    """Planner.plan's RRTConnect for many queries in one device call:
+    ``goal_qpos`` [Q, dof] (one goal state per row) or [Q, G, dof], every row
+    starting at ``start_qpos`` ((dof,) or [Q, dof]).  Returns per row {"status":
+    "Success", "path": [count, dof]} or {"status": "plan failed", "reason":
+    names of the status bits}.  The paths are RRTConnect's, neither simplified
+    nor time-parametrised.  The articulations' qpos is not touched."""
+    path, count, status, _, _ = world.plan_batch(np.asarray(start_qpos, np.float64), np.asarray(goal_qpos, np.float64),
+                                                 range=float(range), max_rounds=int(max_rounds),
+                                                 max_nodes=int(max_nodes), max_waypoints=int(max_waypoints),
+                                                 seed=int(seed), row_seed=row_seed, check_every=int(check_every))
+    out = []
+    for i in np.arange(len(status)):
+        if int(status[i]) == PLAN_SOLVED:
+            out.append({"status": "Success", "path": path[i, :count[i]].copy()})
+        else:
+            out.append({"status": "plan failed", "reason": plan_reason(status[i])})
+    return out
+
+
+def plan_to_pose_batch(world, link, goal_poses, start_qpos, *, max_goals: int = 4, n_init_qpos: int = 20,
+                       threshold: float = 1e-3, ik_seed: int = 0, **plan_options):
+    """What Planner.plan does before TOPP-RA, for M goal poses [M, 7] of
+    ``link`` at once: one ik_batch call (``n_init_qpos`` seeds per pose, seed 0
+    = ``start_qpos`` (dof,)), up to ``max_goals`` of each pose's valid answers
+    (Planner.IK's selection: seed order, none within 0.1 of an earlier one) as
+    the row's goal states, then one plan_batch call over the poses that have
+    an answer.  Returns per pose plan_batch's dictionary, or {"status": "IK
+    failed", "reason": Planner.IK's message}.  ``plan_options``: plan_batch's."""
+    goals = np.asarray(goal_poses, np.float64).reshape(-1, 7)
+    start = np.asarray(start_qpos, np.float64).reshape(-1)
+    q, status, _, _ = world.ik_batch(link, goals, start_qpos=start, n_init_qpos=int(n_init_qpos), seed=int(ik_seed),
+                                     threshold=float(threshold))
+    out = [None] * len(goals)
+    rows, states = [], []
+    G = max(1, min(int(max_goals), 16))
+    for g in np.arange(len(goals)):
+        msg, kept = select_ik(q[g], status[g], start, threshold=threshold)
+        if kept is None:
+            out[g] = {"status": "IK failed", "reason": msg}
+            continue
+        kept = kept[:G]
+        rows.append(int(g))
+        states.append(np.array(kept + [kept[0]] * (G - len(kept))))  # a repeated goal is a second root on the same state
+    if rows:
+        for g, res in zip(rows, plan_batch(world, start, np.array(states), **plan_options)):
+            out[g] = res
+    return out
