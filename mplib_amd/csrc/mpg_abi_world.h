@@ -440,16 +440,25 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
   }
   // phase-A schedule: non-allowed pairs grouped by their lower moving object
   // ---- culling margins: pairs that can reach libccd MPR (directly, on octree
-  // leaves or on mesh triangles) keep everything within its false-hit reach
-  bool may_mpr = false;
+  // leaves or on mesh triangles) keep everything within its false-hit reach.
+  // MPR's own tolerance cannot add to that reach: a larger gjk_tolerance only
+  // ends refinePortal earlier, with "no intersection" (it never gains a hit).
+  // FCL's own GJK (CF_GJK pairs) is the other way round: evaluate() reports
+  // Inside as soon as its ray is shorter than gjk_tolerance, and the ray's
+  // length bounds the true separation from above, so it reports shapes up to
+  // gjk_tolerance apart -- the margins of a world with such a pair cover that
+  // too (at the default 1e-6 the libccd reach is the larger one, as before).
+  bool may_mpr = false, may_gjk = false;
   for (int p = 0; p < d->n_pairs; ++p) {
     if (allowed[p]) continue;
     const int ta = obj_geom_type(d, d->pair_a[p]), tb = obj_geom_type(d, d->pair_b[p]);
     const bool closed = pair_cf[p] != CF_NONE && cf_class(pair_cf[p]) == CLS_CLOSED;
     const bool mesh_mesh = ta == MPG_GEOM_MESH && tb == MPG_GEOM_MESH;
     may_mpr |= !closed && !mesh_mesh;
+    may_gjk |= pair_cf[p] == CF_GJK;
   }
-  const double reach = kCcdFalseHitReach * (1.0 + 1e-3) + 1e-5;
+  double reach = kCcdFalseHitReach * (1.0 + 1e-3) + 1e-5;
+  if (may_gjk) reach = std::max(reach, d->gjk_tolerance * (1.0 + 1e-3) + 1e-5);
   float bp_margin = may_mpr ? (float)std::max((double)kBpMargin, reach) : kBpMargin;
   // The travel of each prismatic joint: a move-group joint's value bound from
   // its limits (kDefaultTravel when unbounded), a fixed joint's own value.

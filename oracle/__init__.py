@@ -168,6 +168,7 @@ class _World(ctypes.Structure):
         ("conv_nbr", _IP),
         ("bvh", ctypes.c_void_p),
         ("gjk_solver", ctypes.c_int),
+        ("gjk_tolerance", ctypes.c_double),
     ]
 
 
@@ -201,9 +202,13 @@ class OracleWorld:
 
     def __init__(self, art: M.Articulation, scene: Sequence[Tuple[str, object, tuple]] = (),
                  attached: Sequence[Tuple[str, int, object, tuple]] = (),
-                 allowed: Sequence[Tuple[str, str]] = (), gjk_solver: str = "libccd"):
+                 allowed: Sequence[Tuple[str, str]] = (), gjk_solver: str = "libccd",
+                 gjk_tolerance: float = 1e-6):
         if gjk_solver not in ("libccd", "indep"):
             raise ValueError(gjk_solver)
+        if not gjk_tolerance > 0:
+            raise ValueError(gjk_tolerance)
+        self.gjk_tolerance = float(gjk_tolerance)  # CollisionRequest::gjk_tolerance (collide and contacts)
         self.gjk_solver = gjk_solver      # CollisionRequest::gjk_solver_type (GST_LIBCCD / GST_INDEP)
         self.art = art
         self.scene = list(scene)          # (name, geom, SE3)
@@ -365,6 +370,7 @@ class OracleWorld:
         w.conv_nbr = ia(nbr_all)
         w.bvh = None
         w.gjk_solver = 1 if getattr(self, "gjk_solver", "libccd") == "indep" else 0
+        w.gjk_tolerance = getattr(self, "gjk_tolerance", 1e-6)
         if lib().orc_bvh_build(ctypes.byref(w)):  # FCL BVHModel<OBBRSS> trees, octree nodes, shape OBBs
             raise ValueError("octree leaves off FCL's root-BV halving grid")
         self._w = w

@@ -127,6 +127,15 @@ typedef struct {
     /* CollisionRequest::gjk_solver_type: 0 = GST_LIBCCD (MPR), 1 = GST_INDEP
      * (FCL's own GJK, fcl_gjk_indep.h; shape pairs only) */
     int gjk_solver;
+    /* CollisionRequest::gjk_tolerance (1e-6 by default).  fcl::collide builds
+     * its solver from the request [ext FCL 0.7.0 collision-inl.h:
+     * solver.collision_tolerance = request.gjk_tolerance (GJKSolver_libccd),
+     * solver.gjk_tolerance = request.gjk_tolerance (GJKSolver_indep)], and
+     * GJKSolver_libccd::shapeIntersect / shapeTriangleIntersect hand
+     * collision_tolerance to GJKCollide, which stores it as ccd.mpr_tolerance
+     * [ext gjk_libccd-inl.h] -- with and without contacts.  Every
+     * mpr_intersect / mpr_penetration / gjk_indep_intersect below takes it. */
+    double gjk_tolerance;
 } orc_world;
 
 typedef struct {
@@ -1771,7 +1780,7 @@ static int octree_intersect(const orc_world *w, int go, const real *TO, int gs, 
             box.type = GEOM_BOX;
             box.stats = st;
             for (int k = 0; k < 3; ++k) box.dim[k] = side[k] / 2.0; /* boxToGJK */
-            hit = mpr_intersect(&box, &shape, 1e-6);
+            hit = mpr_intersect(&box, &shape, w->gjk_tolerance);
         }
         if (hit) return 1;
     }
@@ -1896,7 +1905,7 @@ static int octree_contact(const orc_world *w, int go, const real *TO, int gs, co
             shape_to_gjk(TL, &box);
             box.type = GEOM_BOX;
             for (int k = 0; k < 3; ++k) box.dim[k] = side[k] / 2.0; /* boxToGJK */
-            hit = mpr_penetration(&box, &shape, 1e-6, depth, normal, pos);
+            hit = mpr_penetration(&box, &shape, w->gjk_tolerance, depth, normal, pos);
         }
         if (hit) return 1;
     }
@@ -2502,8 +2511,8 @@ static int ms_leaf(void *vc, int t) {
         shape_to_gjk(c->TM, &tri);
         tri.stats = c->st;
         tri_gjk_obj(w, c->gm, &tri, tt, &tri);
-        hit = c->contact ? mpr_penetration(&c->shape, &tri, 1e-6, c->depth, c->normal, c->pos)
-                         : mpr_intersect(&c->shape, &tri, 1e-6);
+        hit = c->contact ? mpr_penetration(&c->shape, &tri, w->gjk_tolerance, c->depth, c->normal, c->pos)
+                         : mpr_intersect(&c->shape, &tri, w->gjk_tolerance);
     }
     return hit;
 }
@@ -2670,8 +2679,8 @@ static int octmesh_rec(om_ctx *c, int n1, int n2) {
         leaf_box_obj(side, TL, &box);
         box.stats = c->st;
         tri_gjk_obj(c->w, c->gm, &c->frame, (int)c->w->geom_param[4 * c->gm] + (-(b->first_child + 1)), &tri);
-        return c->contact ? mpr_penetration(&box, &tri, 1e-6, c->depth, c->normal, c->pos)
-                          : mpr_intersect(&box, &tri, 1e-6);
+        return c->contact ? mpr_penetration(&box, &tri, c->w->gjk_tolerance, c->depth, c->normal, c->pos)
+                          : mpr_intersect(&box, &tri, c->w->gjk_tolerance);
     }
     const double d[3] = {a->hi[0] - a->lo[0], a->hi[1] - a->lo[1], a->hi[2] - a->lo[2]};
     const double s1 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
@@ -2941,10 +2950,10 @@ static int collide_one(const orc_world *w, const real *q, uint32_t *mask, int W,
         else if (w->geom_type[gs[0]] == GEOM_OCTREE) hit = octree_intersect(w, gs[0], Ts[0], gs[1], Ts[1], st);
         else hit = closed_form_intersect(w, gs[0], Ts[0], gs[1], Ts[1]);
         if (hit < 0 && w->gjk_solver == 1) {
-            hit = gjk_indep_intersect(w, gs[0], Ts[0], gs[1], Ts[1], 1e-6);
+            hit = gjk_indep_intersect(w, gs[0], Ts[0], gs[1], Ts[1], w->gjk_tolerance);
         } else if (hit < 0) {
             for (int s = 0; s < 2; ++s) make_obj(w, gs[s], Ts[s], objs[s], st);
-            hit = mpr_intersect(&a, &b, 1e-6);
+            hit = mpr_intersect(&a, &b, w->gjk_tolerance);
         }
         if (hit) {
             mask[p >> 5] |= 1u << (p & 31);
@@ -3541,7 +3550,7 @@ int orc_contact_pair(const orc_world *w, int ga, const double *Ta, int gb, const
     gjk_obj a, b;
     make_obj(w, ga, Ta, &a, NULL);
     make_obj(w, gb, Tb, &b, NULL);
-    return mpr_penetration(&a, &b, 1e-6, depth, normal, pos);
+    return mpr_penetration(&a, &b, w->gjk_tolerance, depth, normal, pos);
 }
 
 /* every (configuration, pair): penetration of the pairs MPR reports
@@ -3581,7 +3590,7 @@ int orc_contact_batch(const orc_world *w, const double *q, long n, uint8_t *hit,
                 continue;
             }
             for (int s = 0; s < 2; ++s) make_obj(w, gs[s], Ts[s], &o[s], NULL);
-            hit[k] = (uint8_t)mpr_penetration(&o[0], &o[1], 1e-6, depth + k, normal + 3 * k, pos + 3 * k);
+            hit[k] = (uint8_t)mpr_penetration(&o[0], &o[1], w->gjk_tolerance, depth + k, normal + 3 * k, pos + 3 * k);
         }
     }
     free(oMi); free(link_T); free(obj_T); free(att_T);
@@ -3603,11 +3612,11 @@ int orc_collide_pair(const orc_world *w, int ga, const double *Ta, int gb, const
     if (w->geom_type[ga] == GEOM_OCTREE) return octree_intersect(w, ga, Ta, gb, Tb, NULL);
     const int cf = closed_form_intersect(w, ga, Ta, gb, Tb);
     if (cf >= 0) return cf;
-    if (w->gjk_solver == 1) return gjk_indep_intersect(w, ga, Ta, gb, Tb, 1e-6);
+    if (w->gjk_solver == 1) return gjk_indep_intersect(w, ga, Ta, gb, Tb, w->gjk_tolerance);
     gjk_obj a, b;
     make_obj(w, ga, Ta, &a, NULL);
     make_obj(w, gb, Tb, &b, NULL);
-    return mpr_intersect(&a, &b, 1e-6);
+    return mpr_intersect(&a, &b, w->gjk_tolerance);
 }
 
 /* Intersect::intersect_Triangle / sphereTriangleIntersect on raw points
