@@ -15,6 +15,7 @@
 // Everything here compiles for the host too (tests/native/host_fk.cpp) so the
 // fp32-vs-fp64 pose error is checked on the CPU.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -990,6 +991,35 @@ inline void bp_grid_records(const BpGridPlan& G, const std::vector<int>& E, std:
     r[GI_FULL] = (int)(o.sid.size() >= 32 ? ~0u : (1u << o.sid.size()) - 1u);
   }
   for (size_t i = G.obj.size(); i < n; ++i) gi[GI_STRIDE * i + GI_E] = E.empty() ? 0 : E.back();
+}
+
+// ---------------------------------------------------------------------------
+// host: the cull kernel's block size and dynamic LDS (mpg_world_create; the
+// host shim of tests/native/host_fk.cpp tabulates them)
+// ---------------------------------------------------------------------------
+constexpr int kQueue = 128;  // SAT queue entries per wave: < 64 pending + <= 64 pushed
+
+// phase A LDS bytes per thread: records + FK save slots + survivor words + queue share
+inline size_t cull_lds_per_thread(int n_moving, int n_saves, int W) {
+  return (size_t)std::max(n_moving, 1) * 3 * sizeof(float) + (size_t)std::max(n_saves - kRegSaves, 0) * 12 * sizeof(float) +
+         (size_t)W * sizeof(uint32_t) + (kQueue / 64) * sizeof(uint32_t);
+}
+
+// block size that keeps the most waves resident per CU (160 KiB of LDS),
+// ties to the larger block; -1 if even one wave does not fit
+inline int choose_block(size_t per_thread, size_t* lds) {
+  int best = -1, best_waves = 0;
+  for (int b : {256, 128, 64}) {
+    const size_t bytes = per_thread * b;
+    if (bytes > 160 * 1024) continue;
+    const int waves = std::min(32, (int)(160 * 1024 / bytes) * (b / 64));
+    if (waves > best_waves) {
+      best_waves = waves;
+      best = b;
+    }
+  }
+  if (best > 0) *lds = per_thread * best;
+  return best;
 }
 
 }  // namespace mpg

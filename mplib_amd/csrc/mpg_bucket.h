@@ -51,6 +51,8 @@ MPG_INLINE int bk_group_of(int r) { return r / kGroupRanges; }
 // in all has range_scan_kernel do the range sums itself (one launch fewer)
 constexpr int kSumSlots = 4096;
 MPG_INLINE bool bk_fold_sum(int n_ranges, int W) { return (long long)n_ranges * bk_row_words(W) <= kSumSlots; }
+constexpr int kSumCols = 256;  // count-row dwords summed at a time: wider rows (W > 32) take several passes
+static_assert(kGroupRanges * kSumCols <= kSumSlots, "a group's sums must fit the block's LDS");
 // the tile of a cull wave (block of `block` threads, thread tid) and whether
 // it owns a count row: the grid is ceil(n / block) blocks, so waves past the
 // last tile exist whenever n is no multiple of the block

@@ -1029,7 +1029,6 @@ __device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi
 #ifndef MPG_REFILL
 #define MPG_REFILL 32
 #endif
-constexpr int kQueue = 128;  // entries per wave: < 64 pending + <= 64 pushed
 constexpr uint32_t kTask = MPG_TASK;  // narrow phase: candidates of one pair per wave task
 // taper of the task size towards the end of the task list (mpg_bucket.h,
 // bk_task_plan): a level starts where MPG_TAPER_C * target tasks * (the size
@@ -1508,9 +1507,6 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 // Candidates of a pair end up contiguous and sorted by config.  Layouts and
 // index arithmetic: mpg_bucket.h.
 // ---------------------------------------------------------------------------
-constexpr int kSumCols = 256;  // count-row dwords summed at a time
-static_assert(kGroupRanges * kSumCols <= kSumSlots, "a group's sums must fit the block's LDS");
-
 // The range sums of the groups [g0, g0 + ng) by one block of NT threads
 // (ranges of these groups x min(row dwords, kSumCols) <= kSumSlots).  Lanes
 // run along the count row (one dword = four pairs each), so every load is a

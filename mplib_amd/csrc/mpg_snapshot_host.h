@@ -560,25 +560,4 @@ void static_record(const mpg_world_desc* d, int s, const double* geom_rec_all, d
   for (int k = 0; k < 9; ++k) rec[S_R + k] = R[k];
 }
 
-// phase A LDS bytes per thread: records + FK save slots + survivor words + queue share
-size_t cull_lds_per_thread(int n_moving, int n_saves, int W) {
-  return (size_t)std::max(n_moving, 1) * 3 * sizeof(float) + (size_t)std::max(n_saves - kRegSaves, 0) * 12 * sizeof(float) +
-         (size_t)W * sizeof(uint32_t) + (kQueue / 64) * sizeof(uint32_t);
-}
-
-// block size that keeps the most waves resident per CU (160 KiB of LDS),
-// ties to the larger block; -1 if even one wave does not fit
-int choose_block(size_t per_thread, size_t* lds) {
-  int best = -1, best_waves = 0;
-  for (int b : {256, 128, 64}) {
-    const size_t bytes = per_thread * b;
-    if (bytes > 160 * 1024) continue;
-    const int waves = std::min(32, (int)(160 * 1024 / bytes) * (b / 64));
-    if (waves > best_waves) {
-      best_waves = waves;
-      best = b;
-    }
-  }
-  if (best > 0) *lds = per_thread * best;
-  return best;
-}
+// cull_lds_per_thread, choose_block (the cull's block size and LDS): mpg_broadphase.h

@@ -1,6 +1,6 @@
 // mpg_streams_host.h -- per-stream workspaces, stream pinning, launch_collide,
 // input staging, the pinned ring and the world scratch, host side (included by
-// mpg_kernels.hip in an anonymous namespace, after mpg_snapshot_host.h's choose_block).
+// mpg_kernels.hip in an anonymous namespace, after mpg_snapshot_host.h).
 #pragma once
 
 // drops the state kept for caller stream s (its workspace, its side stream

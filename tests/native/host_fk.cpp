@@ -64,6 +64,32 @@ int host_bp_objects(int nj, const int* jt, const int* jp, const int* jqs, const 
   }
   return 0;
 }
+// The cull's launch geometry (mpg_broadphase.h): per-thread LDS bytes of a
+// world, then the block mpg_world_create takes and its dynamic LDS bytes.
+// host_cull_saves: n_saves of the joint tree, as bp_build counts them.
+long host_cull_lds_per_thread(int n_moving, int n_saves, int W) {
+  return (long)mpg::cull_lds_per_thread(n_moving, n_saves, W);
+}
+int host_choose_block(long per_thread, long* lds) {
+  size_t b = 0;
+  const int block = mpg::choose_block((size_t)per_thread, &b);
+  *lds = block > 0 ? (long)b : -1;
+  return block;
+}
+int host_cull_saves(int nj, const int* jt, const int* jp, const int* jqs, const double* jqc, const double* jax,
+                    const double* jpl, int dof, int n_links, const int* lp, const double* lpl, int n_moving,
+                    const int* mlink, const double* moff) {
+  std::vector<int> mgeom(n_moving, 0);
+  mpg_world_desc d{};
+  d.n_joints = nj; d.joint_type = jt; d.joint_parent = jp; d.joint_axis = jax; d.joint_placement = jpl;
+  d.joint_q_source = jqs; d.joint_q_const = jqc; d.dof = dof;
+  d.n_links = n_links; d.link_parent = lp; d.link_placement = lpl;
+  d.n_moving = n_moving; d.moving_link = mlink; d.moving_geom = mgeom.data(); d.moving_offset = moff;
+  std::vector<double> obb(7, 0.0);
+  mpg::BpProgram P;
+  mpg::bp_build(&d, obb, P);
+  return P.n_saves;
+}
 void host_sincos(const double* x, long n, double* s, double* c, int fma) {
   for (long i = 0; i < n; ++i) {
     if (fma == 1) { s[i] = mpg::mpg_sin<true>(x[i]); c[i] = mpg::mpg_cos<true>(x[i]); }

@@ -21,7 +21,7 @@ def lib():
         _lib = _build(os.path.join(_HERE, "native", "bucket_replay.cpp"), "mplib_amd_bucket_replay")
         _lib.bucket_index_check.argtypes = [ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, ctypes.c_int]
         _lib.bucket_replay.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int,
-                                       ctypes.c_void_p, ctypes.c_void_p]
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     return _lib
 
 
@@ -29,6 +29,13 @@ def consts():
     out = (ctypes.c_int * 2)()
     lib().bucket_consts(out)
     return out[0], out[1]  # tiles per range, ranges per group
+
+
+def launch_shape(n, W):
+    """tiles, ranges, groups of a launch of n rows with W mask words, and bk_fold_sum's decision for it."""
+    out = (ctypes.c_int * 4)()
+    lib().bucket_launch_shape(ctypes.c_longlong(n), W, out)
+    return dict(tiles=out[0], ranges=out[1], groups=out[2], fold=bool(out[3]))
 
 
 def tile_counts():
@@ -47,7 +54,7 @@ def test_ranges_partition_tiles_and_sizes_cover_every_write(block):
             for cap in (n, n + 1, max(n, 20000), 1 << 20):
                 if cap < n:
                     continue
-                for W in (1, 5, 18):
+                for W in (1, 5, 18, 35, 70):
                     assert lib().bucket_index_check(n, cap, W, block) == 0, (tiles, n, cap, W)
 
 
@@ -62,20 +69,37 @@ def replay(W, n_pairs, n, cap, block, seed, density=0.06):
         surv[p >> 5] |= bits[p].astype(np.uint32) << np.uint32(p & 31)
     surv = np.ascontiguousarray(surv)
     nc = ctypes.c_longlong(0)
-    rc = lib().bucket_replay(W, n_pairs, n, cap, block, surv.ctypes.data, ctypes.byref(nc))
+    paths = (ctypes.c_int * 5)()
+    rc = lib().bucket_replay(W, n_pairs, n, cap, block, surv.ctypes.data, ctypes.byref(nc), paths)
     assert rc == 0, f"bucket_replay.cpp:{rc} (W={W}, pairs={n_pairs}, n={n}, cap={cap}, block={block})"
     assert nc.value == int(bits[:, :n].sum())
+    return dict(fold=bool(paths[0]), sum_passes=paths[1], col_passes=paths[2], rounds=paths[3], groups=paths[4])
 
 
-@pytest.mark.parametrize("W,n_pairs", [(1, 7), (5, 129), (18, 547)])
+# the last three: worlds of a Panda and 100 / 200 boxes (tests/wide_worlds.py),
+# and a pair count of a multiple of 1024 plus one
+@pytest.mark.parametrize("W,n_pairs", [(1, 7), (5, 129), (18, 547), (35, 1119), (70, 2219), (65, 2049)])
 def test_host_replay_matches_direct_lists(W, n_pairs):
     """Stale workspace contents (the replay poisons cnt, part and grp first)
-    must not show; candidate lists equal per-pair sorted lists built directly."""
+    must not show; candidate lists equal per-pair sorted lists built directly.
+    More than 32 mask words: the range sums pass over the count row more than
+    once, the scan over the columns more than once, the task prefix runs a
+    round per 1024 pairs; 4160 rows fold the range sums into the scan up to 56
+    mask words and not above."""
     T, G = consts()
     R = 64 * T
-    for i, n in enumerate((1, 63, 64, 65, 255, 256, 257, R - 1, R, R + 1, 3 * R + 17, G * R + 65)):
+    seen = []
+    for i, n in enumerate((1, 63, 64, 65, 255, 256, 257, R - 1, R, R + 1, 3 * R + 17, 4160, G * R + 65)):
         for block in (64, 128, 256):
-            replay(W, n_pairs, n, n + (i % 3) * 777, block, seed=1000 * W + n)
+            seen.append((n, replay(W, n_pairs, n, n + (i % 3) * 777, block, seed=1000 * W + n)))
+    for n, p in seen:
+        assert p["sum_passes"] == (W * 8 + 255) // 256  # per block
+        assert p["col_passes"] == (W * 32 + 1023) // 1024 and p["rounds"] == (n_pairs + 1023) // 1024
+        assert p["fold"] == (-(-n // R) * W * 8 <= 4096)
+    assert max(p["groups"] for _, p in seen) == 2
+    assert dict(seen)[4160]["fold"] == (W <= 56)
+    if W > 32:  # narrower worlds fold at every size here
+        assert {p["fold"] for _, p in seen} == {True, False}
 
 
 def test_host_replay_no_pairs():

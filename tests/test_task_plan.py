@@ -97,7 +97,9 @@ def random_lengths(rng, n_pairs, hi, zeros=0.25):
 def test_random_segment_lengths(target):
     rng = np.random.default_rng(17 + target)
     seen = set()
-    for rounds, n_pairs, hi in ((40, 7, 40), (40, 129, 300), (20, 160, 6000), (6, 547, 30000), (3, 160, 1 << 20)):
+    # 1119 and 2219 pairs: a Panda and 100 / 200 boxes (tests/wide_worlds.py), prefixes of more than 1024 pairs
+    for rounds, n_pairs, hi in ((40, 7, 40), (40, 129, 300), (20, 160, 6000), (6, 547, 30000), (3, 160, 1 << 20),
+                                (4, 1119, 3000), (3, 2219, 3000), (2, 2219, 20000)):
         for _ in range(rounds):
             seg = random_lengths(rng, n_pairs, hi)
             seen.add(check(seg, target)[0])
