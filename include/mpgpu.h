@@ -862,6 +862,86 @@ int mpg_plan_batch(mpg_world *world, const double *start /* [Q*dof] */, const do
                    int32_t *tree_sizes /* [Q*2] or NULL */, int mem, void *stream);
 
 /*
+ * Planner.TOPP (mplib/planner.py:358-375) for many joint-space paths in one
+ * device call: row r's n = n_waypoints[r] waypoints q_0 .. q_{n-1} (the layout
+ * mpg_screw_batch and mpg_plan_batch write) get a cubic spline at s_i = i /
+ * (n - 1), the time-optimal parametrisation under the joint velocity and
+ * acceleration limits (TOPP-RA, Pham & Pham 2018), and samples every `step`.
+ * toppra picks its gridpoints adaptively; this call's algorithm is stated
+ * here and in DESIGN.md section 14 instead.  fp64, no fused multiply-add, + - *
+ * / sqrt and comparisons only: a row's result is the same bits as the host
+ * build of mplib_amd/csrc/mpg_topp.h.
+ *
+ * Spline.  C2 cubic, not-a-knot ends (scipy CubicSpline's default, toppra's
+ * SplineInterpolator).  n = 2: the straight line; n = 3: the parabola.
+ * Grid.  N = max(min_grid, grid_per_segment * (n - 1)) intervals, s_k = k / N,
+ * delta = 1 / N.
+ * Constraints of interval k on x = sdot^2 and u = sddot (first-order
+ * interpolation, toppra's default): per joint |q'_k u + q''_k x| <= amax and
+ * |(q'_{k+1} + 2 delta q''_{k+1}) u + q''_{k+1} x| <= amax; 0 <= x + 2 delta u
+ * <= K_{k+1}; x <= min over the joints with q'_k != 0 of (vmax / q'_k)^2, at
+ * most 1e12.
+ * Backward.  K_N = 0; K_k = the largest feasible x (u eliminated exactly by
+ * Fourier-Motzkin over the (2 dof + 1)^2 pairs of a lower and an upper bound),
+ * at least 0.
+ * Forward.  x_0 = 0; u_k = the largest u the acceleration rows allow at x_k;
+ * x_{k+1} = min(max(x_k + 2 delta u_k, 0), K_{k+1}), the continuation row.
+ * Time.  t_{k+1} = t_k + 2 delta / (sqrt x_k + sqrt x_{k+1}); duration = t_N.
+ * Samples.  m = int(duration / step) samples at t_i = i duration / (m - 1)
+ * (np.linspace(0, duration, m): the spacing is not `step`; m = 1: t = 0).  In
+ * the interval with t_k <= t (the largest such k, at most N - 1): tau = t - t_k,
+ * sddot = (x_{k+1} - x_k) / (2 delta), sdot = sqrt x_k + sddot tau, s = s_k +
+ * sqrt x_k tau + sddot tau^2 / 2 clamped to [s_k, s_{k+1}]; position = q(s),
+ * velocity = q'(s) sdot, acceleration = q'(s) sddot + q''(s) sdot^2.
+ *
+ * status: MPG_TOPP_OK; NO_PATH (n_waypoints < 2, such as a failed plan row);
+ * ZERO_LENGTH (all waypoints equal bit for bit); STALLED (an interval with
+ * x_k = x_{k+1} = 0, or a duration that is not finite; NaN inputs end here);
+ * TRUNCATED (with OK: m > max_samples; duration is valid, n_samples is 0).
+ * Rows that are not OK have duration 0 and n_samples 0.  Every loop has a fixed
+ * length.  Sample slots past n_samples repeat the last sample; a row without
+ * samples holds its first waypoint, zero time, velocity and acceleration.
+ * grid_x / grid_t (optional): x_k and t_k with the stride Ncap + 1, Ncap =
+ * max(min_grid, grid_per_segment * (max_waypoints - 1)); slots past a row's N
+ * repeat the last value, rows without a profile hold zeros.
+ *
+ * dof is the world's state width; the world's geometry is not used.
+ * MPG_E_UNSUPPORTED: dof > 32.  MPG_E_INVALID: options out of range,
+ * max_waypoints outside [2, 4096], a limit that is not finite and > 0, rows *
+ * max_waypoints * dof, rows * max_samples * dof or rows * (Ncap + 1) above
+ * 2^31, a NULL required buffer with rows > 0; with MPG_MEM_HOST also
+ * n_waypoints[r] > max_waypoints (the device clamps it) and a non-finite path
+ * value inside a row's count.  rows = 0 returns 0.
+ *
+ * vel_limits, acc_limits and opt are host memory, read during the call.
+ * MPG_MEM_DEVICE: every other buffer is device memory, everything is enqueued
+ * on `stream`, nothing synchronises (the buffers mpg_screw_batch /
+ * mpg_plan_batch just wrote on the same stream can be passed straight in).
+ * MPG_MEM_HOST buffers are staged and the call synchronises.
+ */
+#define MPG_TOPP_OK 1
+#define MPG_TOPP_NO_PATH 2
+#define MPG_TOPP_ZERO_LENGTH 4
+#define MPG_TOPP_STALLED 8
+#define MPG_TOPP_TRUNCATED 16
+
+typedef struct mpg_topp_options {
+  double step;              /* 0.1; > 0, else MPG_E_INVALID */
+  int32_t grid_per_segment; /* 8; 1 .. 64 */
+  int32_t min_grid;         /* 100; 2 .. 65536 */
+  int32_t max_samples;      /* 256; 1 .. 65536 */
+} mpg_topp_options;
+
+int mpg_topp_batch(mpg_world *world, const double *path /* [rows*max_waypoints*dof] */,
+                   const int32_t *n_waypoints /* [rows] */, int64_t rows, int32_t max_waypoints,
+                   const double *vel_limits /* [dof] */, const double *acc_limits /* [dof] */,
+                   const mpg_topp_options *opt /* NULL = defaults */, double *times /* [rows*max_samples] */,
+                   double *position, double *velocity, double *acceleration /* each [rows*max_samples*dof] */,
+                   int32_t *n_samples /* [rows] */, double *duration /* [rows] */, uint8_t *status /* [rows] */,
+                   double *grid_x /* [rows*(Ncap+1)] or NULL */, double *grid_t /* same or NULL */, int mem,
+                   void *stream);
+
+/*
  * Diagnostics (host only, no device): the FCL 0.7.0 BVHModel<OBBRSS> tree the
  * snapshot builds for a BVH mesh (BVHModel::endModel -> buildTree:
  * BVFitter<OBBRSS>::fit, SPLIT_METHOD_MEAN; OBB half), whose OBB tests gate

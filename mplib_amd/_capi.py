@@ -106,6 +106,19 @@ MPG_PLAN_NODES_EXHAUSTED = 16
 MPG_PLAN_TRUNCATED = 32
 
 
+class ToppOptions(ctypes.Structure):
+    """mpg_topp_options (include/mpgpu.h); step 0.1 is the reference's time_step."""
+    _fields_ = [("step", ctypes.c_double), ("grid_per_segment", ctypes.c_int32), ("min_grid", ctypes.c_int32),
+                ("max_samples", ctypes.c_int32)]
+
+
+MPG_TOPP_OK = 1
+MPG_TOPP_NO_PATH = 2
+MPG_TOPP_ZERO_LENGTH = 4
+MPG_TOPP_STALLED = 8
+MPG_TOPP_TRUNCATED = 16
+
+
 class WorldInfo(ctypes.Structure):
     _fields_ = [("n_pairs", ctypes.c_int32), ("mask_words", ctypes.c_int32), ("dof", ctypes.c_int32),
                 ("n_links", ctypes.c_int32), ("device", ctypes.c_int32), ("block_size", ctypes.c_int32),
@@ -181,6 +194,10 @@ SIGNATURES = {
                                        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "mpg_plan_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                       ctypes.c_void_p, ctypes.POINTER(PlanOptions), ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "mpg_topp_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ToppOptions), ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "mpg_profile_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "mpg_profile_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),

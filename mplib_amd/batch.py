@@ -422,6 +422,101 @@ class DeviceWorld:
                 "mpg_plan_batch")
         return path, count, status, iters, sizes
 
+    def _topp_sizes(self, max_waypoints, grid_per_segment, min_grid, max_samples):
+        """Refuses what would size the outputs wrongly; returns Ncap."""
+        if not 2 <= int(max_waypoints) <= 4096:
+            raise ValueError("max_waypoints outside [2, 4096]")
+        if not 1 <= int(grid_per_segment) <= 64 or not 2 <= int(min_grid) <= 65536:
+            raise ValueError("grid_per_segment outside [1, 64] or min_grid outside [2, 65536]")
+        if not 1 <= int(max_samples) <= 65536:
+            raise ValueError("max_samples outside [1, 65536]")
+        return max(int(min_grid), int(grid_per_segment) * (int(max_waypoints) - 1))
+
+    def topp_batch(self, path, n_waypoints, vel_limits, acc_limits, *, step: float = 0.1, grid_per_segment: int = 8,
+                   min_grid: int = 100, max_samples: int = 256, return_grid: bool = False,
+                   stream: Optional[int] = None):
+        """Planner.TOPP for every row of ``path`` [rows, max_waypoints, dof]
+        (numpy; the layout screw_batch / plan_batch return, ``n_waypoints``
+        [rows] the rows' counts) in one call (mpg_topp_batch): a cubic spline
+        through the waypoints, TOPP-RA under ``vel_limits`` / ``acc_limits``
+        [dof], samples every ``step``.  Returns (times [rows, max_samples],
+        position, velocity, acceleration [rows, max_samples, dof], n_samples
+        [rows] i32, duration [rows], status [rows] u8 of ``_capi.MPG_TOPP_*``
+        bits) and, with ``return_grid``, (grid_x, grid_t) [rows, Ncap + 1]: the
+        profile sdot^2 and the time at the gridpoints.  Sample slots past a
+        row's n_samples repeat its last sample."""
+        p = np.ascontiguousarray(np.asarray(path, dtype=np.float64))
+        if p.ndim != 3 or p.shape[2] != self.dof:
+            raise ValueError(f"path must be [rows, max_waypoints, {self.dof}]")
+        rows, mw = p.shape[0], p.shape[1]
+        cnt = np.ascontiguousarray(np.asarray(n_waypoints, dtype=np.int32).reshape(-1))
+        if cnt.size != rows:
+            raise ValueError(f"n_waypoints must hold {rows} values")
+        ncap = self._topp_sizes(mw, grid_per_segment, min_grid, max_samples)
+        vel, acc = self._topp_limits(vel_limits, acc_limits)
+        o = C.ToppOptions(float(step), int(grid_per_segment), int(min_grid), int(max_samples))
+        ms = int(max_samples)
+        times = np.zeros((rows, ms))
+        pos, velo, accel = (np.zeros((rows, ms, self.dof)) for _ in range(3))
+        ns = np.zeros(rows, np.int32)
+        dur = np.zeros(rows)
+        status = np.zeros(rows, np.uint8)
+        gx, gt = (np.zeros((rows, ncap + 1)), np.zeros((rows, ncap + 1))) if return_grid else (None, None)
+        P = ctypes.c_void_p
+        hp = lambda a: P(a.ctypes.data if a is not None else 0)  # noqa: E731
+        C.check(C.lib().mpg_topp_batch(self._h, hp(p), hp(cnt), rows, mw, hp(vel), hp(acc), ctypes.byref(o), hp(times),
+                                       hp(pos), hp(velo), hp(accel), hp(ns), hp(dur), hp(status), hp(gx), hp(gt),
+                                       C.MPG_MEM_HOST, P(stream or 0)), "mpg_topp_batch")
+        out = (times, pos, velo, accel, ns, dur, status)
+        return out + (gx, gt) if return_grid else out
+
+    def _topp_limits(self, vel_limits, acc_limits):
+        vel = np.ascontiguousarray(np.asarray(vel_limits, dtype=np.float64).reshape(-1))
+        acc = np.ascontiguousarray(np.asarray(acc_limits, dtype=np.float64).reshape(-1))
+        if vel.size != self.dof or acc.size != self.dof:
+            raise ValueError(f"vel_limits and acc_limits must hold {self.dof} values")
+        return vel, acc
+
+    def topp_batch_device(self, path, n_waypoints, vel_limits, acc_limits, *, step: float = 0.1,
+                          grid_per_segment: int = 8, min_grid: int = 100, max_samples: int = 256,
+                          return_grid: bool = False, out=None, stream: Optional[int] = None):
+        """``topp_batch`` on torch tensors of the world's device: ``path``
+        [rows, max_waypoints, dof] float64 and ``n_waypoints`` [rows] int32 as
+        ``screw_batch`` / ``plan_batch`` left them (``vel_limits`` /
+        ``acc_limits`` stay host arrays).  Everything is enqueued on ``stream``
+        and nothing synchronises.  ``out``: topp_batch's tuple as preallocated
+        tensors (with the two grids when ``return_grid``), else they are
+        allocated with torch.  Returns the tuple."""
+        import torch
+
+        if path.dim() != 3 or path.shape[2] != self.dof or not path.is_contiguous():
+            raise ValueError(f"path must be a contiguous [rows, max_waypoints, {self.dof}] tensor")
+        rows, mw = int(path.shape[0]), int(path.shape[1])
+        if n_waypoints.numel() != rows or n_waypoints.dtype != torch.int32:
+            raise ValueError(f"n_waypoints must hold {rows} int32 values")
+        ncap = self._topp_sizes(mw, grid_per_segment, min_grid, max_samples)
+        vel, acc = self._topp_limits(vel_limits, acc_limits)
+        o = C.ToppOptions(float(step), int(grid_per_segment), int(min_grid), int(max_samples))
+        ms = int(max_samples)
+        if out is None:
+            f64 = dict(dtype=torch.float64, device=path.device)
+            out = (torch.empty((rows, ms), **f64), torch.empty((rows, ms, self.dof), **f64),
+                   torch.empty((rows, ms, self.dof), **f64), torch.empty((rows, ms, self.dof), **f64),
+                   torch.empty(rows, dtype=torch.int32, device=path.device), torch.empty(rows, **f64),
+                   torch.empty(rows, dtype=torch.uint8, device=path.device))
+            if return_grid:
+                out = out + (torch.empty((rows, ncap + 1), **f64), torch.empty((rows, ncap + 1), **f64))
+        if len(out) != (9 if return_grid else 7):
+            raise ValueError("out must hold topp_batch's tensors")
+        P = ctypes.c_void_p
+        ptr = lambda t: P(t.data_ptr() if t is not None else 0)  # noqa: E731
+        hp = lambda a: P(a.ctypes.data)  # noqa: E731
+        gx, gt = (out[7], out[8]) if return_grid else (None, None)
+        C.check(C.lib().mpg_topp_batch(self._h, ptr(path), ptr(n_waypoints), rows, mw, hp(vel), hp(acc), ctypes.byref(o),
+                                       *(ptr(t) for t in out[:7]), ptr(gx), ptr(gt), C.MPG_MEM_DEVICE, P(stream or 0)),
+                "mpg_topp_batch")
+        return out
+
 
 def device_sincos(x, device: int = 0):
     xa = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))

@@ -817,6 +817,12 @@ class PlanningWorld {
   void plan_batch(const double* start, const double* goal, int64_t Q, int32_t G, const uint64_t* row_seed,
                   mpg_plan_options opt, double* path, int32_t* n_waypoints, uint8_t* status, int32_t* iterations,
                   int32_t* tree_sizes, int mem, void* stream);
+  // Planner.TOPP batched (mpg_topp_batch): rows of [max_waypoints, dim] waypoints as plan_screw_batch /
+  // plan_batch write them; vel_limits / acc_limits [dim] are host memory
+  void topp_batch(const double* path, const int32_t* n_waypoints, int64_t rows, int32_t max_waypoints,
+                  const double* vel_limits, const double* acc_limits, const mpg_topp_options& opt, double* times,
+                  double* position, double* velocity, double* acceleration, int32_t* n_samples, double* duration,
+                  uint8_t* status, double* grid_x, double* grid_t, int mem, void* stream);
   // batched OMPL motion validation over the planner's state space
   // (src/ompl_planner.cpp:248-293): SO2 dofs and the space's maximum extent
   struct MotionSpace {

@@ -1372,6 +1372,87 @@ PYBIND11_MODULE(pymp, m_all) {
            "uint64 row seeds [rows] -> float64 path [rows, max_waypoints, dim], int32 n_waypoints [rows], uint8 status "
            "[rows], optional int32 iterations [rows] and tree_sizes [rows, 2]).  Not a pure enqueue: the host decides "
            "when to stop, so the call synchronises `stream` once per check_every rounds and once at the end.")
+      .def("topp_batch",
+           [](PW& w, py::array_t<double, py::array::c_style | py::array::forcecast> path,
+              py::array_t<int32_t, py::array::c_style | py::array::forcecast> n_waypoints,
+              py::array_t<double, py::array::c_style | py::array::forcecast> vel_limits,
+              py::array_t<double, py::array::c_style | py::array::forcecast> acc_limits, double step,
+              int grid_per_segment, int min_grid, int max_samples, bool return_grid) {
+             const int dim = w.state_dim();
+             if (path.ndim() != 3 || path.shape(2) != dim)
+               throw std::invalid_argument("path must be [rows, max_waypoints, " + std::to_string(dim) + "] float64");
+             const int64_t rows = path.shape(0), mw = path.shape(1);
+             if (n_waypoints.ndim() != 1 || n_waypoints.shape(0) != rows)
+               throw std::invalid_argument("n_waypoints must hold one int32 count per row");
+             if (vel_limits.size() != dim || acc_limits.size() != dim)
+               throw std::invalid_argument("vel_limits and acc_limits must hold " + std::to_string(dim) + " values");
+             // refused before the outputs are sized by them
+             if (mw < 2 || mw > 4096) throw std::invalid_argument("max_waypoints outside [2, 4096]");
+             if (grid_per_segment < 1 || grid_per_segment > 64 || min_grid < 2 || min_grid > 65536)
+               throw std::invalid_argument("grid_per_segment outside [1, 64] or min_grid outside [2, 65536]");
+             if (max_samples < 1 || max_samples > 65536) throw std::invalid_argument("max_samples outside [1, 65536]");
+             const ssize_t g = (ssize_t)std::max<int64_t>(min_grid, (int64_t)grid_per_segment * (mw - 1)) + 1;
+             const ssize_t r = (ssize_t)rows, ms = (ssize_t)max_samples;
+             mpg_topp_options o{step, grid_per_segment, min_grid, max_samples};
+             py::array_t<double> times({r, ms}), pos({r, ms, (ssize_t)dim}), vel({r, ms, (ssize_t)dim}),
+                 acc({r, ms, (ssize_t)dim}), dur(r), gx({return_grid ? r : 0, g}), gt({return_grid ? r : 0, g});
+             py::array_t<int32_t> ns(r);
+             py::array_t<uint8_t> status(r);
+             const double *pp = path.data(), *vl = vel_limits.data(), *al = acc_limits.data();
+             const int32_t* cp = n_waypoints.data();
+             double *to = times.mutable_data(), *po = pos.mutable_data(), *vo = vel.mutable_data(),
+                    *ao = acc.mutable_data(), *du = dur.mutable_data();
+             double *xo = return_grid ? gx.mutable_data() : nullptr, *go = return_grid ? gt.mutable_data() : nullptr;
+             int32_t* no = ns.mutable_data();
+             uint8_t* so = status.mutable_data();
+             {
+               py::gil_scoped_release rel;
+               w.topp_batch(pp, cp, rows, (int32_t)mw, vl, al, o, to, po, vo, ao, no, du, so, xo, go, MPG_MEM_HOST,
+                            nullptr);
+             }
+             if (return_grid) return py::tuple(py::make_tuple(times, pos, vel, acc, ns, dur, status, gx, gt));
+             return py::tuple(py::make_tuple(times, pos, vel, acc, ns, dur, status));
+           },
+           py::arg("path"), py::arg("n_waypoints"), py::arg("vel_limits"), py::arg("acc_limits"), py::kw_only(),
+           py::arg("step") = 0.1, py::arg("grid_per_segment") = 8, py::arg("min_grid") = 100,
+           py::arg("max_samples") = 256, py::arg("return_grid") = false,
+           "Planner.TOPP for the rows of path [rows, max_waypoints, dim] (n_waypoints [rows]: the rows' counts; the "
+           "layout plan_screw_batch / plan_batch return) in one device call (include/mpgpu.h mpg_topp_batch): a cubic "
+           "spline through the waypoints, TOPP-RA under vel_limits / acc_limits [dim], samples every step.  Returns "
+           "(times [rows, max_samples], position, velocity, acceleration [rows, max_samples, dim], n_samples [rows] "
+           "int32, duration [rows], status [rows] uint8 of MPG_TOPP_* bits) and, with return_grid, grid_x and grid_t "
+           "[rows, Ncap + 1]; sample slots past a row's n_samples repeat its last sample; a row is parametrised when "
+           "status == 1.")
+      .def("topp_batch_device",
+           [](PW& w, uintptr_t path, uintptr_t n_waypoints, int64_t rows, int max_waypoints,
+              py::array_t<double, py::array::c_style | py::array::forcecast> vel_limits,
+              py::array_t<double, py::array::c_style | py::array::forcecast> acc_limits, uintptr_t times,
+              uintptr_t position, uintptr_t velocity, uintptr_t acceleration, uintptr_t n_samples, uintptr_t duration,
+              uintptr_t status, uintptr_t grid_x, uintptr_t grid_t, uintptr_t stream, double step, int grid_per_segment,
+              int min_grid, int max_samples) {
+             const int dim = w.state_dim();
+             if (vel_limits.size() != dim || acc_limits.size() != dim)
+               throw std::invalid_argument("vel_limits and acc_limits must hold " + std::to_string(dim) + " values");
+             mpg_topp_options o{step, grid_per_segment, min_grid, max_samples};
+             w.topp_batch(reinterpret_cast<const double*>(path), reinterpret_cast<const int32_t*>(n_waypoints), rows,
+                          max_waypoints, vel_limits.data(), acc_limits.data(), o, reinterpret_cast<double*>(times),
+                          reinterpret_cast<double*>(position), reinterpret_cast<double*>(velocity),
+                          reinterpret_cast<double*>(acceleration), reinterpret_cast<int32_t*>(n_samples),
+                          reinterpret_cast<double*>(duration), reinterpret_cast<uint8_t*>(status),
+                          reinterpret_cast<double*>(grid_x), reinterpret_cast<double*>(grid_t), MPG_MEM_DEVICE,
+                          reinterpret_cast<void*>(stream));
+           },
+           py::arg("path_ptr"), py::arg("n_waypoints_ptr"), py::arg("rows"), py::arg("max_waypoints"),
+           py::arg("vel_limits"), py::arg("acc_limits"), py::arg("times_ptr"), py::arg("position_ptr"),
+           py::arg("velocity_ptr"), py::arg("acceleration_ptr"), py::arg("n_samples_ptr"), py::arg("duration_ptr"),
+           py::arg("status_ptr"), py::arg("grid_x_ptr") = 0, py::arg("grid_t_ptr") = 0, py::arg("stream") = 0,
+           py::arg("step") = 0.1, py::arg("grid_per_segment") = 8, py::arg("min_grid") = 100,
+           py::arg("max_samples") = 256,
+           "Enqueue topp_batch on device buffers (float64 path [rows, max_waypoints, dim] and int32 n_waypoints [rows] "
+           "as plan_screw_batch_device / plan_batch_device left them -> float64 times [rows, max_samples], position, "
+           "velocity, acceleration [rows, max_samples, dim], int32 n_samples [rows], float64 duration [rows], uint8 "
+           "status [rows], optional float64 grid_x / grid_t [rows, Ncap + 1]).  vel_limits / acc_limits: host arrays "
+           "[dim].  No synchronisation.")
       .def("fk_link_pose",
            [](PW& w, py::array_t<double, py::array::c_style | py::array::forcecast> state, int link) {
              const int dim = w.state_dim();

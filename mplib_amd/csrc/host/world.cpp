@@ -779,6 +779,17 @@ void PlanningWorld::plan_batch(const double* start, const double* goal, int64_t 
                               tree_sizes, mem, stream),
                "mpg_plan_batch");
 }
+void PlanningWorld::topp_batch(const double* path, const int32_t* n_waypoints, int64_t rows, int32_t max_waypoints,
+                               const double* vel_limits, const double* acc_limits, const mpg_topp_options& opt,
+                               double* times, double* position, double* velocity, double* acceleration,
+                               int32_t* n_samples, double* duration, uint8_t* status, double* grid_x, double* grid_t,
+                               int mem, void* stream) {
+  ensure_snapshot(CollisionRequest());
+  check_status(mpg_topp_batch(world_->get(), path, n_waypoints, rows, max_waypoints, vel_limits, acc_limits, &opt, times,
+                              position, velocity, acceleration, n_samples, duration, status, grid_x, grid_t, mem,
+                              stream),
+               "mpg_topp_batch");
+}
 void PlanningWorld::collide_batch(const double* q, int64_t n, uint8_t* flags, uint32_t* masks) {
   ensure_snapshot(CollisionRequest());
   check_status(mpg_collide_batch(world_->get(), q, n, flags, masks, MPG_MEM_HOST, nullptr), "mpg_collide_batch");

@@ -851,6 +851,101 @@ int mpg_plan_batch(mpg_world* w, const double* start, const double* goal, int64_
   return st.finish();
 }
 
+// device buffers: every row's profile by topp_row_kernel into the stream's
+// workspace (x and t straight into grid_x / grid_t where the caller asks for
+// them), then the samples.  Launches only; the stream is waited for just where
+// a workspace buffer must grow under queued work.
+static int launch_topp(mpg_world* w, const ToppView& v, const double* path, const int32_t* n_waypoints, long long rows,
+                       double* times, double* position, double* velocity, double* acceleration, int32_t* n_samples,
+                       double* duration, uint8_t* status, double* grid_x, double* grid_t, hipStream_t s) {
+  StreamPin pin(w, s);
+  mpg_world::ToppWork* K = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(w->ws_mu);
+    K = &w->topp_ws[s];
+  }
+  const size_t nm = (size_t)rows * v.max_waypoints * std::max(v.dof, 1), ng = (size_t)rows * ((size_t)v.ncap + 1);
+  const auto grows = [](const DevBuf<double>& b, size_t n) { return b.get() && b.cap() < n; };
+  if (grows(K->M, nm) || grows(K->K, ng) || (!grid_x && grows(K->x, ng)) || (!grid_t && grows(K->t, ng)))
+    HIP_TRY(hipStreamSynchronize(s));  // queued work may still use it
+  HIP_TRY(K->M.reserve(nm));
+  HIP_TRY(K->K.reserve(ng));
+  if (!grid_x) HIP_TRY(K->x.reserve(ng));
+  if (!grid_t) HIP_TRY(K->t.reserve(ng));
+  double* const xs = grid_x ? grid_x : K->x.get();
+  double* const ts = grid_t ? grid_t : K->t.get();
+  hipLaunchKernelGGL(topp_row_kernel, dim3((unsigned)rows), dim3(64), 0, s, v, path, n_waypoints, K->M.get(),
+                     K->K.get(), xs, ts, n_samples, duration, status);
+  HIP_TRY(hipGetLastError());
+  const long long slots = rows * v.max_samples;
+  hipLaunchKernelGGL(topp_sample_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, v, path, n_waypoints,
+                     rows, K->M.get(), xs, ts, n_samples, duration, times, position, velocity, acceleration);
+  HIP_TRY(hipGetLastError());
+  return MPG_OK;
+}
+
+int mpg_topp_batch(mpg_world* w, const double* path, const int32_t* n_waypoints, int64_t rows, int32_t max_waypoints,
+                   const double* vel_limits, const double* acc_limits, const mpg_topp_options* opt, double* times,
+                   double* position, double* velocity, double* acceleration, int32_t* n_samples, double* duration,
+                   uint8_t* status, double* grid_x, double* grid_t, int mem, void* stream) {
+  if (!w) return set_error(MPG_E_INVALID, "world is NULL");
+  if (const int mrc = bad_mem(mem)) return mrc;
+  mpg_topp_options o{0.1, 8, 100, 256};
+  if (opt) o = *opt;
+  const int dof = w->dw.dof;
+  ToppView v{};
+  bool unsupported = false;
+  const std::string why =
+      mpg_args::fill_topp_view(v, o, dof, rows, max_waypoints, vel_limits, acc_limits, &unsupported);
+  if (!why.empty()) return set_error(unsupported ? MPG_E_UNSUPPORTED : MPG_E_INVALID, why);
+  if (rows > 0 && (!n_waypoints || !times || !n_samples || !duration || !status ||
+                   (dof > 0 && (!path || !position || !velocity || !acceleration))))
+    return set_error(MPG_E_INVALID,
+                     "path / n_waypoints / times / position / velocity / acceleration / n_samples / duration / status "
+                     "is NULL");
+  if (mem == MPG_MEM_HOST && rows > 0) {
+    const std::string bad = mpg_args::check_topp_rows(path, n_waypoints, rows, max_waypoints, dof);
+    if (!bad.empty()) return set_error(MPG_E_INVALID, bad);
+  }
+  if (rows == 0) return MPG_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (mem == MPG_MEM_DEVICE)
+    return launch_topp(w, v, path, n_waypoints, rows, times, position, velocity, acceleration, n_samples, duration,
+                       status, grid_x, grid_t, s);
+  std::lock_guard<std::mutex> lk(w->host_mu);
+  if (!s && w->own_stream) s = w->own_stream.get();
+  auto& S = w->topp_stage;
+  const size_t r = (size_t)rows, d1 = (size_t)std::max(dof, 1);
+  const size_t np = r * max_waypoints * dof, ns = r * o.max_samples, nsd = ns * dof, ng = r * ((size_t)v.ncap + 1);
+  HostStage st{s, "TOPP"};
+  st.out(S.path, r * max_waypoints * d1);
+  double* const d_times = st.out(S.times, ns);
+  double* const d_samples = st.out(S.samples, 3 * ns * d1);
+  double* const d_dur = st.out(S.dur, r);
+  double* const d_grid = st.out(S.grid, (grid_x ? ng : 0) + (grid_t ? ng : 0));
+  int32_t* const d_ns = st.out(S.n_samples, r);
+  uint8_t* const d_status = st.out(S.status, r);
+  const double* const d_path = st.in(S.path, path, np);
+  const int32_t* const d_count = st.in(S.count, n_waypoints, r);
+  if (st.rc) return st.rc;
+  double* const d_gx = grid_x ? d_grid : nullptr;
+  double* const d_gt = grid_t ? d_grid + (grid_x ? ng : 0) : nullptr;
+  const int rc = launch_topp(w, v, d_path, d_count, rows, d_times, d_samples, d_samples + nsd, d_samples + 2 * nsd, d_ns,
+                             d_dur, d_status, d_gx, d_gt, s);
+  if (rc) return rc;
+  st.back(times, d_times, ns);
+  st.back(position, d_samples, nsd);
+  st.back(velocity, d_samples + nsd, nsd);
+  st.back(acceleration, d_samples + 2 * nsd, nsd);
+  st.back(n_samples, d_ns, r);
+  st.back(duration, d_dur, r);
+  st.back(status, d_status, r);
+  if (grid_x) st.back(grid_x, d_gx, ng);
+  if (grid_t) st.back(grid_t, d_gt, ng);
+  return st.finish();
+}
+
 int mpg_debug_collide_pairs(mpg_world* w, int32_t geom_a, int32_t geom_b, int64_t n, const double* Ta,
                             const double* Tb, uint8_t* hit) {
   if (!w || n < 0 || (n > 0 && (!Ta || !Tb || !hit))) return set_error(MPG_E_INVALID, "bad arguments");

@@ -12,6 +12,7 @@
 #include "../../include/mpgpu.h"
 #include "mpg_ik.h"
 #include "mpg_rrt.h"
+#include "mpg_topp.h"
 
 namespace mpg_args __attribute__((visibility("hidden"))) {  // nothing of it among the library's exports
 
@@ -134,6 +135,56 @@ inline std::string fill_rrt_view(mpg::RrtView& v, const mpg_plan_options& o, con
            " exceeds 2^31 doubles of tree storage";
   if (Q > ((int64_t)1 << 31) / std::max(v.block, 1 + G))
     return "Q * " + std::to_string(std::max(v.block, 1 + G)) + " states per round exceeds 2^31";
+  return std::string();
+}
+
+// mpg_topp_batch: the options, the limits and the sizes against their bounds,
+// then the call's view.  An empty string, or the reason; *unsupported as above.
+inline std::string fill_topp_view(mpg::ToppView& v, const mpg_topp_options& o, int dof, int64_t rows,
+                                  int32_t max_waypoints, const double* vel, const double* acc, bool* unsupported) {
+  *unsupported = false;
+  if (dof > mpg::kToppDof) {
+    *unsupported = true;
+    return "mpg_topp_batch supports dof <= 32";
+  }
+  if (rows < 0) return "rows < 0";
+  if (!(o.step > 0) || !std::isfinite(o.step)) return "step must be > 0";
+  if (o.grid_per_segment < 1 || o.grid_per_segment > 64) return "grid_per_segment outside [1, 64]";
+  if (o.min_grid < 2 || o.min_grid > 65536) return "min_grid outside [2, 65536]";
+  if (o.max_samples < 1 || o.max_samples > 65536) return "max_samples outside [1, 65536]";
+  if (max_waypoints < 2 || max_waypoints > 4096) return "max_waypoints outside [2, 4096]";
+  if (dof > 0 && (!vel || !acc)) return "vel_limits / acc_limits is NULL";
+  v = mpg::ToppView{};
+  v.dof = dof;
+  v.max_waypoints = max_waypoints;
+  v.grid_per_segment = o.grid_per_segment;
+  v.min_grid = o.min_grid;
+  v.max_samples = o.max_samples;
+  v.ncap = std::max(o.min_grid, o.grid_per_segment * (max_waypoints - 1));
+  v.step = o.step;
+  for (int d = 0; d < dof; ++d) {
+    if (!(std::isfinite(vel[d]) && vel[d] > 0)) return "vel_limits[" + std::to_string(d) + "] must be finite and > 0";
+    if (!(std::isfinite(acc[d]) && acc[d] > 0)) return "acc_limits[" + std::to_string(d) + "] must be finite and > 0";
+    v.vmax[d] = vel[d];
+    v.amax[d] = acc[d];
+  }
+  const int64_t cap = (int64_t)1 << 31, d1 = std::max(dof, 1);
+  if (rows > cap / ((int64_t)max_waypoints * d1)) return "rows * max_waypoints * dof exceeds 2^31";
+  if (rows > cap / ((int64_t)o.max_samples * d1)) return "rows * max_samples * dof exceeds 2^31";
+  if (rows > cap / ((int64_t)v.ncap + 1)) return "rows * (Ncap + 1) exceeds 2^31";
+  return std::string();
+}
+
+// the host-memory rows of mpg_topp_batch: the counts against max_waypoints, finite values inside a row's count
+inline std::string check_topp_rows(const double* path, const int32_t* n_waypoints, int64_t rows, int32_t max_waypoints,
+                                   int dof) {
+  for (int64_t r = 0; r < rows; ++r) {
+    const int32_t n = n_waypoints[r];
+    if (n > max_waypoints) return "n_waypoints[" + std::to_string(r) + "] exceeds max_waypoints";
+    const double* p = path + (size_t)r * max_waypoints * dof;
+    for (int64_t e = 0; e < (int64_t)std::max(n, 0) * dof; ++e)
+      if (!std::isfinite(p[e])) return "non-finite path value in row " + std::to_string(r);
+  }
   return std::string();
 }
 

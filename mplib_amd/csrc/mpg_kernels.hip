@@ -7181,6 +7181,84 @@ __global__ __launch_bounds__(64) void rrt_path_kernel(RrtView v, RrtBufs b, doub
   for (int p = threadIdx.x; p < v.max_waypoints; p += 64) rrt_path_slot(v, b.nodes + row * tree * v.dof, s_idx, n, p, out);
 }
 
+// ---------------------------------------------------------------------------
+// Planner.TOPP (mplib/planner.py:358-375), batched: mpg_topp_batch.  The
+// per-row arithmetic is mpg_topp.h's.
+// ---------------------------------------------------------------------------
+// mpg_topp.h's lane policy for a wave of 64: the minimum is a butterfly, so
+// every lane holds it
+struct ToppWave {
+  static MPG_INLINE int lane() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (int)threadIdx.x;
+#else
+    return 0;
+#endif
+  }
+  static MPG_INLINE int lanes() { return 64; }
+  static MPG_INLINE double wmin(double v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const double u = __shfl_xor(v, o);
+      v = u < v ? u : v;
+    }
+#endif
+    return v;
+  }
+  static MPG_INLINE void sync() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __syncthreads();
+#endif
+  }
+};
+
+// One wave per row, one wave per block.  A row is two dependent chains of N
+// gridpoints (the controllable sets backwards, the profile forwards), each
+// gridpoint a minimum over (2 dof + 1)^2 pairs of constraint rows: the lanes
+// split the joints (spline, constraint rows) and the pairs, the minimum is a
+// wave reduction, the chain's K_k / x_k / t_k are wave-uniform and lane 0
+// stores them.  LDS: the interval's constraint rows.  The workspace M, K, x, t
+// is per row (mpg_world::ToppWork).
+__global__ __launch_bounds__(64) void topp_row_kernel(ToppView v, const double* __restrict__ path,
+                                                     const int32_t* __restrict__ n_waypoints, double* M, double* K,
+                                                     double* x, double* t, int32_t* __restrict__ n_samples,
+                                                     double* __restrict__ duration, uint8_t* __restrict__ status) {
+  __shared__ double s_rows[4 * kToppRows];
+  const size_t row = blockIdx.x;
+  const size_t pstride = (size_t)v.max_waypoints * v.dof, gstride = (size_t)v.ncap + 1;
+  const ToppRowBufs b{M + row * pstride, K + row * gstride, x + row * gstride, t + row * gstride};
+  double dur;
+  int m;
+  const int st = topp_row<ToppWave>(v, path + row * pstride, n_waypoints[row], b, s_rows, &dur, &m);
+  if (threadIdx.x == 0) {
+    n_samples[row] = m;
+    duration[row] = dur;
+    status[row] = (uint8_t)st;
+  }
+}
+
+// One thread per (row, sample slot): a binary search in the row's t, then
+// mpg_topp.h's sample.  Neighbouring threads write neighbouring slots.
+__global__ __launch_bounds__(256) void topp_sample_kernel(ToppView v, const double* __restrict__ path,
+                                                         const int32_t* __restrict__ n_waypoints, long long n_rows,
+                                                         const double* __restrict__ M, const double* __restrict__ x,
+                                                         const double* __restrict__ t,
+                                                         const int32_t* __restrict__ n_samples,
+                                                         const double* __restrict__ duration,
+                                                         double* __restrict__ times, double* __restrict__ pos,
+                                                         double* __restrict__ vel, double* __restrict__ acc) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n_rows * v.max_samples) return;
+  const size_t row = (size_t)(idx / v.max_samples);
+  const int i = (int)(idx - (long long)row * v.max_samples);
+  const size_t pstride = (size_t)v.max_waypoints * v.dof, gstride = (size_t)v.ncap + 1;
+  const ToppRowBufs b{const_cast<double*>(M) + row * pstride, nullptr, const_cast<double*>(x) + row * gstride,
+                      const_cast<double*>(t) + row * gstride};
+  topp_sample(v, path + row * pstride, n_waypoints[row], b, duration[row], n_samples[row], i, times + idx,
+              pos + (size_t)idx * v.dof, vel + (size_t)idx * v.dof, acc + (size_t)idx * v.dof);
+}
+
 // per pair, the configurations whose pair mask has its bit: LDS counters per
 // block (atomics on the block's own copy), then one global add per pair
 __global__ __launch_bounds__(256) void pair_count_kernel(const uint32_t* __restrict__ masks, long long n, int W,

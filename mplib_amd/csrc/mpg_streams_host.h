@@ -12,10 +12,12 @@ void release_stream_locked(mpg_world* w, hipStream_t s) {
   const auto ki = w->ik_ws.find(s);
   const auto ci = w->screw_ws.find(s);
   const auto pi = w->plan_ws.find(s);
+  const auto ti = w->topp_ws.find(s);
   if (wi == w->ws.end() && si == w->sides.end() && ki == w->ik_ws.end() && ci == w->screw_ws.end() &&
-      pi == w->plan_ws.end())
+      pi == w->plan_ws.end() && ti == w->topp_ws.end())
     return;
   hipDeviceSynchronize();
+  if (ti != w->topp_ws.end()) w->topp_ws.erase(ti);
   if (pi != w->plan_ws.end()) w->plan_ws.erase(pi);
   if (ki != w->ik_ws.end()) w->ik_ws.erase(ki);
   if (ci != w->screw_ws.end()) w->screw_ws.erase(ci);

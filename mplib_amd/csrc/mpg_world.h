@@ -83,6 +83,11 @@ struct mpg_world {
     DevBuf<uint8_t> status;
     DevBuf<int32_t> count, iters, sizes;
   } plan_stage;
+  struct ToppStage {
+    DevBuf<double> path, times, samples, dur, grid;  // samples: position, velocity, acceleration; grid: x, t
+    DevBuf<int32_t> count, n_samples;
+    DevBuf<uint8_t> status;
+  } topp_stage;
   // phase A/B workspace, one per stream so concurrent streams never share it
   struct Workspace {
     DevBuf<uint32_t> surv;       // [W * cap] survivor bits, word-major
@@ -140,6 +145,14 @@ struct mpg_world {
     DevBuf<uint8_t> flags;
   };
   std::map<hipStream_t, PlanWork> plan_ws;
+  // mpg_topp_batch: per caller stream the rows' spline moments, controllable
+  // sets, profiles and times (ToppRowBufs per row; guarded by ws_mu, released
+  // with the stream's workspace)
+  struct ToppWork {
+    DevBuf<double> M;        // [rows][max_waypoints][dof]
+    DevBuf<double> K, x, t;  // [rows][Ncap + 1]
+  };
+  std::map<hipStream_t, ToppWork> topp_ws;
   // free frames: the current poses (host copy; free_dev is the device buffer
   // DevWorld::free_cur points to)
   std::vector<double> free_host;

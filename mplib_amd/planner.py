@@ -192,11 +192,93 @@ def ik(world, link, goal_pose, start_qpos, mask=None, *, n_init_qpos: int = 20, 
 
 
 # ---------------------------------------------------------------------------
+# Planner.TOPP (planner.py:358-375): the time-optimal parametrisation of
+# joint-space paths under velocity and acceleration limits, many paths in one
+# device call (PlanningWorld.topp_batch, C ABI mpg_topp_batch).
+# ---------------------------------------------------------------------------
+TOPP_OK, TOPP_NO_PATH, TOPP_ZERO_LENGTH, TOPP_STALLED, TOPP_TRUNCATED = 1, 2, 4, 8, 16
+_TOPP_NAMES = ((TOPP_OK, "OK"), (TOPP_NO_PATH, "NO_PATH"), (TOPP_ZERO_LENGTH, "ZERO_LENGTH"), (TOPP_STALLED, "STALLED"),
+               (TOPP_TRUNCATED, "TRUNCATED"))
+_TOPP_KEYS = ("time", "position", "velocity", "acceleration")  # the reference's keys (planner.py:512-519)
+_TOPP_MAX_SAMPLES = 65536
+
+
+def topp_reason(status: int) -> str:
+    """The names of a topp_batch row's status bits."""
+    return ", ".join(n for b, n in _TOPP_NAMES if int(status) & b)
+
+
+def _topp_rows(world, path, count, joint_vel_limits, joint_acc_limits, step):
+    """One topp_batch call over path [rows, max_waypoints, dof] / count [rows],
+    and a second one with room for the longest row when the default 256
+    samples truncate some.  Returns per row (status, duration, (times,
+    position, velocity, acceleration) cut to the row's samples)."""
+    vel = np.asarray(joint_vel_limits, np.float64)
+    acc = np.asarray(joint_acc_limits, np.float64)
+    res = world.topp_batch(path, count, vel, acc, step=float(step))
+    status, dur = res[6], res[5]
+    cut = (status & TOPP_TRUNCATED) != 0
+    if cut.any():
+        need = int((dur[cut] / float(step)).max())
+        if need <= _TOPP_MAX_SAMPLES:
+            res = world.topp_batch(path, count, vel, acc, step=float(step), max_samples=need)
+            status, dur = res[6], res[5]
+    return [(int(status[r]), float(dur[r]), tuple(a[r, :res[4][r]].copy() for a in res[:4])) for r in range(len(count))]
+
+
+def _pack_paths(paths):
+    """(path [rows, max_waypoints, dof] padded with each row's last waypoint, count [rows])."""
+    paths = [np.asarray(p, np.float64) for p in paths]
+    if any(p.ndim != 2 for p in paths):
+        raise ValueError("a path must be [n, dof]")
+    mw = max([2] + [len(p) for p in paths])
+    out = np.zeros((len(paths), mw, paths[0].shape[1] if paths else 0))
+    for r, p in enumerate(paths):
+        if len(p):
+            out[r, :len(p)] = p
+            out[r, len(p):] = p[-1]
+    return out, np.array([len(p) for p in paths], np.int32)
+
+
+def topp(world, path, joint_vel_limits, joint_acc_limits, step: float = 0.1):
+    """Planner.TOPP: one path [n, dof] returns the reference's tuple (times,
+    position, velocity, acceleration, duration); a list of paths returns a list
+    of such tuples, all from one device call.  A path that cannot be
+    parametrised (fewer than two waypoints, all waypoints equal, a stalled
+    profile, more than 65536 samples) raises ValueError with the names of its
+    status bits -- in a list it is None instead."""
+    single = not isinstance(path, (list, tuple))
+    packed, count = _pack_paths([path] if single else path)
+    out = []
+    for st, dur, arrays in _topp_rows(world, packed, count, joint_vel_limits, joint_acc_limits, step):
+        out.append(arrays + (dur,) if st == TOPP_OK else None)
+        if single and st != TOPP_OK:
+            raise ValueError("topp: " + topp_reason(st))
+    return out[0] if single else out
+
+
+def _add_topp(world, results, ok, path, count, joint_vel_limits, joint_acc_limits, time_step):
+    """The time parametrisation of the Success rows (ok [rows] bool) of a
+    batch into their dictionaries: the reference's keys, or "topp": the
+    status bits' names where a row is not parametrised."""
+    if joint_vel_limits is None or joint_acc_limits is None or not np.any(ok):
+        return
+    rows = _topp_rows(world, path, np.where(ok, count, 0).astype(np.int32), joint_vel_limits, joint_acc_limits,
+                      time_step)
+    for i in np.flatnonzero(ok):
+        st, dur, arrays = rows[i]
+        if st == TOPP_OK:
+            results[i].update(zip(_TOPP_KEYS, arrays), duration=dur)
+        else:
+            results[i]["topp"] = topp_reason(st)
+
+
+# ---------------------------------------------------------------------------
 # Planner.plan_screw (planner.py:526-671): the straight-line screw motion to a
 # goal pose, its waypoints integrated and collision-checked by one device call
 # (PlanningWorld.plan_screw_batch, C ABI mpg_screw_batch).  The result is the
-# joint-space path the reference hands to TOPP-RA; the time parametrisation is
-# not part of it.
+# joint-space path the reference hands to TOPP-RA, and with the joint limits
+# given its time parametrisation (topp above).
 # ---------------------------------------------------------------------------
 SCREW_REACHED, SCREW_COLLISION_FREE, SCREW_VALID = 1, 2, 3
 SCREW_STALLED, SCREW_LIMIT, SCREW_TRUNCATED, SCREW_SINGULAR, SCREW_ROT_PI = 4, 8, 16, 32, 64
@@ -213,33 +295,40 @@ def screw_reason(status: int, first_hit: int = -1) -> str:
     return ", ".join(names)
 
 
-def plan_screw(world, link, goal_pose, current_qpos, qpos_step: float = 0.1, *, max_waypoints: int = 64):
+def plan_screw(world, link, goal_pose, current_qpos, qpos_step: float = 0.1, *, max_waypoints: int = 64,
+               joint_vel_limits=None, joint_acc_limits=None, time_step: float = 0.1):
     """Planner.plan_screw over the world's state: ``goal_pose`` (7,) returns
     {"status": "Success", "path": [count, dof]} or {"status": "screw plan
     failed", "reason": names of the status bits}; an (n, 7) array returns a
     list of such dictionaries, all from one device call, every row starting at
     ``current_qpos`` ((dof,) or [n, dof]).  ``link``: a planned articulation's
-    user link name (or a world link index).  The articulations' qpos is not
-    touched."""
+    user link name (or a world link index).  With ``joint_vel_limits`` and
+    ``joint_acc_limits`` [dof] every Success also carries the reference's
+    "time", "position", "velocity", "acceleration" and "duration" (one
+    topp_batch call over the rows, samples every ``time_step``), or "topp":
+    the names of the status bits of a path that could not be parametrised.
+    The articulations' qpos is not touched."""
     goals = np.asarray(goal_pose, np.float64)
     single = goals.ndim == 1
     goals = goals.reshape(-1, 7)
     path, count, status, hit = world.plan_screw_batch(link, goals, np.asarray(current_qpos, np.float64),
                                                       qpos_step=float(qpos_step), max_waypoints=int(max_waypoints))
     out = []
+    ok = (np.asarray(status) & SCREW_VALID) == SCREW_VALID
     for i in range(len(goals)):
-        if (int(status[i]) & SCREW_VALID) == SCREW_VALID:
+        if ok[i]:
             out.append({"status": "Success", "path": path[i, :count[i]].copy()})
         else:
             out.append({"status": "screw plan failed", "reason": screw_reason(status[i], hit[i])})
+    _add_topp(world, out, ok, path, count, joint_vel_limits, joint_acc_limits, time_step)
     return out[0] if single else out
 
 
 # ---------------------------------------------------------------------------
-# Planner.plan (planner.py:358-524) without its time parametrisation: the
-# RRTConnect searches of many (start, goals) rows in one device call
-# (PlanningWorld.plan_batch, C ABI mpg_plan_batch), and the IK in front of
-# them for goals given as poses.
+# Planner.plan (planner.py:358-524): the RRTConnect searches of many (start,
+# goals) rows in one device call (PlanningWorld.plan_batch, C ABI
+# mpg_plan_batch), the IK in front of them for goals given as poses, and with
+# the joint limits given the paths' time parametrisation (topp above).
 # ---------------------------------------------------------------------------
 PLAN_SOLVED, PLAN_START_INVALID, PLAN_GOAL_INVALID = 1, 2, 4
 PLAN_ROUNDS_EXHAUSTED, PLAN_NODES_EXHAUSTED, PLAN_TRUNCATED = 8, 16, 32
@@ -254,13 +343,19 @@ def plan_reason(status: int) -> str:
 
 
 def plan_batch(world, start_qpos, goal_qpos, *, range: float = 0.0, max_rounds: int = 20000, max_nodes: int = 2048,
-               max_waypoints: int = 256, seed: int = 0, row_seed=None, check_every: int = 8):
+               max_waypoints: int = 256, seed: int = 0, row_seed=None, check_every: int = 8,
+               joint_vel_limits=None, joint_acc_limits=None, time_step: float = 0.1):
     """Planner.plan's RRTConnect for many queries in one device call:
     ``goal_qpos`` [Q, dof] (one goal state per row) or [Q, G, dof], every row
     starting at ``start_qpos`` ((dof,) or [Q, dof]).  Returns per row {"status":
     "Success", "path": [count, dof]} or {"status": "plan failed", "reason":
-    names of the status bits}.  The paths are RRTConnect's, neither simplified
-    nor time-parametrised.  The articulations' qpos is not touched."""
+    names of the status bits}.  The paths are RRTConnect's, not simplified
+    (the reference does not simplify them either).  With ``joint_vel_limits``
+    and ``joint_acc_limits`` [dof] every Success also carries the reference's
+    "time", "position", "velocity", "acceleration" and "duration" (one
+    topp_batch call over the rows, samples every ``time_step``), or "topp": the
+    names of the status bits of a path that could not be parametrised.  The
+    articulations' qpos is not touched."""
     path, count, status, _, _ = world.plan_batch(np.asarray(start_qpos, np.float64), np.asarray(goal_qpos, np.float64),
                                                  range=float(range), max_rounds=int(max_rounds),
                                                  max_nodes=int(max_nodes), max_waypoints=int(max_waypoints),
@@ -271,18 +366,22 @@ def plan_batch(world, start_qpos, goal_qpos, *, range: float = 0.0, max_rounds: 
             out.append({"status": "Success", "path": path[i, :count[i]].copy()})
         else:
             out.append({"status": "plan failed", "reason": plan_reason(status[i])})
+    _add_topp(world, out, np.asarray(status) == PLAN_SOLVED, path, count, joint_vel_limits, joint_acc_limits, time_step)
     return out
 
 
 def plan_to_pose_batch(world, link, goal_poses, start_qpos, *, max_goals: int = 4, n_init_qpos: int = 20,
-                       threshold: float = 1e-3, ik_seed: int = 0, **plan_options):
-    """What Planner.plan does before TOPP-RA, for M goal poses [M, 7] of
+                       threshold: float = 1e-3, ik_seed: int = 0, joint_vel_limits=None, joint_acc_limits=None,
+                       time_step: float = 0.1, **plan_options):
+    """What Planner.plan does, for M goal poses [M, 7] of
     ``link`` at once: one ik_batch call (``n_init_qpos`` seeds per pose, seed 0
     = ``start_qpos`` (dof,)), up to ``max_goals`` of each pose's valid answers
     (Planner.IK's selection: seed order, none within 0.1 of an earlier one) as
     the row's goal states, then one plan_batch call over the poses that have
     an answer.  Returns per pose plan_batch's dictionary, or {"status": "IK
-    failed", "reason": Planner.IK's message}.  ``plan_options``: plan_batch's."""
+    failed", "reason": Planner.IK's message}.  ``joint_vel_limits`` /
+    ``joint_acc_limits`` / ``time_step``: the paths' time parametrisation, as
+    in plan_batch.  ``plan_options``: plan_batch's."""
     goals = np.asarray(goal_poses, np.float64).reshape(-1, 7)
     start = np.asarray(start_qpos, np.float64).reshape(-1)
     q, status, _, _ = world.ik_batch(link, goals, start_qpos=start, n_init_qpos=int(n_init_qpos), seed=int(ik_seed),
@@ -299,6 +398,7 @@ def plan_to_pose_batch(world, link, goal_poses, start_qpos, *, max_goals: int = 
         rows.append(int(g))
         states.append(np.array(kept + [kept[0]] * (G - len(kept))))  # a repeated goal is a second root on the same state
     if rows:
-        for g, res in zip(rows, plan_batch(world, start, np.array(states), **plan_options)):
+        for g, res in zip(rows, plan_batch(world, start, np.array(states), joint_vel_limits=joint_vel_limits,
+                                           joint_acc_limits=joint_acc_limits, time_step=time_step, **plan_options)):
             out[g] = res
     return out
