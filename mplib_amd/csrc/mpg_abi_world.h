@@ -802,6 +802,10 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
   const size_t o_ggf = has_grid ? bb.add(grid_f.data(), grid_f.size()) : 0;
   const size_t o_ggi = has_grid ? bb.add(grid_i.data(), grid_i.size()) : 0;
   const size_t o_gst = has_grid ? bb.add(gst_start.data(), gst_start.size()) : 0;
+  std::vector<int> rev_src = revolute_sources(d->joint_type, d->joint_q_source, d->n_joints);
+  const int n_rev = (int)rev_src.size();
+  if (rev_src.empty()) rev_src.push_back(0);
+  const size_t o_rvs = bb.add(rev_src.data(), rev_src.size());
 
   std::unique_ptr<mpg_world> w(new mpg_world());  // every failure below releases what was built
   w->device = device;
@@ -841,6 +845,8 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
   dw.n_free = n_free;
   dw.far_r = far_r;
   dw.free_obj = to_cptr<int>(base + o_fob);
+  dw.n_rev = n_rev;
+  dw.rev_src = to_cptr<int>(base + o_rvs);
   dw.free_cur = nullptr;
   if (n_free) {  // the current poses start at the frames' link_placement, as (p, wxyz)
     w->free_host.resize((size_t)n_free * 7);
@@ -1057,10 +1063,7 @@ int mpg_world_create(const mpg_world_desc* d_in, int device, mpg_world** out) {
   if (const char* e = std::getenv("MPG_OVERLAP_PARTS")) w->overlap_parts = std::atoi(e);
   if (const char* e = std::getenv("MPG_SMALL_HOST_SC")) w->small_host_sc = std::atoll(e);
   if (const char* e = std::getenv("MPG_SMALL_ARGS")) w->small_args = std::atoi(e) != 0;
-  for (int j = 0; j < d->n_joints; ++j)
-    if (d->joint_q_source[j] >= 0 && joint_is_revolute(d->joint_type[j]) &&
-        std::find(w->h_rev_src.begin(), w->h_rev_src.end(), d->joint_q_source[j]) == w->h_rev_src.end())
-      w->h_rev_src.push_back(d->joint_q_source[j]);
+  w->h_rev_src.assign(rev_src.begin(), rev_src.begin() + n_rev);
   if (const char* e = std::getenv("MPG_SMALL_SERVER")) w->srv_mode = std::atoi(e);
   w->srv_stats = std::getenv("MPG_STATS") != nullptr;
   if (const char* e = std::getenv("MPG_SMALL_SERVER_IDLE_US")) w->srv_idle_us = std::max(10ll, std::atoll(e));

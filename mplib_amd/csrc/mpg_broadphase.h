@@ -540,6 +540,125 @@ MPG_INLINE bool bp_support_separated(const FObb& A, const FObb& B, int ta, int t
   return sep;
 }
 
+// The two tests above in one pass, as the cull's SAT drain runs them: what
+// both need of a pair (d, Rm = A^T B, t = A^T d) is formed once, the 15 SAT
+// axes are evaluated on it, and the support-height axes follow on the same
+// values.  Every expression is written as in fobb_separated and
+// bp_support_separated, so each part decides bit for bit what they decide.
+struct BpPairFrame {
+  float d[3], Rm[3][3], t[3];
+};
+
+MPG_INLINE BpPairFrame bp_pair_frame(const FObb& A, const FObb& B) {
+  MPG_FP32_CONTRACT
+  BpPairFrame F;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) F.d[k] = B.c[k] - A.c[k];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) F.Rm[i][j] = A.R[i] * B.R[j] + A.R[3 + i] * B.R[3 + j] + A.R[6 + i] * B.R[6 + j];
+    F.t[i] = F.d[0] * A.R[i] + F.d[1] * A.R[3 + i] + F.d[2] * A.R[6 + i];
+  }
+  return F;
+}
+
+// fobb_separated on a formed frame
+MPG_INLINE bool bp_frame_sat_separated(const FObb& A, const FObb& B, const BpPairFrame& F, float margin) {
+  MPG_FP32_CONTRACT
+  float Ab[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) Ab[i][j] = fabsf(F.Rm[i][j]) + 1e-6f;
+  bool sep = false;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const float rb = B.e[0] * Ab[i][0] + B.e[1] * Ab[i][1] + B.e[2] * Ab[i][2];
+    sep |= fabsf(F.t[i]) > A.e[i] + rb + margin;
+  }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const float ra = A.e[0] * Ab[0][j] + A.e[1] * Ab[1][j] + A.e[2] * Ab[2][j];
+    const float tb = F.t[0] * F.Rm[0][j] + F.t[1] * F.Rm[1][j] + F.t[2] * F.Rm[2][j];
+    sep |= fabsf(tb) > ra + B.e[j] + margin;
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+      const float ra = A.e[i1] * Ab[i2][j] + A.e[i2] * Ab[i1][j];
+      const float rb = B.e[j1] * Ab[i][j2] + B.e[j2] * Ab[i][j1];
+      const float tl = F.t[i2] * F.Rm[i1][j] - F.t[i1] * F.Rm[i2][j];
+      sep |= fabsf(tl) > ra + rb + margin;
+    }
+  }
+  return sep;
+}
+
+// bp_support_separated on a formed frame: what r8 found holds here too (no
+// early exit between axes, the useful sign of each box axis only, two lookups
+// in flight between the fences)
+template <class P>
+MPG_INLINE bool bp_frame_support_separated(const FObb& A, const FObb& B, const BpPairFrame& F, int ta, int tb, P tab,
+                                           float margin) {
+  MPG_FP32_CONTRACT
+  float s[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) s[i] = F.d[0] * B.R[i] + F.d[1] * B.R[3 + i] + F.d[2] * B.R[6 + i];
+  const float dd = F.d[0] * F.d[0] + F.d[1] * F.d[1] + F.d[2] * F.d[2];
+  float ha = A.e[0] * fabsf(F.t[0]) + A.e[1] * fabsf(F.t[1]) + A.e[2] * fabsf(F.t[2]);
+  float hb = B.e[0] * fabsf(s[0]) + B.e[1] * fabsf(s[1]) + B.e[2] * fabsf(s[2]);
+  bool sep = false;
+  if (ta >= 0) {  // A's table: the centre direction and B's box axes, in A's frame
+    const P tA = tab + (size_t)ta * kShFloats;
+    ha = bp_support_height(tA, F.t[0], F.t[1], F.t[2]);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      if (j == 1) MPG_SCHED_FENCE;
+      const float sg = s[j] < 0.f ? -1.f : 1.f;
+      const float h = bp_support_height(tA, sg * F.Rm[0][j], sg * F.Rm[1][j], sg * F.Rm[2][j]);
+      sep |= fabsf(s[j]) - h - B.e[j] > margin;
+    }
+  }
+  if (tb >= 0) {  // B's table: minus the centre direction and minus A's box axes, in B's frame
+    const P tB = tab + (size_t)tb * kShFloats;
+    hb = bp_support_height(tB, -s[0], -s[1], -s[2]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      if (i == 1) MPG_SCHED_FENCE;
+      const float sg = F.t[i] < 0.f ? 1.f : -1.f;
+      const float h = bp_support_height(tB, sg * F.Rm[i][0], sg * F.Rm[i][1], sg * F.Rm[i][2]);
+      sep |= fabsf(F.t[i]) - A.e[i] - h > margin;
+    }
+  }
+  sep |= dd - ha - hb > margin * sqrtf(dd);
+  return sep;
+}
+
+// fobb_separated(A, B, sat_margin) || bp_support_separated(A, B, ta, tb, tab, sh_margin)
+template <class P>
+MPG_INLINE bool bp_sat_support_separated(const FObb& A, const FObb& B, int ta, int tb, P tab, float sat_margin,
+                                         float sh_margin) {
+  const BpPairFrame F = bp_pair_frame(A, B);
+  if (bp_frame_sat_separated(A, B, F, sat_margin)) return true;
+  return bp_frame_support_separated(A, B, F, ta, tb, tab, sh_margin);
+}
+
+// The cull's fp64 sincos pass as items: item i of total * n_rev is
+// (compacted configuration k, revolute source slot r) = (i / n_rev, i % n_rev),
+// so a configuration's items are adjacent; thread tid of a block of `block`
+// threads takes the items tid, tid + block, ...
+template <class F>
+MPG_INLINE void bp_sincos_items(uint32_t tid, uint32_t block, uint32_t total, uint32_t n_rev, F&& f) {
+  for (uint32_t i = tid; i < total * n_rev; i += block) {
+    const uint32_t k = i / n_rev;
+    f(k, i - k * n_rev);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // host: build the program from a world descriptor + the per-geometry local
 // OBB records (centre, half extents, bounding radius about that centre)

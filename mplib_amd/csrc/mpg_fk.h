@@ -169,6 +169,10 @@ struct DevWorld {
   cptr<int> free_obj;
   const double* free_cur;
   double far_r;
+  // the move-group slots of the revolute joints (revolute_sources): what the
+  // cull's fp64 sincos pass evaluates per configuration with a candidate
+  int n_rev;
+  cptr<int> rev_src;  // [n_rev]
 };
 constexpr int kLatChain = 12;
 // latency pair record: header, then per side (0 = pair_a, 1 = pair_b) the
@@ -197,6 +201,17 @@ MPG_INLINE SE3 load_se3(P p) {
 
 // pinocchio JointModel*::calc as a plain SE3 (see oracle/collide_oracle.c)
 MPG_INLINE bool joint_is_revolute(int type) { return type <= MPG_JOINT_REVOLUTE_UNALIGNED || type >= MPG_JOINT_RUBX; }
+
+// host: the move-group slots (joint_q_source >= 0) of the revolute joints,
+// each once, in joint order: the sc elements a row needs
+inline std::vector<int> revolute_sources(const int* joint_type, const int* joint_q_source, int nj) {
+  std::vector<int> out;
+  for (int j = 0; j < nj; ++j)
+    if (joint_q_source[j] >= 0 && joint_is_revolute(joint_type[j]) &&
+        std::find(out.begin(), out.end(), joint_q_source[j]) == out.end())
+      out.push_back(joint_q_source[j]);
+  return out;
+}
 
 // sc: optional precomputed (mpg_sin(v), mpg_cos(v)) for revolute joints
 template <class P>

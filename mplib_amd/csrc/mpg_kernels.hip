@@ -1083,61 +1083,79 @@ __device__ __forceinline__ FObb bp_obb(const DevWorld& w, const float* __restric
   return o;
 }
 
-// The support-height axes (mpg_broadphase.h bp_support_separated) on cnt SAT
-// survivors, one (schedule entry, lane) per lane: the pairs they do not
-// separate either are the candidates.
+// Both OBBs of a queue entry.  Moving-static entries reach the queue before
+// moving-moving ones, so the lanes of most drains agree on which side is
+// static: such a drain takes a wave-uniform branch with no divergent branch
+// around either object's loads, and A's and B's loads (rq, the static record,
+// the centres from LDS) are issued together in front of one wait.  A mixed
+// drain fetches one object after the other.
 template <int BLOCK>
-__device__ __forceinline__ void support_drain(const DevWorld& w, const float* __restrict__ cen, const float* __restrict__ rq,
-                                           long long cap, long long cfg0, uint32_t* survw, uint32_t e, uint32_t cnt,
-                                           int wbase, uint32_t lane) {
-  if (lane < cnt) {
-    const cptr<int> r = w.sched_rec + SR_STRIDE * (int)(e >> 6);
-    const int p = r[SR_P], sh = r[SR_SH], t = wbase + (int)(e & 63u);
-    const FObb A = bp_obb<BLOCK>(w, cen, rq, cap, r[SR_A], t, cfg0 + t);
-    const FObb B = bp_obb<BLOCK>(w, cen, rq, cap, r[SR_B], t, cfg0 + t);
-    if (!bp_support_separated(A, B, (sh & 0xffff) - 2, (sh >> 16) - 2, w.bp.shtab, w.sh_margin))
-      atomicOr(&survw[(p >> 5) * BLOCK + t], 1u << (p & 31));
+__device__ __forceinline__ void bp_obb_pair(const DevWorld& w, const float* __restrict__ cen, const float* __restrict__ rq,
+                                            long long cap, int ia, int ib, int t, long long cfg, FObb& A, FObb& B) {
+  const unsigned long long act = __ballot(true);
+  const unsigned long long ma = __ballot(ia < w.n_moving), mb = __ballot(ib < w.n_moving);
+  auto moving = [&](int id, FObb& o) {
+    const float* q = rq + (size_t)id * 4 * cap + cfg;
+    const float qx = q[0], qy = q[cap], qz = q[2 * cap], qw = q[3 * cap];
+    const float* c = cen + (size_t)id * 3 * BLOCK + t;
+    o.c[0] = c[0];
+    o.c[1] = c[BLOCK];
+    o.c[2] = c[2 * BLOCK];
+    const cptr<float> g = w.bp.mobj + BM_STRIDE * id;
+    o.e[0] = g[BM_E];
+    o.e[1] = g[BM_E + 1];
+    o.e[2] = g[BM_E + 2];
+    return [=, &o]() { f_quat_to_mat(qw, qx, qy, qz, o.R); };
+  };
+  auto fixed = [&](int id, FObb& o) {
+    const cptr<float> g = w.bp.sobj + BS_STRIDE * (id - w.n_moving);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o.c[k] = g[BS_C + k];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) o.R[k] = g[BS_R + k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o.e[k] = g[BS_E + k];
+  };
+  if (ma == act && mb == 0ull) {
+    auto ra = moving(ia, A);
+    fixed(ib, B);
+    ra();
+  } else if (ma == act && mb == act) {
+    auto ra = moving(ia, A);
+    auto rb = moving(ib, B);
+    ra();
+    rb();
+  } else {
+    A = bp_obb<BLOCK>(w, cen, rq, cap, ia, t, cfg);
+    B = bp_obb<BLOCK>(w, cen, rq, cap, ib, t, cfg);
   }
 }
 
+// One drain of the SAT queue: cnt (schedule entry, lane) entries, one per
+// lane.  The pair's frame (mpg_broadphase.h bp_pair_frame) is formed once; a
+// lane whose pair the 15 SAT axes keep and which has a support-height table
+// takes the support-height axes at once on the OBBs and the frame it holds,
+// and the pairs neither test separates are the candidates.  The support part
+// is skipped for the whole wave when no lane needs it.
 template <int BLOCK>
 __device__ __forceinline__ void sat_drain(const DevWorld& w, const float* __restrict__ cen, const float* __restrict__ rq,
                                           long long cap, long long cfg0, uint32_t* survw, const uint32_t* queue,
-                                          uint32_t head, uint32_t cnt, int wbase, uint32_t lane, uint32_t& pend,
-                                          uint32_t& npend) {
+                                          uint32_t head, uint32_t cnt, int wbase, uint32_t lane) {
   __builtin_amdgcn_wave_barrier();
-  uint32_t e = 0u;
-  bool keep = false;
   if (lane < cnt) {
-    e = queue[(head + lane) & (kQueue - 1)];  // (schedule entry, lane)
+    const uint32_t e = queue[(head + lane) & (kQueue - 1)];  // (schedule entry, lane)
     const cptr<int> r = w.sched_rec + SR_STRIDE * (int)(e >> 6);
     const int p = r[SR_P], sh = r[SR_SH], t = wbase + (int)(e & 63u);
-    const FObb A = bp_obb<BLOCK>(w, cen, rq, cap, r[SR_A], t, cfg0 + t);
-    const FObb B = bp_obb<BLOCK>(w, cen, rq, cap, r[SR_B], t, cfg0 + t);
-    if (!fobb_separated(A, B, w.bp_margin)) {
-      if ((sh & 0xffff) == SH_SKIP + 2) atomicOr(&survw[(p >> 5) * BLOCK + t], 1u << (p & 31));
-      else keep = true;
+    FObb A, B;
+    bp_obb_pair<BLOCK>(w, cen, rq, cap, r[SR_A], r[SR_B], t, cfg0 + t, A, B);
+    const BpPairFrame F = bp_pair_frame(A, B);
+    bool keep = !bp_frame_sat_separated(A, B, F, w.bp_margin);
+    // 16: diagnostics, the fused pass without its support part
+    const bool more = keep && (sh & 0xffff) != SH_SKIP + 2 && !w.dbg(16);
+    if (__ballot(more) != 0ull) {
+      if (more) keep = !bp_frame_support_separated(A, B, F, (sh & 0xffff) - 2, (sh >> 16) - 2, w.bp.shtab, w.sh_margin);
     }
-  }
-  // SAT survivors with a support-height table wait in `pend` (one entry per
-  // lane, lanes [0, npend)) until 64 of them fill a wave: the survivors move
-  // to the lanes after the pending ones (a forward lane permute, no LDS
-  // storage; the other lanes take the remaining targets so that the targets
-  // are a permutation), wrapping to lane 0 once a full wave has been tested
-  const unsigned long long bal = __ballot(keep);
-  const uint32_t ns = (uint32_t)__popcll(bal);
-  if (ns) {
-    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-    const uint32_t dst = keep ? npend + rank : npend + ns + (lane - rank);
-    const uint32_t recv = (uint32_t)__builtin_amdgcn_ds_permute((int)((dst & 63u) << 2), (int)e);
-    if (npend + ns >= 64u) {
-      support_drain<BLOCK>(w, cen, rq, cap, cfg0, survw, lane >= npend ? recv : pend, 64, wbase, lane);
-      pend = recv;
-      npend = npend + ns - 64u;
-    } else {
-      if (lane >= npend && lane < npend + ns) pend = recv;
-      npend += ns;
-    }
+    if (keep) atomicOr(&survw[(p >> 5) * BLOCK + t], 1u << (p & 31));
   }
   __builtin_amdgcn_wave_barrier();
 }
@@ -1249,7 +1267,6 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) v
   }
 
   uint32_t head = 0, tail = 0;  // wave-uniform queue cursors
-  uint32_t pend = 0u, npend = 0u;  // SAT survivors waiting for the support-height axes (sat_drain)
   uint32_t dbg_keep = 0u;       // diagnostics (11): the bounding tests' bits, kept alive
   // queue the entries [eb, eb + 32) some lane kept (kb: this lane's bits);
   // drain 64 queued (pair, lane) entries through the SAT at a time
@@ -1290,7 +1307,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) v
       }
       tail += total;
       while (tail - head >= 64) {
-        sat_drain<BLOCK>(w, cen, rq, cap, cfg0, survw, queue, head, 64, wbase, lane, pend, npend);
+        sat_drain<BLOCK>(w, cen, rq, cap, cfg0, survw, queue, head, 64, wbase, lane);
         head += 64;
       }
       return;
@@ -1313,7 +1330,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) v
       }
       tail += (uint32_t)__popcll(bal);
       if (tail - head >= 64) {
-        sat_drain<BLOCK>(w, cen, rq, cap, cfg0, survw, queue, head, 64, wbase, lane, pend, npend);
+        sat_drain<BLOCK>(w, cen, rq, cap, cfg0, survw, queue, head, 64, wbase, lane);
         head += 64;
       }
     }
@@ -1410,12 +1427,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) v
       push(eb, kb);
     }
   }
-  if (tail != head) sat_drain<BLOCK>(w, cen, rq, cap, cfg0, survw, queue, head, tail - head, wbase, lane, pend, npend);
-  if (npend) support_drain<BLOCK>(w, cen, rq, cap, cfg0, survw, pend, npend, wbase, lane);
+  if (tail != head) sat_drain<BLOCK>(w, cen, rq, cap, cfg0, survw, queue, head, tail - head, wbase, lane);
   __builtin_amdgcn_wave_barrier();
   if (forced)
     for (int k = 0; k < w.W; ++k) survw[k * BLOCK + tid] = (uint32_t)w.all_mask[k];
-  if (w.dbg(8) || w.dbg(11)) {  // ablation: bounding tests + SAT only (11: without the queue and SAT)
+  if (w.dbg(8) || w.dbg(11) || w.dbg(16)) {  // ablation: bounding tests + SAT only (11: without the queue and SAT; 16: SAT without the support axes)
     if (live && (survw[tid] == 12345u || dbg_keep == 12345u)) flags[cfg] = 2;
     return;
   }
@@ -1471,7 +1487,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) v
   // Exact fp64 sin/cos of every revolute move-group joint for the narrow
   // phase's chain FK (the glibc sincos restatement), only for configurations
   // with a candidate pair (about a quarter of them): compacted across the
-  // block through LDS (the SAT queues are free now) so every lane works.
+  // block through LDS (the SAT queues are free now) and given out joint by
+  // joint, so every wave of the block works and no lane walks the joints in
+  // series.
   uint32_t* list = survw + (size_t)w.W * BLOCK;  // [BLOCK] + per-wave counts [BLOCK / 64]
   uint32_t* wcnt = list + BLOCK;
   __syncthreads();
@@ -1486,17 +1504,16 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) v
   if (any)
     list[off + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))] = tid;
   __syncthreads();
-  if ((uint32_t)tid < total) {
-    const long long r = cfg0 + list[tid];
-    for (int j = 0; j < w.nj; ++j) {
-      const int src = w.joint_q_source[j];
-      if (src < 0 || !joint_is_revolute(w.joint_type[j])) continue;
-      double sv, cv;
-      mpg_sincos(in[r * w.dof + src], &sv, &cv);
-      sc[(r * w.dof + src) * 2] = sv;
-      sc[(r * w.dof + src) * 2 + 1] = cv;
-    }
-  }
+  // items (configuration k of the list, revolute source r), spread over the
+  // whole block: a configuration's sc elements are adjacent items
+  bp_sincos_items((uint32_t)tid, (uint32_t)BLOCK, total, (uint32_t)w.n_rev, [&](uint32_t k, uint32_t ri) {
+    const long long r = cfg0 + list[k];
+    const int src = w.rev_src[ri];
+    double sv, cv;
+    mpg_sincos(in[r * w.dof + src], &sv, &cv);
+    sc[(r * w.dof + src) * 2] = sv;
+    sc[(r * w.dof + src) * 2 + 1] = cv;
+  });
 }
 
 // ---------------------------------------------------------------------------

@@ -8,6 +8,8 @@
 #   12 full without the static-partner bounding tests, 13 FK without the
 #   rq stores, 14 launch + output zeroing only, 15 full with the lookup grids
 #   off (the moving-static sphere tests of every object, as before the grids)
+#   16 bounding tests + SAT without the support-height part of the fused
+#   pass (mode 8 minus mode 16 = the support-height axes alone)
 # usage: bash tools/cull_iso.sh <out dir> [bench args]
 set -o pipefail
 OUT=${1:-gpurun_out/cull_iso}; shift
